@@ -89,7 +89,15 @@ def parse():
                         "exactly those steps out of a rocprofv3 kernel trace (build, warm-up, roofline replays and RNG kernels excluded)")
     p.add_argument("--dry-run", action="store_true",
                    help="multi-rank plumbing only, on CPU over gloo, NO device work (for tests): the JSON line is marked as such")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write every layer output of the LAST timed step as DIR/<index>_<layer>.npy (float32, rank 0); "
+                        "at most 64 MB in all: an output beyond its share is a fixed, seeded sample of its elements (see dump_outputs)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload in ("sdxl_unet_all", "sdxl_attn_int8", "flux_attn_int8") or args.dry_run):
+        p.error(f"--dump-outputs is not implemented for {'--dry-run' if args.dry_run else '--workload ' + args.workload}")
+    return args
 
 
 def workload_config(name: str):
@@ -225,17 +233,57 @@ def link_shared_input_layers(layers):
 
 
 @torch.no_grad()
-def run_step(layers):
+def run_step(layers, keep_outputs=False):
     """One pass over every layer (under no_grad, the state every inference pipeline runs its model in -- the reference decorates each forward
     with its inference context).  The activation-quantization cache is emptied first: within a step a tensor consumed by
-    several layers is quantized once (sdnq_amd/linear.py:_ActivationCache), but nothing is carried across steps."""
+    several layers is quantized once (sdnq_amd/linear.py:_ActivationCache), but nothing is carried across steps.
+    Returns the last layer's output, or with `keep_outputs` the list of every layer's output (all of them stay allocated)."""
     from sdnq_amd import linear as L
     L.clear_activation_cache()
     out = None
-    for (_, mod, x, *_rest) in layers:
-        out = mod(x)
+    if keep_outputs:
+        out = [mod(x) for (_, mod, x, *_rest) in layers]
+    else:
+        for (_, mod, x, *_rest) in layers:
+            out = mod(x)
     L.join_weight_pipeline()  # per-call mode: a weight prefetch nobody consumed re-joins the stream (no-op otherwise)
     return out
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: everything written, .npy headers included
+
+
+def dump_outputs(outs, layers, out_dir):
+    """--dump-outputs: every layer output of one step as out_dir/<index>_<layer>.npy, float32 (bfloat16 / float16 values are exact in it).
+    The byte budget is shared out smallest output first, each taking at most an equal part of what is left; an output larger than its
+    share is written as a 1-D sample of that many elements, one from each of as many equal runs of its flattened elements, the position
+    inside the run drawn by numpy's default_rng(layer index).  Which elements are written depends only on the layer list, so two builds
+    run with the same arguments write the same elements."""
+    import re
+
+    import numpy as np
+    assert len(outs) == len(layers), (len(outs), len(layers))
+    os.makedirs(out_dir, exist_ok=True)
+    left = (DUMP_BYTES - 256 * len(outs)) // 4  # float32 elements, after a generous 256 bytes of header per file
+    share = {}
+    for i in sorted(range(len(outs)), key=lambda i: (outs[i].numel(), i)):
+        share[i] = min(outs[i].numel(), left // (len(outs) - len(share)))
+        left -= share[i]
+    written, sampled = 0, 0
+    for i, (t, l) in enumerate(zip(outs, layers)):
+        if share[i] == t.numel():
+            a = t.detach().float().cpu().numpy()
+        else:
+            n = share[i]
+            edges = np.arange(n + 1, dtype=np.int64) * t.numel() // n
+            idx = edges[:-1] + (np.random.default_rng(i).random(n) * np.diff(edges)).astype(np.int64)
+            a = t.detach().reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device)).float().cpu().numpy()
+            sampled += 1
+        path = os.path.join(out_dir, f"{i:04d}_{re.sub(r'[^A-Za-z0-9_.+-]', '_', l[0])}.npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    assert written <= DUMP_BYTES, written
+    return {"dir": out_dir, "arrays": len(outs), "sampled_arrays": sampled, "bytes": written, "dtype": "float32"}
 
 
 def resident_weight_bytes(layers):
@@ -1133,6 +1181,8 @@ def main():
                 self.xs = [l[2] for l in layers]
 
             def forward(self, x0):
+                if args.dump_outputs:
+                    return [mod(x) for mod, x in zip(self.mods, self.xs)]
                 out = None
                 for mod, x in zip(self.mods, self.xs):
                     out = mod(x)
@@ -1187,20 +1237,25 @@ def main():
             from sdnq_amd import ops as _ops
             _ops.reset_fused_calls()
             with torch.cuda.graph(graph, stream=side):
-                run_step(layers)
+                graph_outs = run_step(layers, keep_outputs=bool(args.dump_outputs))  # (the graph's own buffers: every replay rewrites them)
             one_launch = _ops.fused_call_count()
         torch.cuda.synchronize()
 
+    last_outs = [None]  # --dump-outputs: every layer output of the latest step (held only then)
+
     def step():
         if captured is not None:
-            captured(captured_x0)
+            out = captured(captured_x0)
         elif compiled is not None:
             with torch.no_grad():
-                compiled()
+                out = compiled()
         elif graph is not None:
             graph.replay()
+            out = graph_outs
         else:
-            run_step(layers)
+            out = run_step(layers, keep_outputs=bool(args.dump_outputs))
+        if args.dump_outputs:
+            last_outs[0] = out
 
     for _ in range(args.warmup):
         step()
@@ -1229,6 +1284,9 @@ def main():
 
     if tp_peer is not None:
         tp_peer.check()  # a rendezvous that timed out (a rank out of step) is an error, not a number
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs on the device (outside the timed region)
+        dumped = dump_outputs(last_outs[0], layers, args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     replicas = 1 if tp or not distributed else world
     total_ops = ops_per_step * args.steps * replicas
@@ -1264,6 +1322,7 @@ def main():
                    "gather": args.tp_gather, "m_chunks": args.tp_chunks if args.tp_gather == "rccl" else 1}} if tp else {}),
         "tokens_per_s": round(tokens * replicas / (ms_per_step / 1e3), 1),
         "step_latency_ms": round(ms_per_step, 4),
+        **({"dump_outputs": dumped} if dumped else {}),
     }
 
     gathers = None

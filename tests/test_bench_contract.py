@@ -62,3 +62,40 @@ def test_gpus_8_dry_run_through_the_drivers_launcher():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 8 and j["steps"] == 2 and j["dry_run"] is True and j["scaling"] == "weak"
     assert j["ms_per_step"] >= 8.0  # rank r sleeps (r + 1) ms per step: rank 7's 8 ms is the step, not rank 0's 1 ms
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-run"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_is_refused_where_it_is_not_implemented():
+    r = subprocess.run([sys.executable, BENCH, "--workload", "sdxl_attn_int8", "--dump-outputs", "unused"], capture_output=True, text=True,
+                       env=_env(), timeout=300)
+    assert r.returncode != 0 and "--dump-outputs is not implemented" in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """bench.dump_outputs on CPU tensors: small outputs whole and exact, large ones a 1-D sample of their own values, the files within
+    the byte budget, and the same elements written on every call (two builds are compared output for output)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 400_000)
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randn(s, generator=g).to(torch.bfloat16) for s in [(1, 320)] * 3 + [(256, 320)] * 4 + [(1, 8, 16, 16)]]
+    layers = [(f"blk{i}.attn/to_q",) for i in range(len(outs))]
+    info = [bench.dump_outputs(outs, layers, str(tmp_path / d)) for d in ("a", "b")]
+    assert info[0]["arrays"] == len(outs) and 0 < info[0]["sampled_arrays"] < len(outs) and info[0]["bytes"] <= 400_000
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == len(outs) and names[0] == "0000_blk0.attn_to_q.npy"
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) == info[0]["bytes"]
+    for i, n in enumerate(names):
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        ref = outs[i].float().numpy()
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        if a.shape == ref.shape:
+            assert np.array_equal(a, ref)
+        else:
+            assert a.ndim == 1 and a.size < ref.size and np.isin(a, ref.ravel()).all()

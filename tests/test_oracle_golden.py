@@ -198,83 +198,7 @@ def test_conv_case_dequant_and_forward(name):
             assert np.abs(y - ref).max() <= lim * scale, (name, i, float(np.abs(y - ref).max()), scale)
 
 
-def test_golden_fixtures_are_what_the_reference_computes():
-    """Provenance (build container only: the reference does not travel): `make_golden.py --verify` rebuilds the reference layer of
-    every Linear / conv fixture from the STORED tensors and requires the stored outputs from the reference's own forward."""
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/sdnq"):
-        pytest.skip("the reference is not present on this box")
-    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_golden.py"), "--verify"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "mismatching outputs: 0" in r.stdout
-
-
-@pytest.mark.parametrize("tool,args,ok", [("fuzz_oracle_vs_reference.py", ["7", "60"], "0 mismatches"), ("fuzz_quantizer_vs_reference.py", ["7", "80"], "0 mismatches")])
-def test_random_sweeps_against_the_imported_reference(tool, args, ok):
-    """Build container only: beyond the committed fixtures, the ORACLE's forwards and the host-side load-time QUANTIZER are swept
-    against the imported reference over random configurations and shapes (round 4: 630 forwards / 300 layers clean after the oracle
-    stopped restating forms it had never been pinned on)."""
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/sdnq"):
-        pytest.skip("the reference is not present on this box")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", tool), *args], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and ok in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
-
-
-def test_checkpoint_fixture_is_what_the_reference_writes(tmp_path):
-    """Build container only: tests/golden/checkpoint_tiny regenerates byte for byte (tensors, both json files, the re-loaded model's
-    layer inputs / outputs) from the reference's quantizer, save_sdnq_model and load_sdnq_model."""
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/sdnq"):
-        pytest.skip("the reference is not present on this box")
-    out = str(tmp_path / "ckpt")
-    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_golden_checkpoint.py"), out], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
-    for f in ("config.json", "quantization_config.json", "model.safetensors"):
-        assert open(os.path.join(out, f), "rb").read() == open(os.path.join(GOLD, "checkpoint_tiny", f), "rb").read(), f
-    a, b = np.load(os.path.join(out, "io.npz")), np.load(os.path.join(GOLD, "checkpoint_tiny", "io.npz"))
-    assert sorted(a.files) == sorted(b.files) and all(np.array_equal(a[k], b[k]) for k in a.files)
-
-
-def test_reference_loads_what_save_sdnq_model_wrote(tmp_path):
-    """Build container only: a checkpoint written by sdnq_amd.save_sdnq_model (from the model sdnq_amd.load_sdnq_model built out of the
-    fixture) is read by the REFERENCE's load_sdnq_model, and the reference's forward on it reproduces the fixture's outputs bit for bit."""
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/sdnq"):
-        pytest.skip("the reference is not present on this box")
-    import json
-    import sdnq_amd
-    from tests.test_host_logic import TinyNet
-    src = os.path.join(GOLD, "checkpoint_tiny")
-    model = sdnq_amd.load_sdnq_model(src, model_cls=TinyNet, device="cpu")
-    model.config = json.load(open(os.path.join(src, "config.json")))  # (the constructor arguments, as diffusers' save_pretrained writes them)
-    out = str(tmp_path / "ours")
-    sdnq_amd.save_sdnq_model(model, out)
-    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_golden_checkpoint.py"), "--verify", out], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "reproduced" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
-
-
-def test_hf_checkpoint_fixture_is_what_the_reference_plugin_writes(tmp_path):
-    """Build container only: tests/golden/checkpoint_hf_tiny regenerates from the reference's transformers plugin -- tensors and stored
-    logits byte for byte, the config up to the order of `modules_to_not_convert` (the reference builds it from a set)."""
-    import json
-    import subprocess
-    import sys
-    if not os.path.isdir("/root/reference/src/sdnq"):
-        pytest.skip("the reference is not present on this box")
-    out = str(tmp_path / "ckpt")
-    r = subprocess.run([sys.executable, os.path.join(GOLD, "make_golden_hf.py"), out], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
-    src = os.path.join(GOLD, "checkpoint_hf_tiny")
-    assert open(os.path.join(out, "model.safetensors"), "rb").read() == open(os.path.join(src, "model.safetensors"), "rb").read()
-    a, b = np.load(os.path.join(out, "io.npz")), np.load(os.path.join(src, "io.npz"))
-    assert sorted(a.files) == sorted(b.files) and all(np.array_equal(a[k], b[k]) for k in a.files)
-    ca, cb = json.load(open(os.path.join(out, "config.json"))), json.load(open(os.path.join(src, "config.json")))
-    for c in (ca, cb):
-        c["quantization_config"]["modules_to_not_convert"] = sorted(c["quantization_config"]["modules_to_not_convert"])
-    assert ca == cb
+# Where the fixtures come from is checked by the scripts that made them, run by hand on a host where the reference is installed
+# (they execute the reference's own code, which is not part of this repository): tests/golden/make_golden.py --verify,
+# make_golden_checkpoint.py [--verify DIR], make_golden_hf.py DIR, and the random sweeps tools/fuzz_oracle_vs_reference.py and
+# tools/fuzz_quantizer_vs_reference.py.  The tests above pin the oracle to the stored fixtures alone.
