@@ -298,6 +298,22 @@ int sdnq_hip_linear_float_multi(const void* x, const void* wd, const void* bias,
  * [Hadamard rotation in out dtype].  out: [N][K] row-major of out_dtype. */
 int sdnq_hip_dequant(const SdnqWeight* w, int hadamard_group, void* out, int out_dtype, sdnq_stream_t stream);
 
+/* ---- quantized embedding: gather + dequantize ------------------------------------------------
+ * replaces quantized_embedding / quantized_embedding_forward (layers/embedding/forward.py:14-91): for every id
+ *     out[i][:] = embed_scale * hadamard( cast( dequant(W[ids[i]]) [+ svd_up[ids[i]] @ svd_down] ) )
+ * in ONE launch that reads only the gathered rows.  `w` describes the table exactly as for sdnq_hip_dequant with n = V rows of
+ * k = D columns (positions 0 / 1); D % 16 == 0.  Rounding order: w * scale (+ zero_point) in the scale dtype (dequantizer.py:27, 63);
+ * with SVD factors, a table of one group per row rounds to the svd dtype and adds the rank-R product with fp32 accumulation
+ * (addmm_, dequantizer.py:79-83), a grouped table adds the svd-dtype product in the scale dtype (the reference's 3-D
+ * weight[ids] takes the `is_conv` branch, dequantizer.py:76-77); cast to out_dtype; Hadamard rotation per hadamard_group columns
+ * in out_dtype (0 = none, else a power of two in [4, 512] dividing D; quant_utils.py:194-209); then, if has_embed_scale,
+ * out = round(out * (float)embed_scale) (result.mul_(embed_scale), forward.py:65-66).
+ * ids: n_ids indices of ids_dtype (SdnqIds), any shape flattened.  The read index is clamped to [0, V-1]: an id outside [0, V)
+ * never addresses outside the table and yields a row of NaN.  out: [n_ids][D] of out_dtype, 16-byte aligned. */
+typedef enum SdnqIds { SDNQ_IDS_I32 = 0, SDNQ_IDS_I64 = 1 } SdnqIds;
+int sdnq_hip_embedding(const SdnqWeight* w, int hadamard_group, const void* ids, int ids_dtype, int64_t n_ids,
+                       int has_embed_scale, double embed_scale, void* out, int out_dtype, sdnq_stream_t stream);
+
 /* ---- a7: re-quantize for matmul ---------------------------------------------------------------
  * replaces re_quantize_matmul (dequantizer.py:204-239): fp32 dequant (Hadamard NOT undone), then a
  * per-output-row symmetric quantization to the matmul dtype. wq: physical [N][K]; ws: [N] f32. */

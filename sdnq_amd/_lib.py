@@ -19,6 +19,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 F32, BF16, F16 = 0, 1, 2
 MM_I8, MM_FP8, MM_F16 = 0, 1, 2
 ST_PACKED_U8, ST_PACKED_I16, ST_RAW8, ST_RAW16 = 0, 1, 2, 3
+IDS_I32, IDS_I64 = 0, 1
 KIND_INT, KIND_UINT, KIND_FLOAT, KIND_UFLOAT = 0, 1, 2, 3
 
 EXPORTS = [
@@ -35,7 +36,7 @@ EXPORTS = [
     "sdnq_hip_signal_alloc", "sdnq_hip_signal_free", "sdnq_hip_ipc_export", "sdnq_hip_ipc_import", "sdnq_hip_ipc_close",
     "sdnq_hip_linear_w8a8_fused", "sdnq_hip_linear_w8a8_fused_supported", "sdnq_hip_scaled_mm_lp_uzp_svd", "sdnq_hip_stream_capture_id",
     "sdnq_hip_scaled_mm_tile", "sdnq_hip_lut4_build", "sdnq_hip_scaled_mm_w4", "sdnq_hip_scaled_mm_w4_supported",
-    "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16",
+    "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding",
 ]
 
 
@@ -156,6 +157,7 @@ def _declare(lib):
     lib.sdnq_hip_push_post.argtypes = [pvp, i32, i32, c.c_uint64, c.c_uint64, vp]
     lib.sdnq_hip_push_columns.argtypes = [vp, i32, i64, i64, i64, pvp, pvp, pvp, i32, i32, c.c_uint64, i64, i64, i64, vp, vp, i32, vp]
     lib.sdnq_hip_dequant.argtypes = [c.POINTER(SdnqWeight), i32, vp, i32, vp]
+    lib.sdnq_hip_embedding.argtypes = [vp, i32, vp, i32, i64, i32, c.c_double, vp, i32, vp]  # (the SdnqWeight by address: csrc/binding.c serves it too)
     lib.sdnq_hip_requant.argtypes = [c.POINTER(SdnqWeight), i32, vp, vp, vp]
     lib.sdnq_hip_requant_ws.argtypes = [c.POINTER(SdnqWeight), i32, vp, vp, i32, vp]
     lib.sdnq_hip_linear.argtypes = [c.POINTER(SdnqLinearArgs), vp]

@@ -41,6 +41,7 @@ static __typeof__(&sdnq_hip_linear_w8a16_grouped) f_linear_w8a16_grouped;
 static __typeof__(&sdnq_hip_linear_float) f_linear_float;
 static __typeof__(&sdnq_hip_prefetch_hint) f_prefetch_hint;
 static __typeof__(&sdnq_hip_linear_w8a8_fused) f_linear_w8a8_fused;
+static __typeof__(&sdnq_hip_embedding) f_embedding;
 
 #define NOT_READY(f) if (!(f)) { PyErr_SetString(PyExc_RuntimeError, "sdnq_amd._binding.init(path) has not been called"); return NULL; }
 
@@ -97,6 +98,19 @@ static PyObject* w_linear_w8a8_fused(PyObject* s, PyObject* const* args, Py_ssiz
     return PyLong_FromLong(f_linear_w8a8_fused(I(0), P(1), I(2), L(3), L(4), L(5), P(6), (const float*)P(7), P(8), I(9), P(10), I(11), L(12), P(13)));
 }
 
+/* sdnq_hip_embedding: argument 0 is the address of the SdnqWeight, argument 6 (embed_scale) a Python float; a decode step gathers ONE
+ * row, so the call is host-bound (kernel ~3.5 us, the ctypes call around it ~6 us) */
+static PyObject* w_embedding(PyObject* s, PyObject* const* args, Py_ssize_t n) {
+    i64 a[10]; (void)s; NOT_READY(f_embedding);
+    if (n != 10) { PyErr_Format(PyExc_TypeError, "sdnq_hip_embedding takes 10 arguments (%zd given)", n); return NULL; }
+    PyObject* iargs[10];
+    for (int i = 0; i < 10; ++i) iargs[i] = (i == 6) ? Py_None : args[i];
+    if (ints(iargs, 10, 10, a, "sdnq_hip_embedding")) return NULL;
+    const double es = PyFloat_AsDouble(args[6]);
+    if (es == -1.0 && PyErr_Occurred()) return NULL;
+    return PyLong_FromLong(f_embedding((const SdnqWeight*)P(0), I(1), P(2), I(3), L(4), I(5), es, P(7), I(8), P(9)));
+}
+
 static PyObject* w_prefetch_hint(PyObject* s, PyObject* const* args, Py_ssize_t n) {
     i64 a[8]; (void)s; NOT_READY(f_prefetch_hint);
     if (ints(args, n, 8, a, "sdnq_hip_prefetch_hint")) return NULL;
@@ -113,14 +127,14 @@ static PyObject* w_init(PyObject* s, PyObject* arg) {
     if (!h) { PyErr_Format(PyExc_OSError, "dlopen(%s): %s", path, dlerror()); return NULL; }
 #define R(name) do { *(void**)(&f_##name) = dlsym(h, "sdnq_hip_" #name); if (!f_##name) { PyErr_SetString(PyExc_OSError, "missing symbol sdnq_hip_" #name); return NULL; } } while (0)
     R(rowquant); R(scaled_mm); R(linear_w8a8); R(scaled_mm_grouped); R(scaled_mm_lowrank); R(lowrank_down); R(linear_w8a16);
-    R(linear_w8a16_grouped); R(linear_float); R(prefetch_hint); R(linear_w8a8_fused);
+    R(linear_w8a16_grouped); R(linear_float); R(prefetch_hint); R(linear_w8a8_fused); R(embedding);
 #undef R
     Py_RETURN_NONE;
 }
 
 #define M(name) {"sdnq_hip_" #name, (PyCFunction)(void (*)(void))w_##name, METH_FASTCALL, "see include/sdnq_hip.h"}
 static PyMethodDef methods[] = {M(rowquant), M(scaled_mm), M(linear_w8a8), M(scaled_mm_grouped), M(scaled_mm_lowrank), M(lowrank_down),
-                                M(linear_w8a16), M(linear_w8a16_grouped), M(linear_float), M(prefetch_hint), M(linear_w8a8_fused),
+                                M(linear_w8a16), M(linear_w8a16_grouped), M(linear_float), M(prefetch_hint), M(linear_w8a8_fused), M(embedding),
                                 {"init", (PyCFunction)w_init, METH_O, "init(path of libsdnq_hip.so)"},
                                 {NULL, NULL, 0, NULL}};
 static struct PyModuleDef moddef = {PyModuleDef_HEAD_INIT, "_binding", "typed binding of libsdnq_hip.so's hot entry points", -1, methods,

@@ -2,6 +2,7 @@
 //
 //   sdnq_hip_dequant   <- SDNQDequantizer.__call__ / dequantize_weight   (dequantizer.py:135-162, 389-429)
 //                         dequantize_symmetric :52-84, dequantize_asymmetric :15-48
+//   sdnq_hip_embedding <- quantized_embedding (layers/embedding/forward.py:14-68): weight[ids] dequantized, one launch
 //   sdnq_hip_requant   <- re_quantize_matmul -> re_quantize_int_mm / re_quantize_fp_mm
 //                         (dequantizer.py:204-239, 166-174, 190-201; quantize_int_mm quant_utils.py:265-273)
 //   sdnq_hip_linear_float <- torch.nn.functional.linear on the dequantized weight
@@ -108,6 +109,85 @@ __global__ __launch_bounds__(256) void dequant_kernel(const DeqParams p, void* _
         for (int j = 0; j < 16; ++j) v[j] = FT<SVD_T>::round(v[j] + acc[j]);
     }
     uint8_t* o = (uint8_t*)out + (n * p.K + k0) * FT<OUT_T>::bytes;
+    if constexpr (OUT_T == SDNQ_F32) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(uint4*)(o + 16 * q) = Vec16<SDNQ_F32>::pack(v + 4 * q);
+    } else {
+        *(uint4*)o = Vec16<OUT_T>::pack(v);
+        *(uint4*)(o + 16) = Vec16<OUT_T>::pack(v + 8);
+    }
+}
+
+// Gather-dequantize of an embedding table (layers/embedding/forward.py:14-68): one wave per (id, 1024-column chunk of the row),
+// a lane owns 16 consecutive columns.  Only the gathered rows of codes / scales / zero points / svd_up are read; svd_down [R][D]
+// is shared by every row and stays in L2.  The read row is clamped to [0, V-1], so no address leaves the table; an id outside
+// [0, V) writes a row of NaN instead.  Rounding order of the reference on weight[ids] (dequantizer.py:15-84):
+//   v = w * s (+ zp) in the scale dtype (dequant16)
+//   SVD, table not grouped:  v = round_svd(round_svd(v) + sum_r up[r] * down[r])          result.to(svd dtype).addmm_(up, down)
+//   SVD, grouped table:      v = round_sdt(v + round_svd(sum_r up[r] * down[r]))           the 3-D weight[ids] takes the
+//                            `is_conv` branch: result.add_(torch.mm(up, down).unflatten(..)) in the scale dtype
+//   cast to OUT_T; Hadamard rotation in OUT_T (wave_hadamard16: the arithmetic of sdnq_hip_hadamard); v = round(v * embed_scale)
+template <int OUT_T, int SVD_T>
+__global__ __launch_bounds__(256) void embedding_kernel(const DeqParams p, const void* __restrict__ ids, int ids64, int64_t n_ids,
+                                                        int log2g, int has_es, float es, void* __restrict__ out) {
+    const int64_t chunks = (p.K + 1023) / 1024;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= n_ids * chunks) return;  // wave-uniform: the lanes that stay run the cross-lane rotation together
+    int64_t i, c;
+    divmod(wave, chunks, i, c);
+    const int64_t id = ids64 ? ((const int64_t*)ids)[i] : (int64_t)((const int32_t*)ids)[i];
+    const bool valid = id >= 0 && id < p.N;
+    const int64_t row = id < 0 ? 0 : (id >= p.N ? p.N - 1 : id);
+    const int64_t k0 = c * 1024 + (threadIdx.x & 63) * 16;
+    const bool active = k0 < p.K;
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = 0.0f;
+    if (active) {
+        dequant16(p, row, k0, v);
+        if (p.svd_up) {
+            float acc[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+            for (int r = 0; r < p.rank; ++r) {
+                const float up = FT<SVD_T>::load(p.svd_up, row * p.rank + r);
+                float dn[16];
+                if constexpr (SVD_T == SDNQ_F32) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p.svd_down + (int64_t)r * p.K + k0 + 4 * q), dn + 4 * q);
+                } else {
+                    Vec16<SVD_T>::unpack(*(const uint4*)((const uint16_t*)p.svd_down + (int64_t)r * p.K + k0), dn);
+                    Vec16<SVD_T>::unpack(*(const uint4*)((const uint16_t*)p.svd_down + (int64_t)r * p.K + k0 + 8), dn + 8);
+                }
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] = fmaf(up, dn[j], acc[j]);
+            }
+            if (p.G > 1) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = round_rt(v[j] + FT<SVD_T>::round(acc[j]), p.sdt);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = FT<SVD_T>::round(FT<SVD_T>::round(v[j]) + acc[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = FT<OUT_T>::round(v[j]);
+    if (log2g) {
+        wave_hadamard16(v, log2g, hadamard_scale(log2g, OUT_T));
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = FT<OUT_T>::round(v[j]);
+    }
+    if (has_es) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = FT<OUT_T>::round(v[j] * es);
+    }
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = __builtin_nanf("");
+    }
+    if (!active) return;
+    uint8_t* o = (uint8_t*)out + (i * p.K + k0) * FT<OUT_T>::bytes;
     if constexpr (OUT_T == SDNQ_F32) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) *(uint4*)(o + 16 * q) = Vec16<SDNQ_F32>::pack(v + 4 * q);
@@ -1076,6 +1156,44 @@ extern "C" int sdnq_hip_dequant(const SdnqWeight* w, int hadamard_group, void* o
 #undef DQ_CASE
     SDNQ_CHECK_LAUNCH();
     if (hadamard_group != 0) return sdnq_hip_hadamard(out, out_dtype, p.N, p.K, p.K, hadamard_group, out, p.K, stream);
+    return SDNQ_OK;
+}
+
+extern "C" int sdnq_hip_embedding(const SdnqWeight* w, int hadamard_group, const void* ids, int ids_dtype, int64_t n_ids,
+                                  int has_embed_scale, double embed_scale, void* out, int out_dtype, sdnq_stream_t stream) {
+    DeqParams p{};
+    int st = fill_params(w, p);
+    if (st != SDNQ_OK) return st;
+    if (w->positions > 1) return SDNQ_ERR_SHAPE;
+    if (!out || (!ids && n_ids > 0)) return SDNQ_ERR_NULL;
+    if (out_dtype < 0 || out_dtype > 2 || (ids_dtype != SDNQ_IDS_I32 && ids_dtype != SDNQ_IDS_I64)) return SDNQ_ERR_DTYPE;
+    if (n_ids < 0) return SDNQ_ERR_SHAPE;
+    int log2g = 0;
+    if (hadamard_group != 0) {
+        while ((1 << log2g) < hadamard_group) ++log2g;
+        if (hadamard_group < 4 || hadamard_group > 512 || (1 << log2g) != hadamard_group || (p.K % hadamard_group) != 0) return SDNQ_ERR_SHAPE;
+    }
+    if ((uintptr_t)out % 16 || (p.svd_up && (uintptr_t)p.svd_down % 16)) return SDNQ_ERR_ALIGN;
+    if (n_ids == 0) return SDNQ_OK;
+    const int64_t waves = n_ids * ((p.K + 1023) / 1024);
+    if ((waves + 3) / 4 > 0x7fffffff) return SDNQ_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+    const int svd_t = p.svd_up ? w->svd_dtype : out_dtype;
+    const int ids64 = ids_dtype == SDNQ_IDS_I64;
+    const float es = (float)embed_scale;  // a Python float multiplies in the tensor's op-math type (float32 for 16-bit and f32 tensors)
+#define EMB_CASE(O, S) \
+    if (out_dtype == O && svd_t == S) hipLaunchKernelGGL((embedding_kernel<O, S>), grid, block, 0, s, p, ids, ids64, n_ids, log2g, has_embed_scale, es, out);
+    EMB_CASE(SDNQ_F32, SDNQ_F32)
+    else EMB_CASE(SDNQ_F32, SDNQ_BF16)
+    else EMB_CASE(SDNQ_F32, SDNQ_F16)
+    else EMB_CASE(SDNQ_BF16, SDNQ_BF16)
+    else EMB_CASE(SDNQ_BF16, SDNQ_F32)
+    else EMB_CASE(SDNQ_F16, SDNQ_F16)
+    else EMB_CASE(SDNQ_F16, SDNQ_F32)
+    else return SDNQ_ERR_DTYPE;
+#undef EMB_CASE
+    SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
 }
 

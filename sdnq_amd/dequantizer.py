@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .common import conv_types, dtype_dict, linear_types
+from .common import conv_types, dtype_dict, embedding_types, linear_types
 
 
 @dataclass
@@ -102,8 +102,8 @@ class SDNQDequantizer:
     def quant_weight(self, weight, scale, zero_point=None, svd_up=None, svd_down=None) -> ops.QuantWeight:
         if self.use_codebook:
             raise NotImplementedError("use_codebook (Lloyd-Max LUT) is outside the MI355X hot path (SURVEY 8a note)")
-        if self.layer_class_name not in linear_types and self.layer_class_name not in conv_types:
-            raise NotImplementedError(f"{self.layer_class_name}: only Linear and Conv1d / Conv2d / Conv3d layers are built for MI355X")
+        if self.layer_class_name not in linear_types and self.layer_class_name not in conv_types and self.layer_class_name not in embedding_types:
+            raise NotImplementedError(f"{self.layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X")
         n, k, pos = self.out_features, self.in_features, self.kernel_positions
         group = self.group_size if self.group_size > 0 else k // pos
         return ops.make_quant_weight(self.weights_dtype, weight, scale, zero_point, svd_up, svd_down, n, k, group,

@@ -8,9 +8,12 @@ from .common import conv_transpose_types, conv_types, dtype_dict, embedding_type
 
 
 def get_forward_func(layer_class_name: str, quantized_matmul_dtype: str, use_quantized_matmul: bool) -> Callable:
-    if layer_class_name in embedding_types or layer_class_name in conv_transpose_types:
+    if layer_class_name in embedding_types:  # forward.py:7-9
+        from .embedding import quantized_embedding_forward
+        return quantized_embedding_forward
+    if layer_class_name in conv_transpose_types:
         raise NotImplementedError(
-            f"{layer_class_name}: only Linear and Conv1d / Conv2d / Conv3d layers are built for MI355X (quant_embedding and transposed "
+            f"{layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X (transposed "
             "convolutions are outside SURVEY 8)")
     if layer_class_name in conv_types:  # forward.py:10-28
         from . import conv

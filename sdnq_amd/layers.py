@@ -95,9 +95,11 @@ class SDNQLayer(torch.nn.Module):
 
 def _traceable(layer) -> bool:
     """Layers that trace as sdnq_hip:: operators under torch.compile: Linear (one or two operators, torch_ops.layer_plan) and the conv
-    layers (one opaque layer_forward operator each -- round 4: a compiled UNet has no graph breaks at its 49 quantized convs)."""
+    layers (one opaque layer_forward operator each -- round 4: a compiled UNet has no graph breaks at its 49 quantized convs) and the
+    embeddings (one layer_forward operator: the gather-dequantize launch)."""
     dq = layer.__dict__.get("sdnq_dequantizer")
-    return dq is not None and dq.layer_class_name in ("Linear", "SDNQLinear", "Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d")
+    return dq is not None and dq.layer_class_name in ("Linear", "SDNQLinear", "Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d",
+                                                      "Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding")
 
 
 class SDNQLinear(SDNQLayer, torch.nn.Linear):
@@ -116,7 +118,11 @@ class SDNQConv3d(SDNQLayer, torch.nn.Conv3d):
     original_class: torch.nn.Conv3d
 
 
-torch.serialization.add_safe_globals([SDNQLayer, SDNQLinear, SDNQConv1d, SDNQConv2d, SDNQConv3d])
+class SDNQEmbedding(SDNQLayer, torch.nn.Embedding):
+    original_class: torch.nn.Embedding
+
+
+torch.serialization.add_safe_globals([SDNQLayer, SDNQLinear, SDNQConv1d, SDNQConv2d, SDNQConv3d, SDNQEmbedding])
 
 
 def get_sdnq_wrapper_class(original_layer: torch.nn.Module, forward_func: Callable) -> SDNQLayer:
@@ -129,5 +135,7 @@ def get_sdnq_wrapper_class(original_layer: torch.nn.Module, forward_func: Callab
         return SDNQConv2d(original_layer, forward_func)
     if name == "Conv3d":
         return SDNQConv3d(original_layer, forward_func)
-    # transposed conv / embedding wrappers are not built
+    if name in ("Embedding", "Gemma4TextScaledWordEmbedding"):
+        return SDNQEmbedding(original_layer, forward_func)
+    # transposed conv wrappers are not built
     return SDNQLayer(original_layer, forward_func)

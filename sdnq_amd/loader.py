@@ -526,7 +526,8 @@ def apply_sdnq_options_to_model(model: torch.nn.Module, dtype: torch.dtype | Non
         if cls is None or getattr(module.sdnq_dequantizer, "use_codebook", False):
             continue
         conv = cls in ("Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d")
-        if not (conv or cls in ("Linear", "SDNQLinear")):
+        emb = cls in ("Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding")
+        if not (conv or emb or cls in ("Linear", "SDNQLinear")):
             continue
         fwd_now = getattr(module, "forward_func", None)
         if fwd_now is not None and not str(getattr(fwd_now, "__module__", "")).startswith("sdnq_amd"):
@@ -564,8 +565,8 @@ def apply_sdnq_options_to_model(model: torch.nn.Module, dtype: torch.dtype | Non
             module.scale = torch.nn.Parameter(module.scale.to(want_sdt), requires_grad=False)
             if getattr(module, "zero_point", None) is not None:
                 module.zero_point = torch.nn.Parameter(module.zero_point.to(want_sdt), requires_grad=False)
-        if conv:
-            # conv layers: result dtype and scale dtype only -- the reference leaves their matmul switch alone here
+        if conv or emb:
+            # conv and embedding layers: result dtype and scale dtype only -- the reference leaves their matmul switch alone here
             # (`current_use_quantized_matmul = None` for everything that is not a Linear, loader.py:244-255)
             module.forward_func = get_forward_func(dq.layer_class_name, dq.quantized_matmul_dtype, dq.use_quantized_matmul)
             module.__dict__.pop("_sdnq_hip_state", None)

@@ -596,6 +596,25 @@ def dequant(qw: QuantWeight, out_dtype: torch.dtype, hadamard_group: int = 0, us
     return out
 
 
+def embedding(qw: QuantWeight, ids: torch.Tensor, out_dtype: torch.dtype, hadamard_group: int = 0, embed_scale: float | None = None) -> torch.Tensor:
+    """quantized_embedding (layers/embedding/forward.py:14-68) in one launch: out = ids.shape + [D] rows of the dequantized table
+    (SVD added, Hadamard rotation, then * embed_scale).  ids: int32 / int64 of any shape on the table's device; an id outside
+    [0, V) gives a row of NaN (the kernel clamps its read index, nothing is checked on the host)."""
+    _require_cuda(ids)
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise _lib.SdnqHipError(f"embedding ids must be int32 or int64, got {ids.dtype}")
+    dev = qw.keep[0].device
+    if ids.device != dev:
+        raise _lib.SdnqHipError(f"embedding ids on {ids.device}, table on {dev}")
+    flat = ids if ids.is_contiguous() else ids.contiguous()
+    out = torch.empty((*ids.shape, qw.k), device=dev, dtype=out_dtype)
+    check(_lib.load().sdnq_hip_embedding(ctypes.addressof(qw.desc), hadamard_group, flat.data_ptr(),
+                                         _lib.IDS_I64 if ids.dtype == torch.int64 else _lib.IDS_I32, flat.numel(),
+                                         0 if embed_scale is None else 1, 0.0 if embed_scale is None else float(embed_scale),
+                                         out.data_ptr(), float_code(out_dtype), _stream(flat)), "embedding")
+    return out
+
+
 def requant(qw: QuantWeight, mm: int, ws: torch.Tensor | None = None, out: torch.Tensor | None = None):
     """re_quantize_int_mm / re_quantize_fp_mm (dequantizer.py:166-174, 204-239): (wq [N, K] int8 | fp8, ws [N] f32).  `ws`: the row
     scales of an earlier call on the same weights (sdnq_hip_requant_ws: the pass that derives them is skipped where the kernel can).

@@ -4,8 +4,8 @@ API names are the reference's (quantizer.py: SDNQConfig :846, sdnq_quantize_laye
 sdnq_quantize_layer :423, apply_sdnq_to_module :477, QuantizationMethod :60) so host code switches with an
 import change; the module/tensor layout produced is byte-compatible with reference checkpoints
 (SURVEY App. C), which tests/test_quantizer.py checks against the golden fixtures.  Only what feeds the Linear
-hot path is implemented: no HF/diffusers quantizer plugin, no dynamic dtype search, no codebook, no
-stochastic rounding, no conv/embedding (SURVEY 2, rows 12-16 marked out of scope).
+hot path is implemented: no dynamic dtype search, no codebook, no stochastic rounding, no transposed conv.
+Embedding layers (quant_embedding=True) take the reference's non-Linear branch.
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from enum import Enum
 import torch
 
 from . import packed
-from .common import conv_types, dtype_dict, linear_types, sdnq_version
+from .common import conv_types, dtype_dict, embedding_types, linear_types, sdnq_version
 from .dequantizer import SDNQDequantizer
 from .forward import get_forward_func
 from .layers import get_sdnq_wrapper_class
@@ -62,8 +62,7 @@ class SDNQConfig:
             raise ValueError(f"SDNQ only support weight dtypes in {sorted(dtype_dict)} but found {weights_dtype}")
         if quantized_matmul_dtype is not None and quantized_matmul_dtype not in {"int8", "uint8", "fp8", "fp16", "float8_e4m3fn", "float16"}:
             raise ValueError(f"unsupported quantized_matmul_dtype {quantized_matmul_dtype}")
-        for name in ("use_codebook", "use_dynamic_quantization", "use_stochastic_rounding", "quant_embedding",
-                     "is_training"):
+        for name in ("use_codebook", "use_dynamic_quantization", "use_stochastic_rounding", "is_training"):
             if locals()[name]:
                 raise NotImplementedError(f"SDNQConfig({name}=True) is outside the MI355X Linear hot path")
         self.weights_dtype = weights_dtype
@@ -165,8 +164,9 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
     quantize -> (transpose for direct matmul) -> pack.
     """
     is_conv = layer_class_name in conv_types
-    if layer_class_name not in linear_types and not is_conv:
-        raise NotImplementedError(f"{layer_class_name}: only Linear and Conv1d / Conv2d / Conv3d layers are built for MI355X")
+    is_embedding = layer_class_name in embedding_types
+    if layer_class_name not in linear_types and not is_conv and not is_embedding:
+        raise NotImplementedError(f"{layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X")
     weight = weight.detach()
     original_shape, original_stride = weight.shape, weight.stride()
     torch_dtype = weight.dtype if torch_dtype is None else torch_dtype
@@ -177,7 +177,8 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
         kpos *= int(d)
     k = channels * kpos
     mm_dtype = get_quantized_matmul_dtype(weights_dtype, quantized_matmul_dtype)
-    use_qmm = check_quantized_matmul_is_allowed(use_quantized_matmul, n, channels)
+    # embeddings take the reference's generic branch (quantizer.py:144-150): reduction along the last dim, no quantized matmul
+    use_qmm = False if is_embedding else check_quantized_matmul_is_allowed(use_quantized_matmul, n, channels)
     requant = _needs_requant(weights_dtype, mm_dtype)
     ent = dtype_dict[weights_dtype]
     result_shape = None
@@ -196,7 +197,7 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
         if use_qmm:  # the matmul branch consumes x @ svd_down then @ svd_up: store both transposed (:164-167)
             svd_up, svd_down = svd_up.t(), svd_down.t()
 
-    group_size, groups = _pick_group_size(group_size, channels, weights_dtype, not is_conv, svd_up is not None,
+    group_size, groups = _pick_group_size(group_size, channels, weights_dtype, layer_class_name in linear_types, svd_up is not None,
                                           direct_matmul=use_qmm and not requant)
     dim = 1 if (is_conv and not flat) else -1
     if groups > 1:
@@ -320,14 +321,20 @@ def _quant_kwargs(cfg: SDNQConfig, torch_dtype, param_name: str, layer_class_nam
     return kw
 
 
+def _quantizable_class(name: str, quantization_config: SDNQConfig) -> bool:
+    """Layer classes the config quantizes: Linear always, convs with quant_conv, embeddings with quant_embedding."""
+    return (name == "Linear" or (name in ("Conv1d", "Conv2d", "Conv3d") and quantization_config.quant_conv)
+            or (name in ("Embedding", "Gemma4TextScaledWordEmbedding") and quantization_config.quant_embedding))
+
+
 @torch.no_grad()
 def sdnq_quantize_layer(layer: torch.nn.Module, quantization_config: SDNQConfig, torch_dtype: torch.dtype | None = None,
                         param_name: str = "", quant_kwargs: dict | None = None):
-    """Quantize one Linear IN PLACE (the wrapper shares the layer's parameters) -> (SDNQLinear, config)."""
+    """Quantize one Linear / conv / Embedding IN PLACE (the wrapper shares the layer's parameters) -> (SDNQ layer, config)."""
     if torch_dtype is None:
         torch_dtype = layer.weight.dtype
     name = layer.__class__.__name__
-    if name not in linear_types and not (name in ("Conv1d", "Conv2d", "Conv3d") and quantization_config.quant_conv):  # quantizer.py:429-435
+    if not _quantizable_class(name, quantization_config):  # quantizer.py:429-435
         quantization_config.modules_to_not_convert.append(param_name)
         return layer, quantization_config
     kw = quant_kwargs or _quant_kwargs(quantization_config, torch_dtype, param_name, name)
@@ -350,21 +357,26 @@ def sdnq_quantize_layer(layer: torch.nn.Module, quantization_config: SDNQConfig,
 @torch.no_grad()
 def apply_sdnq_to_module(model: torch.nn.Module, quantization_config: SDNQConfig, torch_dtype: torch.dtype | None = None,
                          full_param_name: str = "", pre_quantized: bool = False):
-    """Recursively replace eligible nn.Linear / conv children by SDNQ layers (reference quantizer.py:477-495).  pre_quantized: the
-    model is the skeleton of a stored SDNQ checkpoint -- every Linear (and conv, with quant_conv) the config does not list in
+    """Recursively replace eligible nn.Linear / conv / embedding children by SDNQ layers (reference quantizer.py:477-495).  pre_quantized:
+    the model is the skeleton of a stored SDNQ checkpoint -- every Linear (conv with quant_conv, embedding with quant_embedding) the config does not list in
     modules_to_not_convert WAS quantized, whatever its size (utils.py:73-91: the size rules only decide at quantization time)."""
     for child_name, child in list(model.named_children()):
         pname = f"{full_param_name}.{child_name}" if full_param_name else child_name
         cname = child.__class__.__name__
-        if (cname == "Linear" or (cname in ("Conv1d", "Conv2d", "Conv3d") and quantization_config.quant_conv)) and getattr(child, "weight", None) is not None:
+        if _quantizable_class(cname, quantization_config) and getattr(child, "weight", None) is not None:
             wname = pname + ".weight"
             skip = check_param_name_in(wname, quantization_config.modules_to_not_convert) is not None
-            big = pre_quantized or (child.weight.shape[-1 if cname == "Linear" else 1] >= quantization_config.minimum_allowed_channel_size
+            big = pre_quantized or (child.weight.shape[1 if cname in conv_types else -1] >= quantization_config.minimum_allowed_channel_size
                                     and child.weight.numel() >= quantization_config.minimum_allowed_numel)
             if not skip and big and child.weight.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
                 child, quantization_config = sdnq_quantize_layer(child, quantization_config, torch_dtype=torch_dtype, param_name=wname)
                 setattr(model, child_name, child)
             elif not skip:
+                quantization_config.modules_to_not_convert.append(wname)
+        elif cname in embedding_types and getattr(child, "weight", None) is not None:
+            # an embedding without quant_embedding stays float and is listed, as the reference's check_quant_is_allowed does (utils.py:73-78)
+            wname = pname + ".weight"
+            if check_param_name_in(wname, quantization_config.modules_to_not_convert) is None:
                 quantization_config.modules_to_not_convert.append(wname)
         else:
             apply_sdnq_to_module(child, quantization_config, torch_dtype=torch_dtype, full_param_name=pname, pre_quantized=pre_quantized)

@@ -27,9 +27,9 @@ def unsupported_reason(module) -> str | None:
     if dq is None:
         return "not an SDNQ layer (no sdnq_dequantizer)"
     cls = getattr(dq, "layer_class_name", None)
-    if cls in embedding_types or cls in conv_transpose_types:
-        return f"{cls}: only Linear and Conv1d / Conv2d / Conv3d layers are built for MI355X (embeddings and transposed convolutions are outside SURVEY 8)"
-    if cls not in linear_types and cls not in conv_types:
+    if cls in conv_transpose_types:
+        return f"{cls}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X (transposed convolutions are outside SURVEY 8)"
+    if cls not in linear_types and cls not in conv_types and cls not in embedding_types:
         return f"{cls}: unknown layer class"
     if getattr(dq, "use_codebook", False):
         return "use_codebook (Lloyd-Max LUT) is outside the MI355X hot path (SURVEY 8a note)"
@@ -39,6 +39,8 @@ def unsupported_reason(module) -> str | None:
     qmm = bool(dq.use_quantized_matmul)
     sdt = _scale_dtype(module)
     lp = sdt is not None and sdt not in (torch.float32, torch.float64)
+    if cls in embedding_types:
+        return _embedding_reason(module, dq, sdt, lp)
     if lp and sdt != dq.result_dtype:
         return (f"scale dtype {sdt} differs from the layer's result dtype {dq.result_dtype}: 16-bit scales are built for the layout "
                 "apply_sdnq_options_to_model(dequantize_fp32=False) produces")
@@ -91,6 +93,31 @@ def unsupported_reason(module) -> str | None:
                        or (getattr(module, "zero_point", None) is not None and not dq.re_quantize_for_matmul)):
                 return ("grouped conv matmul with 16-bit scales is built for bfloat16 scales on the int8 / fp8 matmul without a weight zero point (float16: the reference "
                         "casts acc * input_scale to float16 before the weight scale, dequantizer.py:27, 63 -- an epilogue of its own)")
+    return None
+
+
+def _embedding_reason(module, dq, sdt, lp) -> str | None:
+    """The gather-dequantize kernel (sdnq_hip_embedding) takes a [V, D] table with D % 16 == 0 in every storage format of
+    sdnq_hip_dequant, float32 / bfloat16 / float16 results and SVD factors, and Hadamard groups of 4 .. 512."""
+    shape = tuple(int(d) for d in dq.original_shape)
+    if len(shape) != 2:
+        return f"embedding weight of shape {shape}: a [num_embeddings, embedding_dim] table is expected"
+    if shape[1] % 16:
+        return f"embedding_dim {shape[1]} is not a multiple of 16 (the gather kernel reads 16-element runs of a row)"
+    if dq.result_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return f"embedding result dtype {dq.result_dtype} is not built (float32, bfloat16, float16 are)"
+    if sdt is not None and sdt not in (torch.float32, dq.result_dtype):
+        return (f"scale dtype {sdt} differs from the layer's result dtype {dq.result_dtype}: 16-bit scales are built for the layout "
+                "apply_sdnq_options_to_model(dequantize_fp32=False) produces")
+    if lp and dtype_dict[dq.weights_dtype]["num_bits"] > 8:
+        return "16-bit scales with formats wider than 8 bits are not built (the codes are not exact in the scale dtype)"
+    up = getattr(module, "svd_up", None)
+    if up is not None and up.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return f"svd factors in {up.dtype} are not built"
+    if dq.use_hadamard:
+        g = int(dq.hadamard_group_size)
+        if g < 4 or g > 512 or g & (g - 1) or shape[1] % g:
+            return f"Hadamard group {g} on embedding_dim {shape[1]}: the fused rotation takes powers of two in [4, 512] dividing the row"
     return None
 
 

@@ -394,6 +394,8 @@ def layer_plan(module: torch.nn.Module):
 def _(input, handle):
     mod = _layer(handle)
     dq = mod.sdnq_dequantizer
+    if dq.layer_class_name in ("Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding"):  # ids -> ids.shape + [D] rows
+        return input.new_empty((*input.shape, int(dq.original_shape[-1])), dtype=dq.result_dtype)
     if dq.is_conv:
         # Conv1d / Conv2d / Conv3d: output geometry from the module's own attributes (the arithmetic of torch.nn.functional.conv*d;
         # non-zero padding modes pad explicitly by `padding` first, which gives the same extents)
