@@ -68,7 +68,12 @@ typedef enum SdnqKind {
     SDNQ_KIND_INT = 0,   /* signed int: stored as value - min (packed) or two's complement (raw) */
     SDNQ_KIND_UINT = 1,  /* unsigned int, asymmetric (zero_point required) */
     SDNQ_KIND_FLOAT = 2, /* signed eXmY "fn" float code (packed_float.py:86-132) */
-    SDNQ_KIND_UFLOAT = 3 /* unsigned eXmY "fnu" float code, asymmetric (zero_point required) */
+    SDNQ_KIND_UFLOAT = 3, /* unsigned eXmY "fnu" float code, asymmetric (zero_point required) */
+    SDNQ_KIND_CODEBOOK = 4 /* unsigned code indexing a table of L = 2^bits levels per (row, group) (use_codebook,
+                              dequantizer.py:88-131): the value is levels[n][g][code].  `scale` then points at the float32
+                              upcast of the level table, [N][G][L] for Linear / embedding tables and [N][G][L][P] for conv
+                              weights (positions P > 1: the level axis sits before the kernel positions); zero_point must be
+                              NULL; bits 1..8, stored as SDNQ_ST_PACKED_U8 (1..7) or SDNQ_ST_RAW8 (8) */
 } SdnqKind;
 
 /* A quantized Linear weight exactly as the reference state_dict holds it. */
@@ -393,6 +398,19 @@ int sdnq_hip_linear_skinny(const SdnqWeight* w, int hadamard_group, const void* 
  * nan_to_num, clamp, then the native conversion (fp8 e4m3fn / e5m2, fp16, bf16) or the reference's eXmY encoder. */
 int sdnq_hip_quantize_weight(const void* src, int src_dtype, int64_t ld_src, const SdnqWeight* w, float qmin,
                              float qmax, sdnq_stream_t stream);
+
+/* codebook (Lloyd-Max) form of the load-time quantizer: replaces quantize_weight_codebook (quant_utils.py:59-120) followed by
+ * pack_int.  For every reduction slice -- (row n, group g) of a Linear weight, (row, channel group, kernel position) of a conv
+ * weight -- in float32: lo, hi = min, max; s = (hi - lo) / (L - 1); levels[i] = fmaf(i, s, lo); then `steps` rounds of
+ *     sort the levels; mid[j] = (levels[j] + levels[j + 1]) * 0.5; code = #{j : mid[j] < w} (a value on a midpoint takes the
+ *     lower level); every level with members becomes the sum of its members, added in element order, divided by their count
+ * and a final sort; the codes are the final assignment against the sorted levels.  Results equal the reference's CPU
+ * arithmetic bit for bit (its scatter_add_ sums each level's members in element order).
+ * `w` describes the OUTPUT: kind SDNQ_KIND_CODEBOOK, w->weight receives the codes (storage / bits as above, element order
+ * [N][K]), w->scale the float32 levels in the layout of SDNQ_KIND_CODEBOOK; zero_point NULL, svd_* ignored.  The caller casts
+ * the levels to the scale dtype afterwards (dequantize_fp32=False).  group_size <= 16384 (one slice lives in LDS), steps in
+ * [0, 1024]; anything else: a validation status, nothing launched. */
+int sdnq_hip_quantize_codebook(const void* src, int src_dtype, int64_t ld_src, const SdnqWeight* w, int steps, sdnq_stream_t stream);
 
 /* ---- weight prefetch (round 5) -------------------------------------------------------------------
  * Pulls [ptr, ptr + bytes) into the memory-side cache (256-MiB Infinity Cache of MI355X): one 4-byte read per 128-byte line, nothing

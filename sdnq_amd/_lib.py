@@ -20,7 +20,7 @@ F32, BF16, F16 = 0, 1, 2
 MM_I8, MM_FP8, MM_F16 = 0, 1, 2
 ST_PACKED_U8, ST_PACKED_I16, ST_RAW8, ST_RAW16 = 0, 1, 2, 3
 IDS_I32, IDS_I64 = 0, 1
-KIND_INT, KIND_UINT, KIND_FLOAT, KIND_UFLOAT = 0, 1, 2, 3
+KIND_INT, KIND_UINT, KIND_FLOAT, KIND_UFLOAT, KIND_CODEBOOK = 0, 1, 2, 3, 4
 
 EXPORTS = [
     "sdnq_hip_version", "sdnq_hip_strerror", "sdnq_hip_device_supported", "sdnq_hip_rowquant",
@@ -36,7 +36,7 @@ EXPORTS = [
     "sdnq_hip_signal_alloc", "sdnq_hip_signal_free", "sdnq_hip_ipc_export", "sdnq_hip_ipc_import", "sdnq_hip_ipc_close",
     "sdnq_hip_linear_w8a8_fused", "sdnq_hip_linear_w8a8_fused_supported", "sdnq_hip_scaled_mm_lp_uzp_svd", "sdnq_hip_stream_capture_id",
     "sdnq_hip_scaled_mm_tile", "sdnq_hip_lut4_build", "sdnq_hip_scaled_mm_w4", "sdnq_hip_scaled_mm_w4_supported",
-    "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding",
+    "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding", "sdnq_hip_quantize_codebook",
 ]
 
 
@@ -172,6 +172,7 @@ def _declare(lib):
     lib.sdnq_hip_scaled_mm_strided.argtypes = [i32, vp, i64, vp, vp, vp, vp, i32, vp, i64, i32, i64, i64, i64, i64, vp]
     lib.sdnq_hip_linear_skinny.argtypes = [c.POINTER(SdnqWeight), i32, vp, vp, i32, vp, i64, i64, vp]
     lib.sdnq_hip_quantize_weight.argtypes = [vp, i32, i64, c.POINTER(SdnqWeight), c.c_float, c.c_float, vp]
+    lib.sdnq_hip_quantize_codebook.argtypes = [vp, i32, i64, c.POINTER(SdnqWeight), i32, vp]
     lib.sdnq_hip_linear_skinny_svd.argtypes = [c.POINTER(SdnqWeight), vp, vp, vp, i32, vp, i64, i64, vp]
     lib.sdnq_hip_linear_w8a8.argtypes = [i32, vp, i32, i64, i64, i64, i32, vp, vp, vp, vp, vp, i32, vp, i32, i64, vp]
     lib.sdnq_hip_stream_capture_id.argtypes = [vp, c.POINTER(c.c_uint64)]

@@ -25,8 +25,9 @@ struct DeqParams {
     const void* svd_down;  // [R][K]
     int64_t N, K;
     int group_size, G, rank;
-    int P, SG;  // conv weights: kernel positions per channel (1 for Linear) and scales per output row (G * P)
+    int P, SG;  // conv weights: kernel positions per channel (1 for Linear) and scales per output row (G * P; codebooks: G * L * P)
     int sdt;    // SdnqWeight.scale_dtype: 16-bit -> the product below is rounded to it (dequantize_fp32=False)
+    int L;      // SDNQ_KIND_CODEBOOK: levels per (row, group) = 2^bits, `scale` is the level table; 0 otherwise
     WeightFmt fmt;
 };
 
@@ -35,12 +36,30 @@ struct DeqParams {
     SDNQ_KERNARGS_NOW("s"((p).w), "s"((p).scale), "s"((p).zp), "s"((p).svd_up), "s"((p).svd_down), "s"((p).N), "s"((p).K), "s"((p).group_size), \
                       "s"((p).G), "s"((p).rank), "s"((p).P), "s"((p).SG), "s"((p).sdt))
 
-// dequantize 16 elements (row n, columns k0..k0+15) to fp32: f32(w)*s or fma(f32(w), s, zp)
+// dequantize 16 elements (row n, columns k0..k0+15) to fp32: f32(w)*s or fma(f32(w), s, zp); codebooks: levels[n][g][code]
 __device__ __forceinline__ void dequant16(const DeqParams& p, int64_t n, int64_t k0, float (&v)[16]) {
     load16_values(p.w, n * p.K + k0, p.fmt, v);
     const float* srow = p.scale + n * p.SG;
     const float* zrow = p.zp ? p.zp + n * p.SG : nullptr;
-    if (p.P > 1) {
+    if (p.L) {
+        // codebook (dequantize_codebook, dequantizer.py:88-131): scale.gather along the reduction axis.  The code (< L, exact in
+        // v[j]) indexes the level row of its group: [G][L] per output row, [G][L][P] for conv weights.  The levels are values of
+        // the scale dtype already, so the rounding below is the identity on them.
+        if (p.P > 1) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = (int)(k0 + j), c = k / p.P;
+                v[j] = srow[((c / p.group_size) * p.L + (int)v[j]) * p.P + (k - c * p.P)];
+            }
+        } else if ((p.group_size & 15) == 0) {  // one group covers the whole 16-run (wave-uniform branch)
+            const float* lrow = srow + (int)(k0 / p.group_size) * p.L;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = lrow[(int)v[j]];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = srow[(int)((k0 + j) / p.group_size) * p.L + (int)v[j]];
+        }
+    } else if (p.P > 1) {
         // conv weight [C_out][C_in][positions] quantized along C_in (quantizer.py:120-123, 205-209): one scale per
         // (output channel, channel group, kernel position); flattened k = c * P + pos
 #pragma unroll
@@ -283,17 +302,20 @@ __global__ __launch_bounds__(256) void requant_lut4_kernel(const DeqParams p, ui
     const uint8_t* crow = (const uint8_t*)p.w + ((n * p.K) >> 1);
     uint2 cw[NP];
     float sg[NP], zg[NP];
+    int gb[NP];  // codebooks: offset of the group's 16 levels in the row's table
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
         int64_t k0 = (int64_t)ps * 1024 + lane * 16;
         if (k0 >= p.K) k0 = p.K - 16;  // out-of-range lanes read the row's last run and store nothing
         const int g = (int)(k0 / p.group_size);
         cw[ps] = *(const uint2*)(crow + (k0 >> 1));
-        sg[ps] = srow[g];
+        gb[ps] = g * 16;
+        sg[ps] = p.L ? 0.0f : srow[g];
         zg[ps] = zrow ? zrow[g] : 0.0f;
     }
     const float knownscale = ws_known ? ws[n] : 0.0f;
-    auto value_of = [&](u32 code, float s, float z) {
+    auto value_of = [&](u32 code, float s, float z, int gbase) {
+        if (p.L) return srow[gbase + (int)code];  // codebook: entry c of the table is levels[n][g][c] (dequant16)
         float x;
         if (p.fmt.kind == SDNQ_KIND_INT) x = (float)((int)code - 8);
         else if (p.fmt.kind == SDNQ_KIND_UINT) x = (float)code;
@@ -321,7 +343,7 @@ __global__ __launch_bounds__(256) void requant_lut4_kernel(const DeqParams p, ui
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const u32 code = 4u * quad + e;
-                const float v = fabsf(value_of(code, sg[ps], zg[ps]));
+                const float v = fabsf(value_of(code, sg[ps], zg[ps], gb[ps]));
                 if ((present >> code) & 1u) amax = fmaxf(amax, v);
             }
         }
@@ -337,7 +359,7 @@ __global__ __launch_bounds__(256) void requant_lut4_kernel(const DeqParams p, ui
         u32 mine = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float v = value_of(4u * quad + e, sg[ps], zg[ps]);
+            const float v = value_of(4u * quad + e, sg[ps], zg[ps], gb[ps]);
             u32 byte;
             if constexpr (MM == SDNQ_MM_I8) {
                 float q = __builtin_rintf(round_rt(v / scale, p.sdt));
@@ -1107,7 +1129,12 @@ int fill_params(const SdnqWeight* w, DeqParams& p) {
     const int pos = w->positions > 1 ? w->positions : 1;
     if (w->n <= 0 || w->k <= 0 || w->group_size <= 0 || (w->k % pos) != 0 || ((w->k / pos) % w->group_size) != 0) return SDNQ_ERR_SHAPE;
     if ((w->k % 16) != 0) return SDNQ_ERR_SHAPE;
-    if (w->storage < 0 || w->storage > 3 || w->kind < 0 || w->kind > 3) return SDNQ_ERR_DTYPE;
+    if (w->storage < 0 || w->storage > 3 || w->kind < 0 || w->kind > SDNQ_KIND_CODEBOOK) return SDNQ_ERR_DTYPE;
+    if (w->kind == SDNQ_KIND_CODEBOOK) {  // 2^bits levels per group, packed 1..7-bit or raw 8-bit codes, no zero point
+        if (w->bits < 1 || w->bits > 8 || w->native_float) return SDNQ_ERR_DTYPE;
+        if (w->storage != (w->bits == 8 ? SDNQ_ST_RAW8 : SDNQ_ST_PACKED_U8)) return SDNQ_ERR_DTYPE;
+        if (w->zero_point) return SDNQ_ERR_UNSUPPORTED;
+    }
     if (w->bits < 1 || w->bits > 16) return SDNQ_ERR_DTYPE;
     if (w->storage == SDNQ_ST_PACKED_U8 && w->bits > 7) return SDNQ_ERR_DTYPE;
     if (w->storage == SDNQ_ST_PACKED_I16 && (w->bits < 9 || w->bits > 15)) return SDNQ_ERR_DTYPE;
@@ -1123,7 +1150,7 @@ int fill_params(const SdnqWeight* w, DeqParams& p) {
     if (w->svd_up && (w->svd_rank <= 0 || w->svd_dtype < 0 || w->svd_dtype > 2)) return SDNQ_ERR_SHAPE;
     p.w = w->weight; p.scale = w->scale; p.zp = w->zero_point; p.svd_up = w->svd_up; p.svd_down = w->svd_down;
     p.N = w->n; p.K = w->k; p.group_size = w->group_size; p.G = (w->k / pos) / w->group_size; p.rank = w->svd_rank;
-    p.P = pos; p.SG = p.G * pos;
+    p.P = pos; p.L = w->kind == SDNQ_KIND_CODEBOOK ? 1 << w->bits : 0; p.SG = p.G * pos * (p.L ? p.L : 1);
     if (w->scale_dtype < 0 || w->scale_dtype > 2) return SDNQ_ERR_DTYPE;
     p.sdt = w->scale_dtype;
     p.fmt = WeightFmt{w->storage, w->kind, w->bits, w->exponent, w->mantissa, w->native_float};

@@ -218,7 +218,7 @@ __device__ __forceinline__ void load16_values(const void* __restrict__ w, int64_
             else if (f.bits <= 8) iv = (int)(int8_t)c[j];
             else iv = (int)(int16_t)c[j];
             x = (float)iv;
-        } else if (f.kind == SDNQ_KIND_UINT) {
+        } else if (f.kind == SDNQ_KIND_UINT || f.kind == SDNQ_KIND_CODEBOOK) {  // (a codebook code is the level index)
             x = (float)c[j];
         } else if (f.native_float) {
             if (f.bits == 8) x = (f.ebits == 4) ? e4m3fn_to_f32((uint8_t)c[j]) : e5m2_to_f32((uint8_t)c[j]);

@@ -100,15 +100,13 @@ class SDNQDequantizer:
         return bool(self.use_quantized_matmul and not self.re_quantize_for_matmul and not self.is_packed)
 
     def quant_weight(self, weight, scale, zero_point=None, svd_up=None, svd_down=None) -> ops.QuantWeight:
-        if self.use_codebook:
-            raise NotImplementedError("use_codebook (Lloyd-Max LUT) is outside the MI355X hot path (SURVEY 8a note)")
         if self.layer_class_name not in linear_types and self.layer_class_name not in conv_types and self.layer_class_name not in embedding_types:
             raise NotImplementedError(f"{self.layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X")
         n, k, pos = self.out_features, self.in_features, self.kernel_positions
         group = self.group_size if self.group_size > 0 else k // pos
         return ops.make_quant_weight(self.weights_dtype, weight, scale, zero_point, svd_up, svd_down, n, k, group,
                                      transposed=self.weight_is_transposed, svd_transposed=bool(self.use_quantized_matmul),
-                                     positions=pos)
+                                     positions=pos, codebook=bool(self.use_codebook))
 
     @torch.no_grad()
     def re_quantize_matmul(self, weight, scale, zero_point=None, svd_up=None, svd_down=None, hadamard=None,

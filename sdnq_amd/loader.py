@@ -523,7 +523,7 @@ def apply_sdnq_options_to_model(model: torch.nn.Module, dtype: torch.dtype | Non
         # every SDNQ Linear / conv layer, whether or not the HIP forwards compute its (old or new) configuration: the options only
         # re-type tensors and re-point forward_func; an unbuilt configuration then fails loudly at its forward (support.require)
         cls = getattr(getattr(module, "sdnq_dequantizer", None), "layer_class_name", None)
-        if cls is None or getattr(module.sdnq_dequantizer, "use_codebook", False):
+        if cls is None:
             continue
         conv = cls in ("Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d")
         emb = cls in ("Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding")

@@ -102,7 +102,7 @@ def _storage_kind(weights_dtype: str):
 
 def make_quant_weight(weights_dtype: str, weight: torch.Tensor, scale: torch.Tensor, zero_point, svd_up, svd_down,
                       n: int, k: int, group_size: int, transposed: bool, svd_transposed: bool | None = None,
-                      positions: int = 1) -> QuantWeight:
+                      positions: int = 1, codebook: bool = False) -> QuantWeight:
     """Canonicalise module tensors (reference layouts) into the kernels' physical layout.
 
     transposed=False: weight is packed bytes / [N,K] / [N,G,g] (element order [N][K]); svd_up [N,R], svd_down [R,K].
@@ -115,11 +115,18 @@ def make_quant_weight(weights_dtype: str, weight: torch.Tensor, scale: torch.Ten
                       use_quantized_matmul is on, independent of the weight layout (quantizer.py:164-167).
     positions       : P > 1 for conv weights [N, C_in, *kernel] quantized along C_in (quantizer.py:120-123, 205-209):
                       k = C_in * P, group_size counts channels, scale / zero_point hold N * (C_in / group_size) * P values.
+    codebook        : `scale` is the level table of a use_codebook layer, 2^bits levels per (row, group[, position]) with the level
+                      axis before the kernel positions ([N, L], [N, G, L], [N, L, *kernel], [N, G, L, *kernel]); no zero point.
     """
     if svd_transposed is None:
         svd_transposed = transposed
     _require_cuda(weight, scale)
     storage, kind, bits, ebits, mbits, native = _storage_kind(weights_dtype)
+    levels = 1
+    if codebook:
+        if kind != _lib.KIND_UINT or bits > 8 or transposed or zero_point is not None:
+            raise _lib.SdnqHipError(f"codebook weights are unsigned integer codes of up to 8 bits without a zero point (got {weights_dtype})")
+        kind, levels = _lib.KIND_CODEBOOK, 1 << bits
     if transposed:
         if tuple(weight.shape) != (k, n):
             raise _lib.SdnqHipError(f"transposed weight must be [K,N]=({k},{n}), got {tuple(weight.shape)}")
@@ -143,8 +150,8 @@ def make_quant_weight(weights_dtype: str, weight: torch.Tensor, scale: torch.Ten
     # dequantize_fp32=False keeps scale / zero_point in the model dtype (quantizer.py:147-156); the kernels read the exact float32
     # upcast and SdnqWeight.scale_dtype tells them where the reference's 16-bit tensors round
     sc = scale.to(torch.float32).contiguous().view(-1)
-    if sc.numel() != n * g:
-        raise _lib.SdnqHipError(f"scale has {sc.numel()} elements, expected N*G = {n * g}")
+    if sc.numel() != n * g * levels:
+        raise _lib.SdnqHipError(f"scale has {sc.numel()} elements, expected N*G{'*L' if codebook else ''} = {n * g * levels}")
     zp = None
     if zero_point is not None:
         zp = zero_point.to(torch.float32).contiguous().view(-1)
@@ -993,6 +1000,35 @@ def im2col_rowquant(x: torch.Tensor, kernel, stride, padding, dilation, mm: int)
     check(_lib.load().sdnq_hip_im2col_rowquant(x.data_ptr(), float_code(x.dtype), b, c, h, w, kh, kw, sh, sw, ph, pw, dh, dw, mm,
                                                xq.data_ptr(), xs.data_ptr(), ws.data_ptr(), _stream(x)), "im2col_rowquant")
     return xq, xs, (b, ho, wo)
+
+
+def quantize_codebook(weight2d: torch.Tensor, weights_dtype: str, group_size: int, positions: int = 1, steps: int = 24):
+    """Float [N,K] weight -> (codes, levels f32 [N, G, L, P]) of the codebook quantizer (sdnq_hip_quantize_codebook; the reference's
+    quantize_weight_codebook + pack_int): codes packed like `quantize_weight` returns them ([N,K] uint8 for uint8).  `group_size`
+    == K / P for one slice per row; positions as in `quantize_weight`."""
+    from .common import dtype_dict
+    from . import packed as _packed
+    _require_cuda(weight2d)
+    if weight2d.dtype not in _FLOAT_CODE:
+        raise _lib.SdnqHipError(f"quantize_codebook: unsupported source dtype {weight2d.dtype}")
+    w = weight2d if weight2d.stride(1) == 1 else weight2d.contiguous()
+    n, k = w.shape
+    storage, kind, bits, _, _, _ = _storage_kind(weights_dtype)
+    if kind != _lib.KIND_UINT or bits > 8:
+        raise _lib.SdnqHipError(f"codebook quantization is only supported with unsigned integer dtypes of up to 8 bits (got {weights_dtype})")
+    g = (k // positions) // group_size
+    dev = w.device
+    raw = torch.empty((n, k), device=dev, dtype=torch.uint8) if bits == 8 else torch.empty((n * k // 8 * bits,), device=dev, dtype=torch.uint8)
+    levels = torch.empty((n, g, 1 << bits, positions), device=dev, dtype=torch.float32)
+    d = SdnqWeight(weight=raw.data_ptr(), scale=levels.data_ptr(), zero_point=None, svd_up=None, svd_down=None, n=n, k=k,
+                   group_size=group_size, svd_rank=0, svd_dtype=0, storage=storage, kind=_lib.KIND_CODEBOOK, bits=bits, exponent=0,
+                   mantissa=0, native_float=0, positions=positions)
+    check(_lib.load().sdnq_hip_quantize_codebook(w.data_ptr(), float_code(w.dtype), w.stride(0), ctypes.byref(d), int(steps), _stream(w)),
+          "quantize_codebook")
+    if bits != 8:
+        _g, words, _wb = _packed._GEOM[bits]
+        raw = raw if words == 1 else raw.view(-1, words)
+    return raw, levels
 
 
 def quantize_weight(weight2d: torch.Tensor, weights_dtype: str, group_size: int, positions: int = 1):

@@ -108,3 +108,55 @@ def quantize_weight(weight: torch.Tensor, dim, weights_dtype: str, dtype: torch.
         q = q.nan_to_num_()
     q = q.clamp_(ent["min"], ent["max"]).to(ent["torch_dtype"])
     return q, scale, zero_point
+
+
+def _lloyd_max_rows(x: torch.Tensor, n_levels: int, steps: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Lloyd-Max levels of every row of a float32 [R, S] matrix -> (codes int64 [R, S], sorted levels float32 [R, L]).
+
+    Starts from L evenly spaced levels between the row's min and max (one fused multiply-add each), then `steps` rounds of:
+    sort, assign every value to the level whose midpoint interval holds it (a value on a midpoint takes the lower level), move
+    every occupied level to the mean of its members.  On CPU tensors `scatter_add_` adds each level's members in element order,
+    which is the reference's rounding."""
+    lo, hi = torch.aminmax(x, dim=-1, keepdim=True)
+    step = (hi - lo) / (n_levels - 1)
+    idx = torch.arange(n_levels, dtype=x.dtype, device=x.device)
+    levels = torch.addcmul(lo, idx, step)
+    ones = torch.ones(x.shape, dtype=torch.int32, device=x.device)
+
+    def assign(lv):
+        mids = (lv[:, 1:] + lv[:, :-1]) * 0.5
+        return torch.searchsorted(mids, x)
+
+    for _ in range(steps):
+        levels = torch.sort(levels, dim=-1).values
+        codes = assign(levels)
+        count = torch.zeros(levels.shape, dtype=torch.int32, device=x.device).scatter_add_(1, codes, ones)
+        total = torch.zeros_like(levels).scatter_add_(1, codes, x)
+        levels = torch.where(count > 0, total / count.clamp(min=1), levels)
+    levels = torch.sort(levels, dim=-1).values
+    return assign(levels), levels
+
+
+def quantize_codebook(weight: torch.Tensor, dim: int, weights_dtype: str, steps: int = 24, dtype: torch.dtype | None = None):
+    """Codebook quantization along `dim` (the reference's use_codebook): -> (codes of weight's shape in the dtype's torch type,
+    levels).  The levels take weight's shape with `dim` replaced by the L = 2^bits level axis: [N, L] / [N, G, L] for Linear and
+    embedding tables, [N, L, *kernel] / [N, G, L, *kernel] for conv weights.  `dtype`: the scale dtype the levels are cast to last.
+    Meta tensors give placeholders of those shapes."""
+    ent = dtype_dict[weights_dtype]
+    if not (ent["is_integer"] and ent["is_unsigned"]):
+        raise NotImplementedError("codebook quantization is only supported with unsigned integer dtypes")
+    n_levels = int(ent["max"]) + 1
+    dim = dim % weight.dim()
+    lshape = list(weight.shape)
+    lshape[dim] = n_levels
+    if weight.is_meta:
+        return (torch.empty(weight.shape, dtype=ent["torch_dtype"], device="meta"),
+                torch.empty(lshape, dtype=dtype or torch.float32, device="meta"))
+    x = weight.to(torch.float32).movedim(dim, -1)
+    moved = x.shape
+    codes, levels = _lloyd_max_rows(x.reshape(-1, moved[-1]).contiguous(), n_levels, steps)
+    codes = codes.view(moved).movedim(-1, dim)
+    levels = levels.view(*moved[:-1], n_levels).movedim(-1, dim).contiguous()
+    if dtype is not None:
+        levels = levels.to(dtype)
+    return codes.to(ent["torch_dtype"]).contiguous(), levels

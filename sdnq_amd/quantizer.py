@@ -4,8 +4,9 @@ API names are the reference's (quantizer.py: SDNQConfig :846, sdnq_quantize_laye
 sdnq_quantize_layer :423, apply_sdnq_to_module :477, QuantizationMethod :60) so host code switches with an
 import change; the module/tensor layout produced is byte-compatible with reference checkpoints
 (SURVEY App. C), which tests/test_quantizer.py checks against the golden fixtures.  Only what feeds the Linear
-hot path is implemented: no dynamic dtype search, no codebook, no stochastic rounding, no transposed conv.
-Embedding layers (quant_embedding=True) take the reference's non-Linear branch.
+hot path is implemented: no dynamic dtype search, no stochastic rounding, no transposed conv.
+Embedding layers (quant_embedding=True) take the reference's non-Linear branch; use_codebook=True stores Lloyd-Max level tables
+(unsigned integer dtypes up to 8 bits).
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ from .common import conv_types, dtype_dict, embedding_types, linear_types, sdnq_
 from .dequantizer import SDNQDequantizer
 from .forward import get_forward_func
 from .layers import get_sdnq_wrapper_class
-from .quant_utils import apply_hadamard, apply_svdquant, quantize_weight
+from .quant_utils import apply_hadamard, apply_svdquant, quantize_codebook, quantize_weight
 
 
 class QuantizationMethod(str, Enum):
@@ -62,9 +63,13 @@ class SDNQConfig:
             raise ValueError(f"SDNQ only support weight dtypes in {sorted(dtype_dict)} but found {weights_dtype}")
         if quantized_matmul_dtype is not None and quantized_matmul_dtype not in {"int8", "uint8", "fp8", "fp16", "float8_e4m3fn", "float16"}:
             raise ValueError(f"unsupported quantized_matmul_dtype {quantized_matmul_dtype}")
-        for name in ("use_codebook", "use_dynamic_quantization", "use_stochastic_rounding", "is_training"):
+        for name in ("use_dynamic_quantization", "use_stochastic_rounding", "is_training"):
             if locals()[name]:
                 raise NotImplementedError(f"SDNQConfig({name}=True) is outside the MI355X Linear hot path")
+        if use_codebook and not (dtype_dict[weights_dtype]["is_integer"] and dtype_dict[weights_dtype]["is_unsigned"]):
+            raise NotImplementedError("SDNQConfig(use_codebook=True): codebook quantization is only supported with unsigned integer dtypes")
+        if use_codebook and dtype_dict[weights_dtype]["num_bits"] > 8:
+            raise NotImplementedError("SDNQConfig(use_codebook=True): codebooks wider than 8 bits are not built")
         self.weights_dtype = weights_dtype
         self.quantized_matmul_dtype = quantized_matmul_dtype
         self.hadamard_group_size = hadamard_group_size
@@ -134,12 +139,13 @@ def _needs_requant(weights_dtype: str, matmul_dtype: str) -> bool:
 
 
 def _pick_group_size(group_size: int, channel_size: int, weights_dtype: str, is_linear: bool, has_svd: bool,
-                     direct_matmul: bool) -> tuple[int, int]:
-    """-> (group_size or -1, num_groups). Policy of reference quantizer.py:173-201."""
+                     direct_matmul: bool, codebook: bool = False) -> tuple[int, int]:
+    """-> (group_size or -1, num_groups). Policy of reference quantizer.py:173-201 (a codebook's default group is 8x larger: the
+    level table costs 2^bits values per group)."""
     if group_size == 0:
         if direct_matmul and dtype_dict[weights_dtype]["num_bits"] >= 6:
             return -1, 1
-        p = 1 + dtype_dict[weights_dtype]["num_bits"] + (1 if is_linear else 0) + (1 if has_svd else 0)
+        p = 1 + dtype_dict[weights_dtype]["num_bits"] + (1 if is_linear else 0) + (1 if has_svd else 0) + (3 if codebook else 0)
         group_size = 2 ** p
     if group_size <= 0 or group_size >= channel_size:
         return -1, 1
@@ -157,7 +163,7 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
                                quantized_matmul_dtype: str | None = None, group_size: int = 0, hadamard_group_size: int = 256,
                                svd_rank: int = 32, svd_steps: int = 8, use_svd: bool = False, use_hadamard: bool = False,
                                use_quantized_matmul: bool = False, dequantize_fp32: bool = True,
-                               torch_dtype: torch.dtype | None = None, **_unused):
+                               torch_dtype: torch.dtype | None = None, use_codebook: bool = False, codebook_steps: int = 24, **_unused):
     """Float [N,K] weight -> (SDNQDequantizer, {"weight","scale","zero_point","svd_up","svd_down"}).
 
     Order of operations as in the reference (quantizer.py:158-253): Hadamard -> SVD split -> grouping ->
@@ -179,8 +185,10 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
     mm_dtype = get_quantized_matmul_dtype(weights_dtype, quantized_matmul_dtype)
     # embeddings take the reference's generic branch (quantizer.py:144-150): reduction along the last dim, no quantized matmul
     use_qmm = False if is_embedding else check_quantized_matmul_is_allowed(use_quantized_matmul, n, channels)
-    requant = _needs_requant(weights_dtype, mm_dtype)
+    requant = use_codebook or _needs_requant(weights_dtype, mm_dtype)  # codes index a table: never a matmul operand (:104-105)
     ent = dtype_dict[weights_dtype]
+    if use_codebook and not (ent["is_integer"] and ent["is_unsigned"] and ent["num_bits"] <= 8):
+        raise NotImplementedError(f"codebook quantization is only supported with unsigned integer dtypes of up to 8 bits (got {weights_dtype})")
     result_shape = None
     # conv weights feeding the matmul directly are flattened BEFORE quantization: one scale per output channel over all of
     # (C_in, kernel); every other conv layout keeps one scale per kernel position (quantizer.py:120-125)
@@ -198,7 +206,7 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
             svd_up, svd_down = svd_up.t(), svd_down.t()
 
     group_size, groups = _pick_group_size(group_size, channels, weights_dtype, layer_class_name in linear_types, svd_up is not None,
-                                          direct_matmul=use_qmm and not requant)
+                                          direct_matmul=use_qmm and not requant, codebook=use_codebook)
     dim = 1 if (is_conv and not flat) else -1
     if groups > 1:
         if flat:
@@ -220,7 +228,12 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
     if not dequantize_fp32 and ent["max"] <= 16384 and torch_dtype in (torch.bfloat16, torch.float16):
         scale_dtype = torch_dtype
 
-    if weight.is_cuda and USE_HIP_QUANTIZER and weight.dtype in (torch.float32, torch.bfloat16, torch.float16) and k % 16 == 0 \
+    if use_codebook:
+        q, scale = _quantize_codebook_layer(weight, dim, weights_dtype, codebook_steps, scale_dtype, n, k, groups, group_size, channels,
+                                            positions)
+        zero_point = None
+        quantized_weight_shape = weight.shape
+    elif weight.is_cuda and USE_HIP_QUANTIZER and weight.dtype in (torch.float32, torch.bfloat16, torch.float16) and k % 16 == 0 \
             and (ent["is_packed"] or ent["num_bits"] in (8, 16)) and weights_dtype not in _HIP_QUANTIZER_SKIP and scale_dtype is None:
         # GPU tensors: one HIP launch pair does scale/zero-point, quantize and pack (csrc/quantize.hip); the element order
         # [N][K] is the same for the plain, grouped, conv and transposed layouts, only the logical views differ
@@ -256,10 +269,38 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
     dq = SDNQDequantizer(result_dtype=torch_dtype, result_shape=result_shape, original_shape=original_shape,
                          original_stride=original_stride, quantized_weight_shape=quantized_weight_shape,
                          weights_dtype=weights_dtype, quantized_matmul_dtype=mm_dtype, hadamard_group_size=hadamard_group_size,
-                         group_size=group_size, svd_rank=svd_rank, svd_steps=svd_steps, codebook_steps=24,
+                         group_size=group_size, svd_rank=svd_rank, svd_steps=svd_steps, codebook_steps=codebook_steps,
                          use_quantized_matmul=use_qmm, re_quantize_for_matmul=requant, use_stochastic_rounding=False,
-                         use_hadamard=bool(use_hadamard), use_codebook=False, layer_class_name=layer_class_name)
+                         use_hadamard=bool(use_hadamard), use_codebook=bool(use_codebook), layer_class_name=layer_class_name)
     return dq, {"weight": q, "scale": scale, "zero_point": zero_point, "svd_up": svd_up, "svd_down": svd_down}
+
+
+def _quantize_codebook_layer(weight: torch.Tensor, dim: int, weights_dtype: str, steps: int, scale_dtype, n: int, k: int, groups: int,
+                             group_size: int, channels: int, positions: int):
+    """(codes of weight's shape, levels) of the codebook branch.  GPU tensors: one HIP launch pair (csrc/quantize.hip,
+    sdnq_hip_quantize_codebook) -- the same bits as the torch restatement the CPU takes (quant_utils.quantize_codebook)."""
+    ent = dtype_dict[weights_dtype]
+    slice_len = group_size if groups > 1 else channels
+    if (weight.is_cuda and USE_HIP_QUANTIZER and weight.dtype in (torch.float32, torch.bfloat16, torch.float16) and k % 16 == 0
+            and weights_dtype not in _HIP_QUANTIZER_SKIP and slice_len <= 16384):
+        from . import ops
+        codes, levels = ops.quantize_codebook(weight.reshape(n, k), weights_dtype, slice_len, positions=positions, steps=steps)
+        lshape = list(weight.shape)
+        lshape[dim] = int(ent["max"]) + 1
+        levels = levels.view(lshape)
+        if scale_dtype is not None:
+            levels = levels.to(scale_dtype)
+        if not ent["is_packed"]:
+            codes = codes.view(weight.shape)
+        return codes, levels
+    # CPU tensors, and on the GPU what the kernel does not take (1-bit codes, slices longer than its LDS): the torch restatement, on a
+    # host copy for GPU tensors -- the GPU's scatter_add_ adds in no fixed order, the reference's CPU one in element order
+    codes, levels = quantize_codebook(weight if weight.is_meta else weight.cpu(), dim, weights_dtype, steps=steps, dtype=scale_dtype)
+    if ent["is_packed"]:
+        codes = packed.pack_int(codes, weights_dtype)
+        if ent["torch_dtype"] == torch.bool:  # the reference packs 1-bit codes from a bool tensor: int64 words of 8 bits each
+            codes = codes.to(torch.int64)
+    return codes.to(weight.device), levels.to(weight.device)
 
 
 def check_param_name_in(param_name: str, param_list) -> str | None:
@@ -304,7 +345,8 @@ def _quant_kwargs(cfg: SDNQConfig, torch_dtype, param_name: str, layer_class_nam
     kw = dict(weights_dtype=cfg.weights_dtype, quantized_matmul_dtype=cfg.quantized_matmul_dtype, group_size=cfg.group_size,
               hadamard_group_size=cfg.hadamard_group_size, svd_rank=cfg.svd_rank, svd_steps=cfg.svd_steps,
               use_svd=cfg.use_svd, use_hadamard=cfg.use_hadamard, use_quantized_matmul=cfg.use_quantized_matmul,
-              dequantize_fp32=cfg.dequantize_fp32, torch_dtype=torch_dtype)
+              dequantize_fp32=cfg.dequantize_fp32, torch_dtype=torch_dtype, use_codebook=cfg.use_codebook,
+              codebook_steps=cfg.codebook_steps)
     conv_mm = cfg.use_quantized_matmul_conv
     key = check_param_name_in(param_name, list(cfg.modules_quant_config.keys()))
     if key is not None:

@@ -31,10 +31,12 @@ def unsupported_reason(module) -> str | None:
         return f"{cls}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X (transposed convolutions are outside SURVEY 8)"
     if cls not in linear_types and cls not in conv_types and cls not in embedding_types:
         return f"{cls}: unknown layer class"
-    if getattr(dq, "use_codebook", False):
-        return "use_codebook (Lloyd-Max LUT) is outside the MI355X hot path (SURVEY 8a note)"
     if dq.weights_dtype not in dtype_dict or dq.quantized_matmul_dtype not in dtype_dict:
         return f"unknown dtype {dq.weights_dtype} / {dq.quantized_matmul_dtype}"
+    if getattr(dq, "use_codebook", False):
+        why = _codebook_reason(dq, cls)
+        if why is not None:
+            return why
     mm = dtype_dict[dq.quantized_matmul_dtype]
     qmm = bool(dq.use_quantized_matmul)
     sdt = _scale_dtype(module)
@@ -93,6 +95,25 @@ def unsupported_reason(module) -> str | None:
                        or (getattr(module, "zero_point", None) is not None and not dq.re_quantize_for_matmul)):
                 return ("grouped conv matmul with 16-bit scales is built for bfloat16 scales on the int8 / fp8 matmul without a weight zero point (float16: the reference "
                         "casts acc * input_scale to float16 before the weight scale, dequantizer.py:27, 63 -- an epilogue of its own)")
+    return None
+
+
+def _codebook_reason(dq, cls) -> str | None:
+    """use_codebook layers: the codes index a level table per (row, group) that every weight-side kernel gathers from (dequant16)."""
+    w = dtype_dict[dq.weights_dtype]
+    if not (w["is_integer"] and w["is_unsigned"]):
+        return f"codebook quantization is only supported with unsigned integer dtypes (got {dq.weights_dtype})"
+    if w["num_bits"] > 8:
+        return f"codebooks wider than 8 bits are not built (got {dq.weights_dtype})"
+    if int(dq.group_size) == -2:
+        return "tensorwise codebooks (group_size=-2) are not built"
+    if not dq.re_quantize_for_matmul and dq.use_quantized_matmul:
+        return "a codebook layer whose codes feed the matmul directly has no form in the reference (use_codebook re-quantizes)"
+    if cls in conv_types and dq.use_quantized_matmul and int(dq.group_size) <= 0:
+        return ("an ungrouped codebook conv with a quantized matmul fails in the reference's own forward (its result_shape is None); "
+                "grouped codebook convs are built")
+    if dq.use_quantized_matmul and dq.quantized_matmul_dtype in ("float16", "fp16"):
+        return "the float16 matmul of codebook layers is not built (int8, fp8 and uint8 are)"
     return None
 
 
