@@ -319,6 +319,18 @@ typedef enum SdnqIds { SDNQ_IDS_I32 = 0, SDNQ_IDS_I64 = 1 } SdnqIds;
 int sdnq_hip_embedding(const SdnqWeight* w, int hadamard_group, const void* ids, int ids_dtype, int64_t n_ids,
                        int has_embed_scale, double embed_scale, void* out, int out_dtype, sdnq_stream_t stream);
 
+/* ---- dynamic quantization: reconstruction loss of one candidate ------------------------------
+ * replaces the loss of sdnq_quantize_layer_weight_dynamic (quantizer.py:384-400): mse_loss(W, dequantize(q)) without the
+ * dequantized copy.  *sum_out (DEVICE fp64) = sum over [N][K] of (double)(d * d), d = deq[n][k] - ref[n][k] in fp32, where deq is
+ * bit for bit the float32 output of sdnq_hip_dequant(w, hadamard_group, out, SDNQ_F32) (every kind, grouped / row-wise / conv
+ * positions, zero points, 16-bit scale_dtype, the SVD term in the svd dtype, the Hadamard rotation in fp32).  ref: the original
+ * float weight of ref_dtype (SdnqFloat, upcast exactly), row stride ld_ref elements, 16-byte aligned rows.  Two launches: one pass
+ * writes a fp64 partial per workgroup to `workspace`, a single workgroup adds them in a fixed order -- no atomics, the result is
+ * the same bits on every call.  workspace: sdnq_hip_dequant_loss_workspace_bytes(n, k) bytes (< 0: SdnqStatus), 8-byte aligned. */
+int64_t sdnq_hip_dequant_loss_workspace_bytes(int64_t n, int64_t k);
+int sdnq_hip_dequant_loss(const SdnqWeight* w, int hadamard_group, const void* ref, int ref_dtype, int64_t ld_ref,
+                          double* sum_out, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 /* ---- a7: re-quantize for matmul ---------------------------------------------------------------
  * replaces re_quantize_matmul (dequantizer.py:204-239): fp32 dequant (Hadamard NOT undone), then a
  * per-output-row symmetric quantization to the matmul dtype. wq: physical [N][K]; ws: [N] f32. */

@@ -37,6 +37,7 @@ EXPORTS = [
     "sdnq_hip_linear_w8a8_fused", "sdnq_hip_linear_w8a8_fused_supported", "sdnq_hip_scaled_mm_lp_uzp_svd", "sdnq_hip_stream_capture_id",
     "sdnq_hip_scaled_mm_tile", "sdnq_hip_lut4_build", "sdnq_hip_scaled_mm_w4", "sdnq_hip_scaled_mm_w4_supported",
     "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding", "sdnq_hip_quantize_codebook",
+    "sdnq_hip_dequant_loss", "sdnq_hip_dequant_loss_workspace_bytes",
 ]
 
 
@@ -157,6 +158,9 @@ def _declare(lib):
     lib.sdnq_hip_push_post.argtypes = [pvp, i32, i32, c.c_uint64, c.c_uint64, vp]
     lib.sdnq_hip_push_columns.argtypes = [vp, i32, i64, i64, i64, pvp, pvp, pvp, i32, i32, c.c_uint64, i64, i64, i64, vp, vp, i32, vp]
     lib.sdnq_hip_dequant.argtypes = [c.POINTER(SdnqWeight), i32, vp, i32, vp]
+    lib.sdnq_hip_dequant_loss.argtypes = [c.POINTER(SdnqWeight), i32, vp, i32, i64, vp, vp, i64, vp]
+    lib.sdnq_hip_dequant_loss_workspace_bytes.restype = i64
+    lib.sdnq_hip_dequant_loss_workspace_bytes.argtypes = [i64, i64]
     lib.sdnq_hip_embedding.argtypes = [vp, i32, vp, i32, i64, i32, c.c_double, vp, i32, vp]  # (the SdnqWeight by address: csrc/binding.c serves it too)
     lib.sdnq_hip_requant.argtypes = [c.POINTER(SdnqWeight), i32, vp, vp, vp]
     lib.sdnq_hip_requant_ws.argtypes = [c.POINTER(SdnqWeight), i32, vp, vp, i32, vp]

@@ -124,6 +124,26 @@ torch_dtype_dict = {
     torch.float8_e4m3fn: "float8_e4m3fn", torch.float8_e5m2: "float8_e5m2",
 }
 
+
+def _build_weights_dtype_order() -> list:
+    """Candidate order of the dynamic dtype search (the reference's weights_dtype_order, common.py:302-334), by its rule: for every
+    width B = 1..16 the signed formats -- intB, the native OCP floats of that width, the custom eXmYfn floats by ascending exponent
+    (E <= 5) -- then the unsigned ones -- uintB, the eXmYfnu floats by ascending exponent.  (There is no int1 / signed 1-bit float.)"""
+    order = []
+    for bits in range(1, 17):
+        if bits >= 2:
+            order.append(f"int{bits}")
+            order += {8: ["float8_e4m3fn", "float8_e5m2"], 16: ["float16"]}.get(bits, [])
+            for e in range(1, min(5, bits - 1) + 1):
+                name = f"float{bits}_e{e}m{bits - 1 - e}fn"
+                order.append("float8_e4m3fn_sdnq" if name == "float8_e4m3fn" else name)
+        order.append(f"uint{bits}")
+        order += [f"float{bits}_e{e}m{bits - e}fnu" for e in range(1, min(5, bits) + 1)]
+    return order
+
+
+weights_dtype_order = _build_weights_dtype_order()
+
 linear_types = {"Linear", "SDNQLinear"}
 embedding_types = {"Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding"}
 conv_types = {"Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d"}

@@ -3,6 +3,7 @@
 //   sdnq_hip_dequant   <- SDNQDequantizer.__call__ / dequantize_weight   (dequantizer.py:135-162, 389-429)
 //                         dequantize_symmetric :52-84, dequantize_asymmetric :15-48
 //   sdnq_hip_embedding <- quantized_embedding (layers/embedding/forward.py:14-68): weight[ids] dequantized, one launch
+//   sdnq_hip_dequant_loss <- mse_loss(W, dequantize(q)) of the dynamic dtype search (quantizer.py:384-400), fused, deterministic
 //   sdnq_hip_requant   <- re_quantize_matmul -> re_quantize_int_mm / re_quantize_fp_mm
 //                         (dequantizer.py:204-239, 166-174, 190-201; quantize_int_mm quant_utils.py:265-273)
 //   sdnq_hip_linear_float <- torch.nn.functional.linear on the dequantized weight
@@ -214,6 +215,106 @@ __global__ __launch_bounds__(256) void embedding_kernel(const DeqParams p, const
         *(uint4*)o = Vec16<OUT_T>::pack(v);
         *(uint4*)(o + 16) = Vec16<OUT_T>::pack(v + 8);
     }
+}
+
+// Reconstruction loss of a quantized weight (sdnq_hip_dequant_loss): sum over [N][K] of (deq - ref)^2 without writing deq.  One wave
+// per (row, 1024-column chunk) as in embedding_kernel, a grid-stride loop over the chunks; a lane owns 16 consecutive columns, so a
+// Hadamard group (<= 512 columns, dividing K) lies inside one wave's chunk and is undone in registers.  deq is formed exactly as
+// dequant_kernel<SDNQ_F32, SVD_T> forms it (2-D SVD rounding: round_svd(round_svd(v) + sum_r up * down)), then rotated by
+// wave_hadamard16 in fp32 -- the butterflies of hadamard_kernel<SDNQ_F32> (sdnq_hip_hadamard) in the same order.  Each term is
+// (d * d) in fp32, as mse_loss computes it, accumulated in fp64 per lane; the 256 lanes are added by a fixed tree and each
+// workgroup writes one partial: no atomics, the same bits on every call.
+constexpr int kLossMaxBlocks = 2048;  // 8 workgroups of 4 waves per CU on 256 CUs: enough loads in flight to stream HBM
+
+__host__ __device__ inline int64_t loss_blocks(int64_t n, int64_t k) {
+    const int64_t waves = n * ((k + 1023) / 1024);
+    const int64_t b = (waves + 3) / 4;
+    return b < kLossMaxBlocks ? b : kLossMaxBlocks;
+}
+
+template <int REF_T, int SVD_T>
+__global__ __launch_bounds__(256) void dequant_loss_kernel(const DeqParams p, const void* __restrict__ ref, int64_t ld_ref, int log2g,
+                                                           double* __restrict__ partial) {
+    __shared__ double red[256];
+    const int lane = threadIdx.x & 63;
+    const int64_t chunks = (p.K + 1023) / 1024;
+    const int64_t total = p.N * chunks;
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    double acc = 0.0;
+    for (int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); wave < total; wave += stride) {  // wave-uniform trip count
+        int64_t n, c;
+        divmod(wave, chunks, n, c);
+        const int64_t k0 = c * 1024 + lane * 16;
+        const bool active = k0 < p.K;
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = 0.0f;
+        if (active) {
+            dequant16(p, n, k0, v);
+            if (p.svd_up) {
+                float sacc[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { v[j] = FT<SVD_T>::round(v[j]); sacc[j] = 0.0f; }
+                for (int r = 0; r < p.rank; ++r) {
+                    const float up = FT<SVD_T>::load(p.svd_up, n * p.rank + r);
+                    float dn[16];
+                    if constexpr (SVD_T == SDNQ_F32) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p.svd_down + (int64_t)r * p.K + k0 + 4 * q), dn + 4 * q);
+                    } else {
+                        Vec16<SVD_T>::unpack(*(const uint4*)((const uint16_t*)p.svd_down + (int64_t)r * p.K + k0), dn);
+                        Vec16<SVD_T>::unpack(*(const uint4*)((const uint16_t*)p.svd_down + (int64_t)r * p.K + k0 + 8), dn + 8);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) sacc[j] = fmaf(up, dn[j], sacc[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = FT<SVD_T>::round(v[j] + sacc[j]);
+            }
+        }
+        // inactive lanes (the tail chunk of a row) hold zeros and join the cross-lane butterflies; their groups are all inactive
+        if (log2g) wave_hadamard16(v, log2g, hadamard_scale(log2g, SDNQ_F32));
+        if (active) {
+            float rv[16];
+            if constexpr (REF_T == SDNQ_F32) {
+                const float* rp = (const float*)ref + n * ld_ref + k0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) Vec16<SDNQ_F32>::unpack(*(const uint4*)(rp + 4 * q), rv + 4 * q);
+            } else {
+                const uint16_t* rp = (const uint16_t*)ref + n * ld_ref + k0;
+                Vec16<REF_T>::unpack(*(const uint4*)rp, rv);
+                Vec16<REF_T>::unpack(*(const uint4*)(rp + 8), rv + 8);
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float d = v[j] - rv[j];
+                acc += (double)(d * d);
+            }
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// the partials of dequant_loss_kernel in a fixed order: lane t adds t, t + 256, ... in turn, then the same tree
+__global__ __launch_bounds__(256) void loss_sum_kernel(const double* __restrict__ partial, int64_t nparts, double* __restrict__ out) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < nparts; i += 256) acc += partial[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = red[0];
 }
 
 // one wave per weight row: phase 1 amax of the fp32 dequant, phase 2 quantize (recompute, L2-hot)
@@ -1220,6 +1321,52 @@ extern "C" int sdnq_hip_embedding(const SdnqWeight* w, int hadamard_group, const
     else EMB_CASE(SDNQ_F16, SDNQ_F32)
     else return SDNQ_ERR_DTYPE;
 #undef EMB_CASE
+    SDNQ_CHECK_LAUNCH();
+    return SDNQ_OK;
+}
+
+extern "C" int64_t sdnq_hip_dequant_loss_workspace_bytes(int64_t n, int64_t k) {
+    if (n <= 0 || k <= 0) return SDNQ_ERR_SHAPE;
+    return loss_blocks(n, k) * (int64_t)sizeof(double);
+}
+
+extern "C" int sdnq_hip_dequant_loss(const SdnqWeight* w, int hadamard_group, const void* ref, int ref_dtype, int64_t ld_ref,
+                                     double* sum_out, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream) {
+    DeqParams p{};
+    int st = fill_params(w, p);
+    if (st != SDNQ_OK) return st;
+    if (!ref || !sum_out || !workspace) return SDNQ_ERR_NULL;
+    if (ref_dtype < 0 || ref_dtype > 2) return SDNQ_ERR_DTYPE;
+    if (ld_ref < p.K) return SDNQ_ERR_SHAPE;
+    int log2g = 0;
+    if (hadamard_group != 0) {
+        while ((1 << log2g) < hadamard_group) ++log2g;
+        if (hadamard_group < 4 || hadamard_group > 512 || (1 << log2g) != hadamard_group || (p.K % hadamard_group) != 0) return SDNQ_ERR_SHAPE;
+    }
+    const int rb = ref_dtype == SDNQ_F32 ? 4 : 2;
+    if ((uintptr_t)ref % 16 || (ld_ref * rb) % 16 || (uintptr_t)sum_out % 8 || (uintptr_t)workspace % 8 || (p.svd_up && (uintptr_t)p.svd_down % 16))
+        return SDNQ_ERR_ALIGN;
+    const int64_t blocks = loss_blocks(p.N, p.K);
+    if (workspace_bytes < blocks * (int64_t)sizeof(double)) return SDNQ_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int svd_t = p.svd_up ? w->svd_dtype : SDNQ_F32;
+    double* part = (double*)workspace;
+    dim3 grid((unsigned)blocks), block(256);
+#define LOSS_CASE(R, S) \
+    if (ref_dtype == R && svd_t == S) hipLaunchKernelGGL((dequant_loss_kernel<R, S>), grid, block, 0, s, p, ref, ld_ref, log2g, part);
+    LOSS_CASE(SDNQ_F32, SDNQ_F32)
+    else LOSS_CASE(SDNQ_F32, SDNQ_BF16)
+    else LOSS_CASE(SDNQ_F32, SDNQ_F16)
+    else LOSS_CASE(SDNQ_BF16, SDNQ_F32)
+    else LOSS_CASE(SDNQ_BF16, SDNQ_BF16)
+    else LOSS_CASE(SDNQ_BF16, SDNQ_F16)
+    else LOSS_CASE(SDNQ_F16, SDNQ_F32)
+    else LOSS_CASE(SDNQ_F16, SDNQ_BF16)
+    else LOSS_CASE(SDNQ_F16, SDNQ_F16)
+    else return SDNQ_ERR_DTYPE;
+#undef LOSS_CASE
+    SDNQ_CHECK_LAUNCH();
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)part, blocks, sum_out);
     SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
 }

@@ -603,6 +603,35 @@ def dequant(qw: QuantWeight, out_dtype: torch.dtype, hadamard_group: int = 0, us
     return out
 
 
+def dequant_loss_sum(qw: QuantWeight, ref: torch.Tensor, hadamard_group: int = 0) -> torch.Tensor:
+    """sum((dequant(qw, float32, hadamard_group) - ref) ** 2) over [N][K] as a device fp64 scalar, in one fused pass that never writes
+    the dequantized weight (sdnq_hip_dequant_loss; each term (d * d) in fp32, the sum in fp64, bitwise the same on every call).
+    ref: the original float weight, [N, K] (or any shape whose leading dim is N and the rest flattens to K), fp32 / bf16 / f16, rows
+    of unit stride.  Runs on torch's current stream; nothing is synchronised."""
+    _require_cuda(ref)
+    dev = qw.keep[0].device
+    if ref.device != dev:
+        raise _lib.SdnqHipError(f"dequant_loss: ref on {ref.device}, weight on {dev}")
+    r = ref.reshape(qw.n, -1) if ref.dim() != 2 else ref
+    if tuple(r.shape) != (qw.n, qw.k):
+        raise _lib.SdnqHipError(f"dequant_loss: ref shape {tuple(ref.shape)} is not [N, K] = ({qw.n}, {qw.k})")
+    if r.stride(1) != 1 or r.data_ptr() % 16 or (r.stride(0) * r.element_size()) % 16:
+        r = r.contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.sdnq_hip_dequant_loss_workspace_bytes(qw.n, qw.k))
+    check(nbytes if nbytes < 0 else 0, "dequant_loss_workspace_bytes")
+    ws = torch.empty((nbytes // 8 + 1,), device=dev, dtype=torch.float64)
+    out = ws[-1:]
+    check(lib.sdnq_hip_dequant_loss(ctypes.byref(qw.desc), hadamard_group, r.data_ptr(), float_code(r.dtype), r.stride(0), out.data_ptr(),
+                                    ws.data_ptr(), nbytes, _stream(r)), "dequant_loss")
+    return out.view(())
+
+
+def dequant_loss(qw: QuantWeight, ref: torch.Tensor, hadamard_group: int = 0) -> float:
+    """`dequant_loss_sum` read back to the host once (one synchronisation): the fp64 sum of squared reconstruction errors."""
+    return float(dequant_loss_sum(qw, ref, hadamard_group).item())
+
+
 def embedding(qw: QuantWeight, ids: torch.Tensor, out_dtype: torch.dtype, hadamard_group: int = 0, embed_scale: float | None = None) -> torch.Tensor:
     """quantized_embedding (layers/embedding/forward.py:14-68) in one launch: out = ids.shape + [D] rows of the dequantized table
     (SVD added, Hadamard rotation, then * embed_scale).  ids: int32 / int64 of any shape on the table's device; an id outside

@@ -110,6 +110,53 @@ def quantize_weight(weight: torch.Tensor, dim, weights_dtype: str, dtype: torch.
     return q, scale, zero_point
 
 
+def dequantize_host(dq, weight: torch.Tensor, scale: torch.Tensor, zero_point=None, svd_up=None, svd_down=None,
+                    dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Torch restatement of SDNQDequantizer.__call__(..., skip_quantized_matmul=dq.use_quantized_matmul, dtype=dtype) for host tensors
+    (the reference's dequantize_weight, dequantizer.py:135-162, with dequantize_symmetric / _asymmetric / _codebook :15-131): the
+    dynamic search's loss of a candidate on the CPU.  The HIP path computes the same quantity without the copy (ops.dequant_loss_sum)."""
+    from . import packed
+    ent = dtype_dict[dq.weights_dtype]
+    shape = dq.quantized_weight_shape
+    if ent["is_packed"]:
+        if ent["is_integer"]:
+            w = packed.unpack_int(weight, dq.weights_dtype, shape, dtype=torch.int32 if dq.use_codebook else scale.dtype)
+        else:
+            w = packed.unpack_float(weight, dq.weights_dtype, shape)
+    else:
+        w = weight
+    if dq.use_codebook:
+        if dq.group_size == -2:
+            r = scale[w.to(torch.int32)]
+        else:
+            r = scale.gather((2 if dq.group_size != -1 else 1) if dq.is_conv else -1, w.to(torch.int64))
+    elif ent["is_unsigned"]:
+        r = torch.addcmul(zero_point, w.to(scale.dtype), scale)
+    else:
+        r = w.to(scale.dtype) * scale  # (out of place: a native float16 code tensor would be its own .to(float16))
+    if dq.weight_is_transposed:
+        r = r.t()
+    if dq.result_shape is not None:
+        r = r.reshape(dq.result_shape)
+    is_conv = r.ndim > 2 and w.ndim > 2
+    if svd_up is not None:
+        if dq.use_quantized_matmul:
+            svd_up, svd_down = svd_up.t().contiguous(), svd_down.contiguous().t()
+        if is_conv:
+            r = r + torch.mm(svd_up, svd_down).unflatten(-1, tuple(r.shape[1:]))
+        else:
+            r = r.to(svd_up.dtype).addmm_(svd_up, svd_down)
+    r = r.to(dtype)
+    if dq.use_hadamard:
+        g = dq.hadamard_group_size
+        h = get_hadamard(g, dtype=dtype, device=r.device)
+        if is_conv:
+            r = torch.matmul(r.flatten(1, -1).unflatten(-1, (-1, g)), h).flatten(-2, -1).unflatten(-1, tuple(r.shape[1:]))
+        else:
+            r = torch.matmul(r.unflatten(-1, (-1, g)), h).flatten(-2, -1)
+    return r
+
+
 def _lloyd_max_rows(x: torch.Tensor, n_levels: int, steps: int) -> tuple[torch.Tensor, torch.Tensor]:
     """Lloyd-Max levels of every row of a float32 [R, S] matrix -> (codes int64 [R, S], sorted levels float32 [R, L]).
 

@@ -4,9 +4,10 @@ API names are the reference's (quantizer.py: SDNQConfig :846, sdnq_quantize_laye
 sdnq_quantize_layer :423, apply_sdnq_to_module :477, QuantizationMethod :60) so host code switches with an
 import change; the module/tensor layout produced is byte-compatible with reference checkpoints
 (SURVEY App. C), which tests/test_quantizer.py checks against the golden fixtures.  Only what feeds the Linear
-hot path is implemented: no dynamic dtype search, no stochastic rounding, no transposed conv.
+hot path is implemented: no stochastic rounding, no transposed conv.
 Embedding layers (quant_embedding=True) take the reference's non-Linear branch; use_codebook=True stores Lloyd-Max level tables
-(unsigned integer dtypes up to 8 bits).
+(unsigned integer dtypes up to 8 bits); use_dynamic_quantization=True picks each layer's dtype by its reconstruction loss
+(sdnq_quantize_layer_weight_dynamic, reference quantizer.py:279-417).
 """
 from __future__ import annotations
 
@@ -17,11 +18,11 @@ from enum import Enum
 import torch
 
 from . import packed
-from .common import conv_types, dtype_dict, embedding_types, linear_types, sdnq_version
+from .common import conv_types, dtype_dict, embedding_types, linear_types, sdnq_version, weights_dtype_order
 from .dequantizer import SDNQDequantizer
 from .forward import get_forward_func
 from .layers import get_sdnq_wrapper_class
-from .quant_utils import apply_hadamard, apply_svdquant, quantize_codebook, quantize_weight
+from .quant_utils import apply_hadamard, apply_svdquant, dequantize_host, quantize_codebook, quantize_weight
 
 
 class QuantizationMethod(str, Enum):
@@ -63,7 +64,7 @@ class SDNQConfig:
             raise ValueError(f"SDNQ only support weight dtypes in {sorted(dtype_dict)} but found {weights_dtype}")
         if quantized_matmul_dtype is not None and quantized_matmul_dtype not in {"int8", "uint8", "fp8", "fp16", "float8_e4m3fn", "float16"}:
             raise ValueError(f"unsupported quantized_matmul_dtype {quantized_matmul_dtype}")
-        for name in ("use_dynamic_quantization", "use_stochastic_rounding", "is_training"):
+        for name in ("use_stochastic_rounding", "is_training"):
             if locals()[name]:
                 raise NotImplementedError(f"SDNQConfig({name}=True) is outside the MI355X Linear hot path")
         if use_codebook and not (dtype_dict[weights_dtype]["is_integer"] and dtype_dict[weights_dtype]["is_unsigned"]):
@@ -163,11 +164,14 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
                                quantized_matmul_dtype: str | None = None, group_size: int = 0, hadamard_group_size: int = 256,
                                svd_rank: int = 32, svd_steps: int = 8, use_svd: bool = False, use_hadamard: bool = False,
                                use_quantized_matmul: bool = False, dequantize_fp32: bool = True,
-                               torch_dtype: torch.dtype | None = None, use_codebook: bool = False, codebook_steps: int = 24, **_unused):
+                               torch_dtype: torch.dtype | None = None, use_codebook: bool = False, codebook_steps: int = 24,
+                               using_pre_calculated_svd: bool = False, using_pre_rotated_hadamard: bool = False, **_unused):
     """Float [N,K] weight -> (SDNQDequantizer, {"weight","scale","zero_point","svd_up","svd_down"}).
 
     Order of operations as in the reference (quantizer.py:158-253): Hadamard -> SVD split -> grouping ->
-    quantize -> (transpose for direct matmul) -> pack.
+    quantize -> (transpose for direct matmul) -> pack.  using_pre_calculated_svd / using_pre_rotated_hadamard: the dynamic search
+    (sdnq_quantize_layer_weight_dynamic) hands over a weight it already split / rotated -- the group policy counts the SVD and the
+    dequantizer undoes the rotation (quantizer.py:187-188, 276).
     """
     is_conv = layer_class_name in conv_types
     is_embedding = layer_class_name in embedding_types
@@ -205,7 +209,8 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
         if use_qmm:  # the matmul branch consumes x @ svd_down then @ svd_up: store both transposed (:164-167)
             svd_up, svd_down = svd_up.t(), svd_down.t()
 
-    group_size, groups = _pick_group_size(group_size, channels, weights_dtype, layer_class_name in linear_types, svd_up is not None,
+    group_size, groups = _pick_group_size(group_size, channels, weights_dtype, layer_class_name in linear_types,
+                                          svd_up is not None or using_pre_calculated_svd,
                                           direct_matmul=use_qmm and not requant, codebook=use_codebook)
     dim = 1 if (is_conv and not flat) else -1
     if groups > 1:
@@ -271,7 +276,8 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
                          weights_dtype=weights_dtype, quantized_matmul_dtype=mm_dtype, hadamard_group_size=hadamard_group_size,
                          group_size=group_size, svd_rank=svd_rank, svd_steps=svd_steps, codebook_steps=codebook_steps,
                          use_quantized_matmul=use_qmm, re_quantize_for_matmul=requant, use_stochastic_rounding=False,
-                         use_hadamard=bool(use_hadamard), use_codebook=bool(use_codebook), layer_class_name=layer_class_name)
+                         use_hadamard=bool(use_hadamard or using_pre_rotated_hadamard), use_codebook=bool(use_codebook),
+                         layer_class_name=layer_class_name)
     return dq, {"weight": q, "scale": scale, "zero_point": zero_point, "svd_up": svd_up, "svd_down": svd_down}
 
 
@@ -301,6 +307,103 @@ def _quantize_codebook_layer(weight: torch.Tensor, dim: int, weights_dtype: str,
         if ent["torch_dtype"] == torch.bool:  # the reference packs 1-bit codes from a bool tensor: int64 words of 8 bits each
             codes = codes.to(torch.int64)
     return codes.to(weight.device), levels.to(weight.device)
+
+
+def _candidate_mse(dq: SDNQDequantizer, data: dict, original: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+    """mse_loss(original, dequantize(candidate)) of one candidate of the dynamic search (reference quantizer.py:384-397) as a 0-dim
+    tensor on the weight's device, float32 (float64 for float64 weights).  GPU tensors: ONE fused HIP pass over the codes and `ref`
+    (the original weight in its own 16-bit or float32 dtype, an exact upcast) that never writes the dequantized weight
+    (ops.dequant_loss_sum: fp32 terms, fp64 sum; the mean is rounded to float32).  Host tensors and float64 weights: the torch
+    restatement of the dequantizer and F.mse_loss -- as do GPU layers whose reduction length K is not a multiple of 16 (a Linear with
+    in_features 100, a conv with C_in * kh * kw = 36), which no weight-side kernel lays out; the quantizer itself takes torch ops there
+    too (sdnq_quantize_layer_weight: `k % 16 == 0` gates the HIP quantizer)."""
+    if original.is_cuda and original.dtype == torch.float32 and (original.numel() // original.shape[0]) % 16 == 0:
+        from . import ops
+        qw = dq.quant_weight(data["weight"], data["scale"], data["zero_point"], data["svd_up"], data["svd_down"])
+        s = ops.dequant_loss_sum(qw, ref, dq.hadamard_group_size if dq.use_hadamard else 0)
+        return (s / original.numel()).to(torch.float32)
+    deq = dequantize_host(dq, data["weight"], data["scale"], data["zero_point"], data["svd_up"], data["svd_down"], dtype=original.dtype)
+    return torch.nn.functional.mse_loss(original, deq.reshape(original.shape))
+
+
+@torch.no_grad()
+def sdnq_quantize_layer_weight_dynamic(weight: torch.Tensor, layer_class_name: str | None = None, weights_dtype: str = "uint4",
+                                       quantized_matmul_dtype: str | None = None, group_size: int = 0, hadamard_group_size: int = 256,
+                                       svd_rank: int = 32, svd_steps: int = 8, codebook_steps: int = 24,
+                                       dynamic_loss_threshold: float | None = None, use_svd: bool = False, use_hadamard: bool = False,
+                                       use_codebook: bool = False, use_quantized_matmul: bool = False, use_stochastic_rounding: bool = False,
+                                       dequantize_fp32: bool = True, hadamard: torch.Tensor | None = None, param_name: str | None = None,
+                                       torch_dtype: torch.dtype | None = None, quantization_config: SDNQConfig | None = None, **_unused):
+    """Dynamic quantization (reference quantizer.py:279-417): walk weights_dtype_order from `weights_dtype` and keep the first candidate
+    whose mse_loss(W, dequantize(q)) / var(W) is <= dynamic_loss_threshold (default 10 ** -(bits / 2) of the starting dtype).
+
+    Hadamard and SVD are applied once, before the walk; each candidate is quantized by sdnq_quantize_layer_weight and scored by
+    `_candidate_mse` (one fused HIP pass on GPU tensors, one host sync to read the verdict: the early exit needs the value).
+    -> (SDNQDequantizer, tensors) or None when no candidate passes (the layer stays float); with a quantization_config, the pair
+    (that, config) and the choice recorded: modules_dtype_dict[dtype] gets the layer, modules_to_not_use_matmul the layers the
+    candidate's matmul dtype excluded, modules_to_not_convert the layers that stay float."""
+    if use_stochastic_rounding:
+        raise NotImplementedError("use_stochastic_rounding is a training feature and is not built")
+    if torch_dtype is None:
+        torch_dtype = weight.dtype
+    if dynamic_loss_threshold is None or dynamic_loss_threshold < 0:
+        dynamic_loss_threshold = 10 ** -(dtype_dict[weights_dtype]["num_bits"] / 2)
+    start = weights_dtype_order.index(weights_dtype)  # an unknown starting dtype raises ValueError, as in the reference
+    is_conv = layer_class_name in conv_types
+    source = weight.detach()
+    weight = source if source.dtype == torch.float64 else source.to(torch.float32)
+    weight_std = weight.std().square_().clamp_(min=1e-8)
+    original = weight
+    # the kernel reads the original in its own dtype (16-bit -> float32 is exact): no float32 copy is streamed per candidate
+    ref = source if source.dtype in (torch.bfloat16, torch.float16) else original
+
+    if use_hadamard:
+        weight, use_hadamard, hadamard_group_size = apply_hadamard(weight, hadamard_group_size, is_conv=is_conv)
+    svd_up = svd_down = svd_up_t = svd_down_t = None
+    if use_svd:
+        try:
+            weight, svd_up, svd_down = apply_svdquant(weight, rank=svd_rank, steps=svd_steps, dtype=torch_dtype)
+            svd_up, svd_down = svd_up.contiguous(), svd_down.contiguous()
+            if use_quantized_matmul:  # the factors of a layer on the quantized matmul are stored transposed (quantizer.py:164-167)
+                svd_up_t, svd_down_t = svd_up.clone().t(), svd_down.clone().t()
+        except Exception:  # noqa: BLE001  (a failed SVD drops the factors, quantizer.py:317-319)
+            svd_up = svd_down = svd_up_t = svd_down_t = None
+
+    start_bits = dtype_dict[weights_dtype]["num_bits"]
+    for current in weights_dtype_order[start:]:
+        ent = dtype_dict[current]
+        if use_codebook and not (ent["is_unsigned"] and ent["is_integer"]):
+            continue
+        if use_codebook and ent["num_bits"] > 8:
+            raise NotImplementedError(f"{param_name}: the dynamic codebook search reached {current}; codebooks wider than 8 bits are not built")
+        current_mm = get_quantized_matmul_dtype(current, quantized_matmul_dtype)
+        mm = dtype_dict[current_mm]
+        # fp8 matmuls are supported on gfx950 (kernel_wrappers.is_fp8_mm_supported): only the reference's three format conditions
+        # take a candidate off the quantized matmul (quantizer.py:343-354)
+        add_to_not_use_matmul = bool((mm["is_integer"] and not ent["is_integer"])
+                                     or (ent["num_bits"] == mm["num_bits"] and ent["is_unsigned"] and not mm["is_integer"])
+                                     or (start_bits <= mm["num_bits"] and ent["num_bits"] > mm["num_bits"]))
+        current_use_qmm = use_quantized_matmul and not add_to_not_use_matmul
+        dq, data = sdnq_quantize_layer_weight(weight, layer_class_name=layer_class_name or "Linear", weights_dtype=current,
+                                              quantized_matmul_dtype=current_mm, torch_dtype=torch_dtype,
+                                              hadamard_group_size=hadamard_group_size, group_size=group_size, svd_rank=svd_rank,
+                                              svd_steps=svd_steps, codebook_steps=codebook_steps, use_svd=False, use_hadamard=False,
+                                              use_codebook=use_codebook, use_quantized_matmul=current_use_qmm,
+                                              dequantize_fp32=dequantize_fp32, using_pre_calculated_svd=use_svd,
+                                              using_pre_rotated_hadamard=use_hadamard)
+        data["svd_up"], data["svd_down"] = (svd_up_t, svd_down_t) if dq.use_quantized_matmul else (svd_up, svd_down)
+        loss = _candidate_mse(dq, data, original, ref).div_(weight_std.to(original.device))
+        if bool(loss <= dynamic_loss_threshold):  # the tensor comparison rounds the threshold to the loss dtype, as the reference's
+            if quantization_config is None:
+                return dq, data
+            quantization_config.modules_dtype_dict.setdefault(dq.weights_dtype, []).append(param_name)
+            if add_to_not_use_matmul and check_param_name_in(param_name, quantization_config.modules_to_not_use_matmul) is None:
+                quantization_config.modules_to_not_use_matmul.append(param_name)
+            return (dq, data), quantization_config
+    if quantization_config is None:
+        return None
+    quantization_config.modules_to_not_convert.append(param_name)
+    return None, quantization_config
 
 
 def check_param_name_in(param_name: str, param_list) -> str | None:
@@ -346,7 +449,8 @@ def _quant_kwargs(cfg: SDNQConfig, torch_dtype, param_name: str, layer_class_nam
               hadamard_group_size=cfg.hadamard_group_size, svd_rank=cfg.svd_rank, svd_steps=cfg.svd_steps,
               use_svd=cfg.use_svd, use_hadamard=cfg.use_hadamard, use_quantized_matmul=cfg.use_quantized_matmul,
               dequantize_fp32=cfg.dequantize_fp32, torch_dtype=torch_dtype, use_codebook=cfg.use_codebook,
-              codebook_steps=cfg.codebook_steps)
+              codebook_steps=cfg.codebook_steps, use_dynamic_quantization=cfg.use_dynamic_quantization,
+              dynamic_loss_threshold=cfg.dynamic_loss_threshold)
     conv_mm = cfg.use_quantized_matmul_conv
     key = check_param_name_in(param_name, list(cfg.modules_quant_config.keys()))
     if key is not None:
@@ -379,11 +483,22 @@ def sdnq_quantize_layer(layer: torch.nn.Module, quantization_config: SDNQConfig,
     if not _quantizable_class(name, quantization_config):  # quantizer.py:429-435
         quantization_config.modules_to_not_convert.append(param_name)
         return layer, quantization_config
-    kw = quant_kwargs or _quant_kwargs(quantization_config, torch_dtype, param_name, name)
+    kw = dict(quant_kwargs or _quant_kwargs(quantization_config, torch_dtype, param_name, name))
+    dynamic = kw.pop("use_dynamic_quantization", False)
+    threshold = kw.pop("dynamic_loss_threshold", None)
     layer.weight.requires_grad_(False)
     dev = layer.weight.device if quantization_config.return_device is None else quantization_config.return_device
     w = layer.weight if quantization_config.quantization_device is None else layer.weight.to(quantization_config.quantization_device)
-    dq, tensors = sdnq_quantize_layer_weight(w, layer_class_name=name, **kw)
+    if dynamic and not w.is_meta:  # (a meta skeleton is never searched: its dtypes come from the stored config)
+        result, quantization_config = sdnq_quantize_layer_weight_dynamic(w, layer_class_name=name, dynamic_loss_threshold=threshold,
+                                                                         param_name=param_name, quantization_config=quantization_config,
+                                                                         **kw)
+        if result is None:  # no candidate passed: the layer stays float (quantizer.py:466-467), listed in modules_to_not_convert
+            layer.weight = torch.nn.Parameter(layer.weight.to(dev, dtype=torch_dtype), requires_grad=False)
+            return layer, quantization_config
+        dq, tensors = result
+    else:
+        dq, tensors = sdnq_quantize_layer_weight(w, layer_class_name=name, **kw)
     layer.sdnq_dequantizer = dq
     layer = get_sdnq_wrapper_class(layer, get_forward_func(name, dq.quantized_matmul_dtype, dq.use_quantized_matmul))
     for key, value in tensors.items():  # (a meta skeleton -- load_sdnq_model -- keeps meta placeholders of the stored shapes and dtypes)
@@ -431,6 +546,8 @@ def sdnq_post_load_quant(model: torch.nn.Module, weights_dtype: str = "int8", to
     loader's use (loader.py:150): `model` is a skeleton (meta tensors), the layers become SDNQ layers with placeholders of the stored
     shapes, and nothing is computed."""
     cfg = quantization_config if quantization_config is not None else SDNQConfig(weights_dtype=weights_dtype, **kwargs)
+    if pre_quantized:  # a stored checkpoint is never searched again: its dtypes are in modules_dtype_dict (quantizer.py:535-540)
+        cfg.use_dynamic_quantization = False
     model, cfg = apply_sdnq_to_module(model, cfg, torch_dtype=torch_dtype, pre_quantized=pre_quantized)
     model.quantization_config = cfg
     model.quantization_method = QuantizationMethod.SDNQ
