@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI library ``libsdnq_hip.so`` (include/sdnq_hip.h).
 
-The shared object is built in-tree by ``sdnq_amd/csrc/build.sh`` (hipcc --offload-arch=gfx950) so
+The shared object is built in-tree by ``build()`` (the recipe is ``sdnq_amd/_build.py``; hipcc --offload-arch=gfx950) so
 that it travels with the source snapshot; nothing here falls back to another implementation: if
 the library is missing or the device is not gfx950 the product path raises.
 """
@@ -8,12 +8,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-import subprocess
 import threading
+
+from . import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SDNQ_HIP_LIB") or os.path.join(_HERE, "libsdnq_hip.so")  # override: development builds only
-_CSRC = os.path.join(_HERE, "csrc")
 
 # enums of include/sdnq_hip.h
 F32, BF16, F16 = 0, 1, 2
@@ -80,59 +80,25 @@ _lock = threading.Lock()
 _lib = None
 
 
-_SRCS = ("api", "rowquant", "gemm", "gemm_aq", "gemm_ks", "gemm_w4", "dequant", "quantize", "conv", "attention", "parallel")
-_FLAGS = " --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-command-line-argument"
-
-
 def source_hash() -> str:
-    """SHA-256 over every HIP source, header and compiler flag, computed exactly as sdnq_amd/csrc/build.sh does: the library that
-    is loaded is the one built from the sources in the tree iff this equals the contents of ``libsdnq_hip.so.srchash``."""
-    import hashlib
-    hdrs = sorted(f for f in os.listdir(_CSRC) if f.endswith(".h"))
-    h = hashlib.sha256()
-    for f in hdrs:
-        h.update(open(os.path.join(_CSRC, f), "rb").read())
-    h.update(open(os.path.join(_HERE, "..", "include", "sdnq_hip.h"), "rb").read())
-    hdr_hash = h.hexdigest()
-    flags = os.environ.get("SDNQ_EXTRA_FLAGS", "") + _FLAGS.replace("-ffp-contract=off", "-ffp-contract=" + os.environ.get("SDNQ_FP_CONTRACT", "off"))
-    parts = ""
-    for f in _SRCS:
-        extra = "-mllvm -amdgpu-mfma-vgpr-form" if f == "attention" else ""
-        if f == "rowquant" and os.environ.get("SDNQ_PRELOAD_ROWQUANT", "1") != "0":  # as build.sh
-            extra = "-DSDNQ_PRELOAD_ROWQUANT -mllvm -amdgpu-kernarg-preload-count=14"
-        if f == "gemm" and os.environ.get("SDNQ_PRELOAD_GEMM", "1") != "0":
-            extra = "-DSDNQ_PRELOAD_GEMM -mllvm -amdgpu-kernarg-preload-count=14"
-        if f in ("dequant", "conv", "gemm_aq", "gemm_ks", "gemm_w4"):
-            extra = "-mllvm -amdgpu-kernarg-preload-count=14"
-        g = hashlib.sha256((f"{hdr_hash} {flags} {extra}\n").encode())
-        g.update(open(os.path.join(_CSRC, f + ".hip"), "rb").read())
-        parts += f" {f}:{g.hexdigest()}"
-    parts += " binding:" + hashlib.sha256(open(os.path.join(_CSRC, "binding.c"), "rb").read()).hexdigest()
-    parts += " fastpath:" + hashlib.sha256(open(os.path.join(_CSRC, "fastpath.cpp"), "rb").read()
-                                           + open(os.path.join(_HERE, "..", "include", "sdnq_hip.h"), "rb").read()).hexdigest()
-    return hashlib.sha256((parts + "\n").encode()).hexdigest()
+    """The source hash of the tree (_build.source_hash): the library that is loaded is the one built from the sources in the tree iff
+    this equals the contents of ``libsdnq_hip.so.srchash``."""
+    return _build.source_hash()
 
 
 def lib_is_current() -> bool:
     try:
-        host = [os.path.join(os.path.dirname(LIB_PATH), f) for f in ("_binding.so", "_fastpath.so")]  # built by the same script
-        return os.path.exists(LIB_PATH) and all(os.path.exists(f) for f in host) and open(LIB_PATH + ".srchash").read().strip() == source_hash()
+        return (os.path.exists(LIB_PATH) and all(os.path.exists(f) for f in _build.host_modules(LIB_PATH))
+                and open(LIB_PATH + ".srchash").read().strip() == source_hash())
     except OSError:
         return False
-
-
-def sources_newer_than_lib() -> bool:  # kept for callers of the old name
-    return not lib_is_current()
 
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into sdnq_amd/libsdnq_hip.so (no GPU needed).  Content-addressed: nothing is rebuilt
     when the library's recorded source hash equals the hash of the tree; `force` recompiles every object."""
     if force or not lib_is_current():
-        env = dict(os.environ, FORCE="1") if force else None
-        subprocess.run(["bash", os.path.join(_CSRC, "build.sh"), LIB_PATH], check=True, env=env)
-        if not lib_is_current():
-            raise SdnqHipError("libsdnq_hip.so was built but its source hash does not match the tree (build.sh / _lib.source_hash out of sync)")
+        _build.build(LIB_PATH, force=force)
     return LIB_PATH
 
 
@@ -256,7 +222,7 @@ def _with_typed_binding(lib):
     if not USE_BINDING:
         return lib
     try:
-        from . import _binding  # built by csrc/build.sh next to the library
+        from . import _binding  # built by build() next to the library
     except ImportError:
         return lib  # binding only: every call still lands in libsdnq_hip.so, through ctypes
     _binding.init(LIB_PATH)

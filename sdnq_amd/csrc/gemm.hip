@@ -442,7 +442,7 @@ constexpr int HT_BYTES = 16384, HT_SLOTS = 8;
 // the product with the activation scale is rounded to bf16, and the last fma (fp32 op-math) is rounded by the bf16 store.
 template <int MM, int OUT_T, int EPI, int BM, int BN, int WM, int WN, int NS, int LD, int BK, bool LP = false>
 // Kernel arguments: the 14 dwords everything in front of the first LDS-DMA needs come FIRST, as scalars -- a kernarg-preloading build
-// (-mllvm -amdgpu-kernarg-preload-count=14, build.sh) delivers them in SGPRs with the wave, so tile mapping, descriptors and the prologue
+// (-mllvm -amdgpu-kernarg-preload-count=14, _build.py) delivers them in SGPRs with the wave, so tile mapping, descriptors and the prologue
 // DMAs run without a scalar-cache round trip; the rest of the parameter struct is fetched in one batch behind them.  hk_flags: bits 0-7
 // group_m, 8-15 swz, 16 fastmap, 17 fastunit, 18 grouped launch.
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const uint8_t* hk_a, const uint8_t* hk_b, int hk_lda, int hk_ldb, int hk_M,
@@ -1072,7 +1072,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
 #endif
         };
 #ifdef SDNQ_LAB_LUT4
-        // TIMING-ONLY lab build (wrong results; tools/lut4_lab.sh): what a fused 4-bit loader would add to this K loop.  Every weight
+        // TIMING-ONLY lab build (wrong results; _build.py --define SDNQ_LAB_LUT4): what a fused 4-bit loader would add to this K loop.  Every weight
         // fragment is treated as 8 bytes of packed codes + a 16-entry byte table of its (row, group) and expanded to the 16 int8 codes
         // of the MFMA operand with the cheapest sequence found (nibble split, two v_perm per 4 codes, bit-3 blend; the even / odd
         // interleave is assumed away by a k-permuted activation operand): 34 vector-ALU instructions per fragment, placed in the

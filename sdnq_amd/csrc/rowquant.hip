@@ -74,7 +74,7 @@ __device__ __forceinline__ void store8(void* row, int64_t idx, const float (&v)[
 // THAT dtype (`input.to(dtype=scale.dtype)`, linear_int8.py:15-22): scale = round_T(amax / qmax), q = rint(round_T(x / scale)).
 // Built for the two-phase path only (NP == 0): a compatibility mode, not the tuned one.
 template <int T_ID, int MM, bool HAD, int NP, int WPR = 1, bool LP = false>
-// Argument order: what the row loads need first -- 14 dwords, the part a kernarg-preloading build (SDNQ_PRELOAD_ROWQUANT, build.sh)
+// Argument order: what the row loads need first -- 14 dwords, the part a kernarg-preloading build (SDNQ_PRELOAD_ROWQUANT, _build.py)
 // delivers in SGPRs with the wave -- then the rest, fetched in one batch (SDNQ_KERNARGS_NOW, sdnq_dev.h).
 __global__ __launch_bounds__(256) void rowquant_kernel(const void* __restrict__ x, int64_t M, int64_t K, int64_t ldx, int row_blocks,
                                                        int log2g, uint8_t* __restrict__ xq, float* __restrict__ xs,

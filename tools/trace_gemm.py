@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Development aid: per-workgroup phase timeline of the GEMM kernel (needs the -DSDNQ_TRACE build: tools/build_trace.sh)."""
+"""Development aid: per-workgroup phase timeline of the GEMM kernel (needs the -DSDNQ_TRACE build:
+    python sdnq_amd/_build.py --define SDNQ_TRACE --out build/libsdnq_hip_trace.so
+    SDNQ_HIP_LIB=$PWD/build/libsdnq_hip_trace.so python tools/trace_gemm.py [--lowrank | --w8a16])."""
 import ctypes, os, sys
 import numpy as np
 import torch

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Development aid: phase timeline of ONE GEMM problem as it runs INSIDE a bench.py step (cold weights from HBM, its row quantizer in
-front of it) next to the same launch replayed alone.  Needs the -DSDNQ_TRACE build (tools/build_trace.sh):
+front of it) next to the same launch replayed alone.  Needs the -DSDNQ_TRACE build
+(python sdnq_amd/_build.py --define SDNQ_TRACE --out build/libsdnq_hip_trace.so):
     SDNQ_HIP_LIB=$PWD/build/libsdnq_hip_trace.so python tools/trace_in_step.py [workload] "M,N,K;M,N,K"   [SDNQ_HIP_TILE_MAP=... to force tiles]"""
 import ctypes, os, sys
 import numpy as np
