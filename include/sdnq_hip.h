@@ -696,6 +696,27 @@ int sdnq_hip_attn(const void* q, const void* k, const void* v, int dtype, int64_
                   int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* out, int out_dtype,
                   const int64_t* out_strides, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* Quantized attention backward (the default configuration: int8 Q.K^T, P.V in the value dtype) on the operands of sdnq_hip_attn_prepare
+ * with Q quantized (qq / qs), K in fragment order (kq / ks).
+ * sdnq_hip_attn_lse <- the save_lse tail of sdnq_attn_kernel (triton_atten.py:328-334): lse [batch][q_heads][q_len] of lse_dtype (the
+ *   output dtype) = m + log2(l) in the log2(e) * sm_scale domain; 0 for a row with no visible key when a mask is given.  One launch.
+ * sdnq_hip_attn_bwd <- sdnq_triton_atten_bwd (triton_atten_backward.py:728-841) without the Hadamard rotation back:
+ *   delta [batch * q_heads * q_len] f32 workspace = sum(out * grad) (get_attn_backward_inputs, :705-724), then
+ *   dq <- sdnq_attn_bwd_dq_kernel (:139-223) and dk / dv <- sdnq_attn_bwd_dkv_kernel (:344-483); dq / dk / dv NULL: not computed.
+ *   v [batch][kv_heads][kv_len][head_dim] and grad_v (dO as the matmul operand) in v_dtype; out, grad, lse and dq / dk / dv in grad_dtype;
+ *   every tensor with element strides (NULL: contiguous); dq_channels / dk_channels: head_dim, or the padded 64 / 128 (a Hadamard rotation
+ *   is undone by the caller over the padded head dim).  Launches: delta, dq, dk + dv (three at most); deterministic, no atomics. */
+int sdnq_hip_attn_lse(const void* qq, const float* qs, const void* kq, const float* ks, float sm_scale, int is_causal, const void* mask,
+                      int mask_dtype, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* lse, int lse_dtype,
+                      int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len, int64_t head_dim, sdnq_stream_t stream);
+int sdnq_hip_attn_bwd(const void* qq, const float* qs, const void* kq, const float* ks, const void* v, const int64_t* v_strides, int v_dtype,
+                      const void* out, const int64_t* out_strides, const void* grad, const int64_t* grad_strides, int grad_dtype,
+                      const void* grad_v, const int64_t* grad_v_strides, const void* lse, float sm_scale, int is_causal, const void* mask,
+                      int mask_dtype, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, float* delta,
+                      void* dq, const int64_t* dq_strides, int64_t dq_channels, void* dk, const int64_t* dk_strides, int64_t dk_channels,
+                      void* dv, const int64_t* dv_strides, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len,
+                      int64_t kv_len, int64_t head_dim, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

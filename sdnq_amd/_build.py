@@ -51,6 +51,7 @@ UNITS = (
     # attention.hip: keep the MFMA accumulators in VGPRs (the softmax rescales / reads them with VALU every block; in AGPR form
     # the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),
+    ("attention_bwd", "", None),
     ("parallel", "", None),
 )
 

@@ -37,7 +37,7 @@ EXPORTS = [
     "sdnq_hip_linear_w8a8_fused", "sdnq_hip_linear_w8a8_fused_supported", "sdnq_hip_scaled_mm_lp_uzp_svd", "sdnq_hip_stream_capture_id",
     "sdnq_hip_scaled_mm_tile", "sdnq_hip_lut4_build", "sdnq_hip_scaled_mm_w4", "sdnq_hip_scaled_mm_w4_supported",
     "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding", "sdnq_hip_quantize_codebook",
-    "sdnq_hip_dequant_loss", "sdnq_hip_dequant_loss_workspace_bytes",
+    "sdnq_hip_dequant_loss", "sdnq_hip_dequant_loss_workspace_bytes", "sdnq_hip_attn_lse", "sdnq_hip_attn_bwd",
 ]
 
 
@@ -172,6 +172,9 @@ def _declare(lib):
     lib.sdnq_hip_attn_fwd_q16.argtypes = [vp, vp, vp, vp, vp, i32, c.c_float, i32, vp, i32, i64, i64, i64, vp, i32, vp] + [i64] * 6 + [vp]
     lib.sdnq_hip_attn.argtypes = [vp, vp, vp, i32] + [i64] * 6 + [vp, vp, vp, i32, i32, c.c_float, i32, vp, i32, i64, i64, i64, vp, i32, vp, vp, i64, vp]
     lib.sdnq_hip_attn_workspace_bytes.argtypes = [i64] * 6 + [i32]
+    lib.sdnq_hip_attn_lse.argtypes = [vp, vp, vp, vp, c.c_float, i32, vp, i32, i64, i64, i64, vp, i32] + [i64] * 6 + [vp]
+    lib.sdnq_hip_attn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, c.c_float, i32, vp, i32, i64, i64, i64, vp,
+                                      vp, vp, i64, vp, vp, i64, vp, vp] + [i64] * 6 + [vp]
     lib.sdnq_hip_scaled_mm_tile.argtypes = [i32, i32, i32, i64, i64, i64, c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int), c.POINTER(c.c_int64)]
     lib.sdnq_hip_lut4_build.argtypes = [c.POINTER(SdnqWeight), i32, vp, i32, vp, vp]
     lib.sdnq_hip_scaled_mm_w4.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, i64, i64, i64, i64, vp]

@@ -286,3 +286,125 @@ def sdnq_hip_atten(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, 
                                 1 if is_causal else 0, mptr, mdt, *ms, out.data_ptr(), ops.float_code(out_dtype), _strides(out),
                                 ws.data_ptr() if ws is not None else None, nbytes, ops._stream(query)), "attn")
     return out
+
+
+# ---- backward (sdnq_triton_atten_with_backward, kernels/triton_atten_backward.py:844-950) ------------------------------------------------
+def _mask_args(attn_mask):
+    if attn_mask is None:
+        return None, 0, (0, 0, 0)
+    mdt = -1 if attn_mask.dtype == torch.int8 else ops.float_code(attn_mask.dtype)
+    return attn_mask.data_ptr(), mdt, tuple(attn_mask.stride(i) if attn_mask.shape[i] != 1 else 0 for i in range(3))
+
+
+def atten_lse(qq, qs, kq, ks, kn: int, sm_scale: float, is_causal: bool, lse_dtype: torch.dtype, attn_mask: torch.Tensor | None = None,
+              head_dim: int | None = None) -> torch.Tensor:
+    """The lse output of the reference's forward (triton_atten.py:328-334) on the operands of ``quantize_attn``: [Z, QH, QN] of ``lse_dtype``
+    (the output dtype), m + log2(l) in the log2(e) * sm_scale domain, 0 for a row with no visible key when a mask is given."""
+    z, qh, qn, d = qq.shape
+    lse = torch.empty((z, qh, qn), device=qq.device, dtype=lse_dtype)
+    mptr, mdt, ms = _mask_args(attn_mask)
+    ops.check(_lib.load().sdnq_hip_attn_lse(qq.data_ptr(), qs.data_ptr(), kq.data_ptr(), ks.data_ptr(), float(sm_scale), 1 if is_causal else 0,
+                                            mptr, mdt, *ms, lse.data_ptr(), ops.float_code(lse_dtype), z, qh, kq.shape[1], qn, kn,
+                                            head_dim or d, ops._stream(qq)), "attn_lse")
+    return lse
+
+
+def atten_bwd(grad: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, qq, qs, kq, ks, value: torch.Tensor, sm_scale: float, is_causal: bool,
+              attn_mask: torch.Tensor | None = None, hadamard_group: int = 0, need=(True, True, True), token_major: bool = False):
+    """sdnq_triton_atten_bwd (triton_atten_backward.py:728-841) for the default configuration: (dq, dk, dv) in the dtype of ``grad``,
+    None where ``need`` says so.  Under a rotation dq and dk come back out of the rotated basis over the padded head dim; dv is not rotated."""
+    z, qh, qn, dp = qq.shape
+    _, kh, kn, d = value.shape
+    gdt = grad.dtype
+    grad = _rows16(grad)
+    grad_v = grad if gdt == value.dtype else _rows16(grad.to(value.dtype))  # dO as the operand of dO.V^T and dO^T.P
+    dev = grad.device
+    delta = torch.empty((z * qh * qn,), device=dev, dtype=torch.float32)
+    ch = dp if hadamard_group else d
+    dq = dk = dv = None
+    if need[0]:
+        dq = (torch.empty((z, qn, qh, ch), device=dev, dtype=gdt).transpose(1, 2) if token_major and not hadamard_group
+              else torch.empty((z, qh, qn, ch), device=dev, dtype=gdt))
+    if need[1]:
+        dk = torch.empty((z, kh, kn, ch), device=dev, dtype=gdt)
+    if need[2]:
+        dv = torch.empty((z, kh, kn, d), device=dev, dtype=gdt)
+    if not any(need):
+        return None, None, None
+    mptr, mdt, ms = _mask_args(attn_mask)
+
+    def ptr(t):
+        return (t.data_ptr(), _strides(t)) if t is not None else (None, None)
+    ops.check(_lib.load().sdnq_hip_attn_bwd(qq.data_ptr(), qs.data_ptr(), kq.data_ptr(), ks.data_ptr(), value.data_ptr(), _strides(value),
+                                            ops.float_code(value.dtype), out.data_ptr(), _strides(out), grad.data_ptr(), _strides(grad),
+                                            ops.float_code(gdt), grad_v.data_ptr(), _strides(grad_v), lse.data_ptr(), float(sm_scale),
+                                            1 if is_causal else 0, mptr, mdt, *ms, delta.data_ptr(), *ptr(dq), ch, *ptr(dk), ch, *ptr(dv),
+                                            z, qh, kh, qn, kn, d, ops._stream(grad)), "attn_bwd")
+    if hadamard_group:  # rotate_hadamard_compiled(..)[..., :QHD] (:782-784, 832-835), in the grad dtype
+        if dq is not None:
+            dq = ops.hadamard(dq, hadamard_group)[..., :d]
+        if dk is not None:
+            dk = ops.hadamard(dk, hadamard_group)[..., :d]
+    return dq, dk, dv
+
+
+class SDNQAttenBackward(torch.autograd.Function):
+    """SDNQAttenBackward (triton_atten_backward.py:844-916): the forward is quantize_attn + the forward kernel (the three-call route of
+    ``sdnq_hip_atten``, bit for bit the same output) plus the lse pass; the backward runs the HIP dQ and dK / dV kernels."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, attn_mask, is_causal, sm_scale, smooth_k, group, out_dtype, token_major):
+        qq, qs, kq, ks, vt = quantize_attn(query, key, value, smooth_k=smooth_k, hadamard_group=group)
+        d, kn = query.shape[-1], key.shape[2]
+        out = atten_fwd(qq, qs, kq, ks, vt, kn, sm_scale, is_causal, out_dtype, attn_mask, token_major=token_major, head_dim=d)
+        lse = atten_lse(qq, qs, kq, ks, kn, sm_scale, is_causal, out_dtype, attn_mask, head_dim=d)
+        ctx.sm_scale, ctx.is_causal, ctx.group, ctx.token_major = sm_scale, is_causal, group, token_major
+        ctx.save_for_backward(qq, qs, kq, ks, _rows16(value), out, lse, attn_mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        qq, qs, kq, ks, value, out, lse, attn_mask = ctx.saved_tensors
+        dq, dk, dv = atten_bwd(grad_output, out, lse, qq, qs, kq, ks, value, ctx.sm_scale, ctx.is_causal, attn_mask, ctx.group,
+                               need=tuple(ctx.needs_input_grad[:3]), token_major=ctx.token_major)
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def sdnq_hip_atten_with_backward(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask: torch.Tensor | None = None,
+                                 dropout_p: float = 0.0, is_causal: bool = False, scale: float | None = None, enable_gqa: bool = False,
+                                 smooth_k: bool = True, use_hadamard: bool = False, hadamard_group_size: int = 256,
+                                 matmul_dtype: str = "int8", pv_matmul_dtype: str | None = None, do_quantize: bool = True,
+                                 use_fp16_accum: bool = False, out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """Drop-in for ``sdnq_triton_atten_with_backward`` (triton_atten_backward.py:919-950): the attention of ``sdnq_hip_atten`` with a
+    backward on HIP kernels.  Built: int8 Q.K^T (and its spellings) with P.V in the value dtype; other formats raise NotImplementedError."""
+    if use_fp16_accum:
+        raise NotImplementedError("use_fp16_accum is an RDNA work-around; the MI355X kernels accumulate in fp32")
+    if not do_quantize or matmul_dtype in _DISABLED:
+        raise NotImplementedError("the unquantized attention (do_quantize=False / matmul_dtype disabled) is torch's SDPA, not an SDNQ kernel")
+    mm, pv = _mm_name(matmul_dtype), _mm_name(pv_matmul_dtype, pv=True)
+    if mm != "int8":
+        raise NotImplementedError(f"the attention backward with matmul_dtype={matmul_dtype!r} is not built (int8 Q.K^T is)")
+    if pv is not None:
+        raise NotImplementedError(f"the attention backward with pv_matmul_dtype={pv_matmul_dtype!r} is not built (P.V in the value dtype is)")
+    if query.ndim != 4 or key.ndim != 4 or value.ndim != 4:
+        raise ValueError("query / key / value must be [batch, heads, tokens, head_dim]")
+    d = query.shape[-1]
+    if key.shape[-1] != d or value.shape[-1] != d or d % 8 or not 8 <= d <= 128:
+        raise NotImplementedError("query, key and value must share a head_dim that is a multiple of 8 and at most 128")
+    if query.dtype not in (torch.bfloat16, torch.float16) or key.dtype != query.dtype or value.dtype != query.dtype:
+        raise NotImplementedError("query / key / value must share one of bfloat16 / float16")
+    if out_dtype is None:
+        out_dtype = query.dtype
+    sm_scale = d ** -0.5 if scale is None else scale
+    group = 0
+    if use_hadamard:
+        from .quant_utils import get_hadamard_group_size
+        dp = 64 if d <= 64 else 128
+        use_hadamard, group = get_hadamard_group_size(dp, min(hadamard_group_size, dp))
+        group = group if use_hadamard else 0
+    if not query.is_cuda or not key.is_cuda or not value.is_cuda or (attn_mask is not None and not attn_mask.is_cuda):
+        raise _lib.SdnqHipError("sdnq_amd attention needs CUDA/HIP tensors (no CPU fallback)")
+    if attn_mask is not None:
+        attn_mask = prepare_mask(attn_mask, query.shape[2], key.shape[2])
+    token_major = query.shape[1] > 1 and query.shape[2] > 1 and query.stride(2) > query.stride(1) and query.stride(-1) == 1
+    return SDNQAttenBackward.apply(query, key, value, attn_mask, bool(is_causal), float(sm_scale), bool(smooth_k), group, out_dtype, token_major)
