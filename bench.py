@@ -20,6 +20,11 @@ number measures the GPU, not the Python launch loop (the reference's own harness
                   oracle ("port_c_oracle") beside it; for the headline also BASELINE configs[0] (cfg1) on CPU and GPU
                   (rank 0, N=1 only)
 
+A plain run builds the layers, warms up, times the steps, writes --dump-outputs and prints the line: metric, value, unit,
+ms_per_step, dtype and the configuration.  Everything measured beside the headline -- roofline (with its per-shape table), the
+eager step figure, cpu_baseline, the column-sharded `tp` report of a multi-GPU run (or --tp-report), the gathers of a --tp run alone, the per-kernel
+and per-part figures of the attention / sdxl_unet_all workloads -- runs only with ``--full``, after the timed steps as before.
+
 N > 1: one rank per GPU.  The driver launches the ranks via torch.distributed.run; started plainly (`python bench.py --gpus N`, no
 WORLD_SIZE in the environment) this script re-executes itself under torch.distributed.run with N ranks, and exits non-zero when
 fewer than N GPUs are visible -- it never silently runs one.  Default = one independent latent per GPU (replicas, weak scaling,
@@ -67,9 +72,13 @@ def parse():
     p.add_argument("--tp-gather", choices=["rccl", "peer"], default="rccl",
                    help="with --tp: RCCL all-gather + re-assembly pass (default), or the copy-free gather -- every rank pushes its slab into every "
                         "rank's [M, N] output over peer-mapped memory (sdnq_amd.parallel.PeerArena, sdnq_hip_push_columns)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure everything beside the headline: roofline and its per-shape table, the eager step, "
+                        "cpu_baseline (unless --no-cpu-baseline), the `tp` report of a multi-GPU run, the gathers of a --tp run alone, the "
+                        "per-kernel / per-part figures of the attention and sdxl_unet_all workloads (off: the headline line only)")
     p.add_argument("--tp-report", action="store_true",
                    help="attach the column-sharded (strong-scaling) numbers of the same workload, RCCL and copy-free gather, to the default line; "
-                        "ON by default when --gpus > 1 without --tp (SDNQ_BENCH_TP_REPORT=0 turns it off)")
+                        "ON by default with --full when --gpus > 1 without --tp (SDNQ_BENCH_TP_REPORT=0 turns it off)")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     p.add_argument("--launch", choices=["graph", "eager", "compile", "capture"], default=None,
                    help="how a step is launched: one captured hipGraph (default), eager Python (= --no-graph), or torch.compile(mode='reduce-overhead') "
@@ -77,8 +86,8 @@ def parse():
     p.add_argument("--activation-pool", type=int, default=0,
                    help="sensitivity variant: distinct activations of one shape rotate through this many buffers (0 = one buffer per activation, "
                         "every read cold from HBM; a model's activations were just written by their producer)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-seconds", type=float, default=10.0)
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: time budget of cpu_baseline")
     p.add_argument("--fuse-projections", action="store_true",
                    help="variant: q/k/v (and cross-attention k/v) projections fused into one layer each, like diffusers' fuse_projections()")
     p.add_argument("--no-link-projections", action="store_true",
@@ -896,7 +905,7 @@ def attention_bench(args, device, distributed, world, rank):
                    "matmul_dtype": "int8", "pv_matmul_dtype": None, "ops_per_step": ops_per_step},
         "step_latency_ms": round(ms_per_step, 4),
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         # the forward kernel alone (operands prepared once), graph-replayed, HIP events on the launch stream
         prepared = {name: A.quantize_attn(*tensors[name]) for name in tensors}
 
@@ -926,6 +935,7 @@ def attention_bench(args, device, distributed, world, rank):
                 result["cpu_baseline"] = cpu_baseline_attention(calls, args.cpu_seconds)
             except Exception as e:  # noqa: BLE001
                 result["cpu_baseline_error"] = repr(e)
+    if rank == 0:
         print(json.dumps(result))
 
 
@@ -1004,7 +1014,7 @@ def unet_all_bench(args, device, distributed, world, rank):
                          "launch": "hipGraph replay", "activations": "bf16", "linked_projection_groups": linked, "ops_per_step": total_ops,
                          "ops_by_part": ops},
               "step_latency_ms": round(ms, 4)}
-    if rank == 0:
+    if rank == 0 and args.full:
         part_ms = {}
         for name, fn in parts.items():  # each part alone, graph-replayed, HIP events
             gr = capture(fn)
@@ -1017,6 +1027,7 @@ def unet_all_bench(args, device, distributed, world, rank):
             torch.cuda.synchronize()
             part_ms[name] = round(e0.elapsed_time(e1) / 5, 4)
         result["parts_ms"] = part_ms
+    if rank == 0:
         print(json.dumps(result))
 
 
@@ -1326,7 +1337,7 @@ def main():
     }
 
     gathers = None
-    if tp:
+    if tp and args.full:
         try:
             gathers = time_all_gathers(layers, device)  # a collective: every rank takes part
         except Exception as e:  # noqa: BLE001
@@ -1342,7 +1353,7 @@ def main():
                 "note": "bytes received per rank / time of the step's all-gathers run alone; a fully connected all-gather receives from "
                         "W - 1 peers over W - 1 links at once, each bound by 153 GB/s"})
 
-    want_tp_report = distributed and not tp and not is_conv and (args.tp_report or (world > 1 and os.environ.get("SDNQ_BENCH_TP_REPORT", "1") != "0"))
+    want_tp_report = distributed and not tp and not is_conv and (args.tp_report or (args.full and world > 1 and os.environ.get("SDNQ_BENCH_TP_REPORT", "1") != "0"))
 
     float_mode = not cfg_kwargs.get("use_quantized_matmul", cfg_kwargs.get("use_quantized_matmul_conv", False))
     if float_mode:
@@ -1350,7 +1361,7 @@ def main():
         result["config"]["workload"] = (f"{args.workload}: {len(layers)} quantized Linear layers of one denoising step, bs=1, the reference's DEFAULT mode "
                                         f"({sum(1 for l in layers if l[3] >= 32)} int8-weight x bf16-activation GEMMs, weights dequantized inside the kernel, "
                                         f"+ {sum(1 for l in layers if l[3] < 32)} M=1 layers)")
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             gk = time_float_kernel(layers, device) if float_mode else time_gemm_kernel(layers, mm_name, device)
         except Exception as e:  # noqa: BLE001

@@ -1,10 +1,13 @@
 """bench.py's launch contract, on CPU: `--gpus N` started without a launcher spawns N ranks itself (or refuses when fewer than N
 GPUs are visible -- never a silent 1-GPU run), and the multi-rank skeleton (rendezvous, barriers, MAX over ranks, ONE JSON line from
-rank 0 with n_gpus = N) works over gloo with world_size 2 (`--dry-run`: no device work, marked as not a measurement)."""
+rank 0 with n_gpus = N) works over gloo with world_size 2 (`--dry-run`: no device work, marked as not a measurement).  On the GPU:
+a plain run measures the headline alone, `--full` everything beside it."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -99,3 +102,27 @@ def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_elements
             assert np.array_equal(a, ref)
         else:
             assert a.ndim == 1 and a.size < ref.size and np.isin(a, ref.ravel()).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_full_adds_the_rest():
+    """A plain run times the steps and prints the headline; what is measured beside it (roofline, the eager step, cpu_baseline) comes
+    with --full only, on the same line (a small slice of the headline's layer list)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0.2"])):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--layers-scale", "0.05"] + extra,
+                           capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[mode] = json.loads(out[0])
+    for j in lines.values():
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert key in j, key
+        assert j["dtype"] == "i8" and j["unit"] == "GOP/s" and j["higher_is_better"] is True and j["value"] > 0 and j["steps"] == 3
+    assert lines["plain"]["metric"] == lines["full"]["metric"]
+    plain, full = lines["plain"], lines["full"]
+    assert not {"roofline", "roofline_error", "cpu_baseline", "cpu_baseline_error"} & set(plain) and "eager_ms_per_step" not in plain["config"]
+    assert "roofline" in full and full["roofline"]["launches_per_step"] > 0 and "eager_ms_per_step" in full["config"]
+    assert "cpu_baseline" in full and "cfg1" in full["cpu_baseline"]

@@ -12,12 +12,12 @@ for set in sdxl sdxl_fp8 sdxl_dequant linear flux flux_svd; do
   cp gpurun_out/${1:-r6/final}_pmc_$set/pmc_gemm_traffic.json $D/r06_pmc_gemm_traffic_$set.json
   [ $set = sdxl ] && cp gpurun_out/${1:-r6/final}_pmc_$set/pmc_rowquant_traffic.json $D/r06_pmc_rowquant_traffic_sdxl.json
 done
-timeout 900 python bench.py > $D/bench_sdxl_int8.json 2> $D/bench.err
+timeout 900 python bench.py --full > $D/bench_sdxl_int8.json 2> $D/bench.err
 tail -c 400 $D/bench_sdxl_int8.json
 bash tools/prof_bench.sh ${1:-r6/final}_prof --steps 20 --warmup 3 > $D/prof.log 2>&1
 cp gpurun_out/${1:-r6/final}_prof_window_kernels.csv gpurun_out/${1:-r6/final}_prof_window_summary.txt gpurun_out/${1:-r6/final}_prof_kernel_stats.csv gpurun_out/${1:-r6/final}_prof_bench.json $D/ 2>/dev/null
 for w in sdxl_fp8 sdxl_int8_dequant sdxl_int4 flux_int4_had flux_int8_svd sdxl_conv_int8 sdxl_attn_int8 linear_int8 sdxl_unet_all; do
-  timeout 900 python bench.py --workload $w --no-cpu-baseline > $D/bench_$w.json 2>> $D/bench.err
+  timeout 900 python bench.py --workload $w --full --no-cpu-baseline > $D/bench_$w.json 2>> $D/bench.err
   python - <<PY
 import json
 try:
