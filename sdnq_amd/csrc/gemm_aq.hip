@@ -16,9 +16,9 @@
 //   * the K loop then fills LDS with weight rows only (2/3 of the bytes per stage of the 64x128 tile), and nothing is exchanged
 //     between workgroups: no flags, no grid barrier, no deadlock to argue about.
 // Bit-identical to the two-launch route by construction (the same quant8, the same MFMA, the same epilogue expression) and by
-// tests/test_gemm_aq.py.
+// tests/test_gemm_aq.py; tests/test_gemm_aq_geometry.py runs the same cases on each tile geometry below.
 //
-// Quantization layout: wave w owns tile rows 8w .. 8w+7 in two passes of 4 rows; a row is read by a QUARTER wave (16 lanes x 16 bytes
+// Quantization layout (64 x 128 tile; the 32 x 256 tile: rows 4w .. 4w+3, one pass): wave w owns tile rows 8w .. 8w+7 in two passes of 4 rows; a row is read by a QUARTER wave (16 lanes x 16 bytes
 // = 128 elements per load instruction = one K stage), so the row amax is a reduction inside one 16-lane DPP row (four DPP exchanges,
 // no LDS) and lane l's j-th chunk (8 elements) IS bytes 8 (l & 15) .. +8 of stage j's row: one ds_write_b64.
 #include <atomic>
@@ -32,8 +32,11 @@ int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr
 
 namespace {
 
-constexpr int BM = 64, BN = 128, BK = 128, NW = 8, NT = NW * 64;
-constexpr int A_STAGE = BM * BK, B_STAGE = BN * BK;
+// Tile geometries (template parameters BM x BN of the kernel; BK, the wave count and the 32x32 accumulator per wave are common):
+//   64 x 128, 4 ring slots : waves 2 x 4; a wave quantizes 8 rows in two passes; 16-KB weight stages; tiles_n workgroups repeat a row block
+//   32 x 256, 3 ring slots : waves 1 x 8; a wave quantizes 4 rows in one pass (half the ingest and the arithmetic in front of the K loop,
+//                            half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280
+constexpr int BK = 128, NW = 8, NT = NW * 64;
 
 struct AqParams {
     const float* sb;      // [N] weight row scales
@@ -91,19 +94,24 @@ template <int N> __device__ __forceinline__ void aq_wait_vmcnt() { asm volatile(
         if (p.trace != nullptr && threadIdx.x == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
     } while (0)
 
-// X_T: activation dtype (bf16 / f16) = output dtype; NJ: K stages held (K <= 128 NJ); NSB: weight ring depth
-template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB>
+// X_T: activation dtype (bf16 / f16) = output dtype; NJ: K stages held (K <= 128 NJ); NSB: weight ring depth; BM x BN: tile geometry
+template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN>
 __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, int ldx, int ldb, int M, int N,
                                                        int K, int tiles_m, int tiles_n, int group_m, AqParams p_) {
     SDNQ_KERNARGS_NOW("s"(x), "s"(w), "s"(ldx), "s"(ldb), "s"(M), "s"(N), "s"(K), "s"(tiles_m), "s"(tiles_n), "s"(group_m));
     const AqParams& p = p_;
     typedef AqMma<MM> MT;
+    static_assert(BM % 32 == 0 && BN % 32 == 0 && (BM / 32) * (BN / 32) == NW, "one 32x32 accumulator per wave");
+    constexpr int A_STAGE = BM * BK, B_STAGE = BN * BK;
+    constexpr int PS = BM / (4 * NW);   // quantization passes of a wave: 4 rows (one per quarter wave) each
+    constexpr int PPW = BN / (8 * NW);  // 1-KB ring pieces (8 weight rows) of a stage that one wave moves
+    static_assert(PS >= 1 && PS <= 2 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
-    uint8_t* const ldsA = lds;                       // [NJ][64 rows][128 B] quantized activation rows, resident
-    uint8_t* const ldsB = lds + NJ * A_STAGE;        // [NSB][128 rows][128 B] weight ring
+    uint8_t* const ldsA = lds;                       // [NJ][BM rows][128 B] quantized activation rows, resident
+    uint8_t* const ldsB = lds + NJ * A_STAGE;        // [NSB][BN rows][128 B] weight ring
     float* const s_sb = (float*)(ldsB + NSB * B_STAGE);
     float* const s_bias = s_sb + BN;
-    float* const s_xs = s_bias + BN;                 // [64] activation row scales
+    float* const s_xs = s_bias + BN;                 // [BM] activation row scales
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -147,22 +155,22 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 
     // ---- activation rows: every load of the wave's 8 rows in flight before anything else ---------------------------------------------
     const auto rsX = SDNQ_MAKE_RSRC_N((const uint8_t*)x + (int64_t)m0 * ldx * 2, ((int64_t)(m_rows - 1) * ldx + K) * 2);
-    v4i xr[2][NJ];
-    int qrow[2];
+    v4i xr[PS][NJ];
+    int qrow[PS];
 #pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-        qrow[ps] = wave * 8 + ps * 4 + (lane >> 4);
+    for (int ps = 0; ps < PS; ++ps) {
+        qrow[ps] = wave * (4 * PS) + ps * 4 + (lane >> 4);
         const int rc = qrow[ps] < m_rows ? qrow[ps] : m_rows - 1;  // rows past M: computed on valid memory, never stored
         const int vo = rc * ldx * 2 + (lane & 15) * 16;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) xr[ps][j] = SDNQ_BUF_LOAD16(rsX, vo, j < nk ? j * 256 : 0x40000000);  // stages past K: out of range = zeros
     }
     // ---- weight ring prologue: piece = 8 rows x 128 B, lane l -> row l / 8, physical chunk l % 8 (source chunk = swizzle-inverse);
-    // wave w owns pieces w and w + 8 of every stage; constant per-lane offsets, the K advance in the scalar operand
+    // wave w owns pieces w, w + 8, ... (PPW of them) of every stage; constant per-lane offsets, the K advance in the scalar operand
     const auto rsB = SDNQ_MAKE_RSRC_N(w + (int64_t)n0 * ldb, (int64_t)(n_lim - 1) * ldb + K);
-    int voB[2];
+    int voB[PPW];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < PPW; ++u) {
         const int r = (wave + u * NW) * 8 + (lane >> 3);
         const int rc = r < n_lim ? r : n_lim - 1;
         voB[u] = rc * ldb + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
@@ -170,7 +178,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     auto issueB = [&](int st, int slot) {  // stages past the end re-fetch stage 0 (never consumed; keeps the counted vmcnt a constant)
         const int s = st < nk ? st : 0;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) SDNQ_DMA16(rsB, ldsB + slot * B_STAGE + (wave + u * NW) * 1024, voB[u], s * BK);
+        for (int u = 0; u < PPW; ++u) SDNQ_DMA16(rsB, ldsB + slot * B_STAGE + (wave + u * NW) * 1024, voB[u], s * BK);
     };
     constexpr int AHEAD = NSB - 1;
 #pragma unroll
@@ -194,10 +202,10 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // ---- row quantization: amax inside the 16-lane row group, IEEE scale, lean codes -> the resident LDS image -------------------------
     constexpr float QMAX = (MM == SDNQ_MM_I8) ? 127.0f : 448.0f;
 #pragma unroll
-    for (int ps = 0; ps < 2; ++ps) {
-        // loads return in order: pass 0 has landed when at most the NJ loads of pass 1 and this wave's 2 AHEAD ring pieces are outstanding
-        if (ps == 0) aq_wait_vmcnt<NJ + 2 * AHEAD>();
-        else aq_wait_vmcnt<2 * AHEAD>();
+    for (int ps = 0; ps < PS; ++ps) {
+        // loads return in order: a pass has landed when at most the NJ loads of each later pass and this wave's PPW AHEAD ring pieces are outstanding
+        if (ps == 0) aq_wait_vmcnt<(PS - 1) * NJ + PPW * AHEAD>();
+        else aq_wait_vmcnt<PPW * AHEAD>();
         // |x| of 16-bit floats orders like the unsigned integer of its low 15 bits: packed integer max, two elements per instruction
         us2 mx = {0, 0};
 #pragma unroll
@@ -211,7 +219,27 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
             const u32 o = (u32)lane_xor_i32((int)m32, s);
             m32 = __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(us2, m32), __builtin_bit_cast(us2, o)));
         }
-        const u32 mb = (m32 & 0xffffu) > (m32 >> 16) ? (m32 & 0xffffu) : (m32 >> 16);
+        u32 mb = (m32 & 0xffffu) > (m32 >> 16) ? (m32 & 0xffffu) : (m32 >> 16);
+        // a NaN orders above everything here, but the row quantizer's fmaxf drops it (rowquant.hip): a row that holds one takes its amax
+        // over the other elements, as there.  Off the ordinary path: one compare per pass, the second sweep only for such a row's wave.
+        constexpr u32 INF_BITS = X_T == SDNQ_BF16 ? 0x7f80u : 0x7c00u;
+        if (__builtin_amdgcn_ballot_w64(mb > INF_BITS) != 0) {
+            u32 mn = 0;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    const u32 lo = (u32)xr[ps][j][d] & 0x7fffu, hi = ((u32)xr[ps][j][d] >> 16) & 0x7fffu;
+                    mn = lo > INF_BITS ? mn : (lo > mn ? lo : mn);
+                    mn = hi > INF_BITS ? mn : (hi > mn ? hi : mn);
+                }
+#pragma unroll
+            for (int s = 1; s <= 8; s <<= 1) {
+                const u32 o = (u32)lane_xor_i32((int)mn, s);
+                mn = o > mn ? o : mn;
+            }
+            mb = mn;
+        }
         const float amax = X_T == SDNQ_BF16 ? __uint_as_float(mb << 16) : f16_bits_to_f32((uint16_t)mb);
         const float scale = amax / QMAX;  // get_scale_symmetric, quant_utils.py:23-24
         RowDiv rd;
@@ -257,7 +285,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     typename MT::acc_t acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0;
-    const int wm = wave >> 2, wn = wave & 3;
+    const int wm = wave / (BN / 32), wn = wave % (BN / 32);
     const int frow = lane & 31, fgrp = lane >> 5;
     constexpr int KS = BK / MT::KB;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's codes and scales are in LDS before the first barrier lets anyone read them
@@ -271,7 +299,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
         fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
     };
-    aq_wait_vmcnt<(AHEAD - 1) * 2>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
+    aq_wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     issueB(AHEAD, AHEAD);              // the ring's last free slot
@@ -284,7 +312,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #endif
     auto half = [&](auto setc, int kt) {
         constexpr int sx = decltype(setc)::value;
-        aq_wait_vmcnt<(NSB - 2) * 2>();                      // this wave's pieces of stage kt + 1 have landed
+        aq_wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads of stage kt have retired: the slot may be refilled
         __builtin_amdgcn_sched_barrier(0);
         if (!(lab & 8)) __builtin_amdgcn_s_barrier();
@@ -366,12 +394,38 @@ inline int aq_cu_count() {  // of the CURRENT device (a process may drive differ
 }
 
 std::atomic<unsigned long long*> g_aq_trace{nullptr};
+std::atomic<int> g_aq_geometry{-1};  // tests / labs: -1 by shape, 0 = 64 x 128, 1 = 32 x 256
 
-template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB>
-int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, int64_t k, AqParams p, hipStream_t s) {
-    constexpr int LDS_BYTES = NJ * A_STAGE + NSB * B_STAGE + (2 * BN + BM) * 4;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    auto kern = linear_aq_kernel<X_T, MM, HAS_BIAS, NJ, NSB>;
+// The launcher's choices for one problem, in one place (tests/test_gemm_aq_plan.py holds the table this implements).
+//   geometry 1 (32 x 256, 3 ring slots) where the front of the 64 x 128 tile -- ingest + quantization of 64 rows x K, repeated by every
+//   column tile -- outweighs its K loop: int8, K of more than 5 stages, N a multiple of 256 (no column tile half empty), and one round:
+//   at most one tile per CU.  Everything else keeps geometry 0 (64 x 128, 4 ring slots).
+struct AqPlan { int geometry, bm, bn, tiles_m, tiles_n, group_m; int64_t prefetch_room; };
+inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
+    static const int geo_env = (int)aq_env("SDNQ_HIP_FUSED_ROWQUANT_GEOMETRY", -1);  // tuning aid
+    static const int gm_env = (int)aq_env("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);     // tuning aid (1 = n fastest)
+    int geo = g_aq_geometry.load(std::memory_order_relaxed);
+    if (geo < 0) geo = geo_env;
+    if (geo < 0) geo = (mm_dtype == SDNQ_MM_I8 && k > 640 && (n % 256) == 0 && ((m + 31) / 32) * (n / 256) <= cus) ? 1 : 0;
+    AqPlan pl;
+    pl.geometry = geo ? 1 : 0;
+    pl.bm = geo ? 32 : 64;
+    pl.bn = geo ? 256 : 128;
+    pl.tiles_m = (int)((m + pl.bm - 1) / pl.bm);
+    pl.tiles_n = (int)((n + pl.bn - 1) / pl.bn);
+    // the walk groups 8 row blocks in either geometry.  32 x 256 at 1024 x 1280 x 1280: a group is 40 tiles = the 20 of two XCDs, each
+    // 8 row blocks x 2.5 weight blocks; in the step 8 blocks ran 7.02 ms, 16 (the same ROWS as 8 of 64) 7.08, 2 / 4 / 6 7.04
+    const int gm = gm_env < 1 ? 1 : gm_env;
+    pl.group_m = gm > pl.tiles_m ? pl.tiles_m : gm;
+    pl.prefetch_room = (int64_t)cus - (int64_t)pl.tiles_m * pl.tiles_n;  // one workgroup per CU in either geometry (LDS)
+    return pl;
+}
+
+template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN>
+int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, int64_t k, const AqPlan& pl, AqParams p, hipStream_t s) {
+    constexpr int LDS_BYTES = NJ * BM * BK + NSB * BN * BK + (2 * BN + BM) * 4;
+    static_assert(LDS_BYTES <= 160 * 1024 && 2 * LDS_BYTES > 160 * 1024, "LDS budget: one workgroup per CU (aq_plan's prefetch room)");
+    auto kern = linear_aq_kernel<X_T, MM, HAS_BIAS, NJ, NSB, BM, BN>;
     // (the attribute belongs to the function ON ONE DEVICE: a process that drives several GPUs sets it once per device, not once)
     static std::atomic<uint64_t> attr_devices{0};
     if (LDS_BYTES > 64 * 1024) {
@@ -383,16 +437,14 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
             attr_devices.fetch_or(bit, std::memory_order_release);
         }
     }
-    const int tiles_m = (int)((m + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
+    if (pl.bm != BM || pl.bn != BN) return SDNQ_ERR_LAUNCH;
+    const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, group_m = pl.group_m;
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
-    constexpr int WG_PER_CU = (160 * 1024) / LDS_BYTES;
     p.trace = g_aq_trace.load(std::memory_order_relaxed);
 #ifdef SDNQ_AQ_LAB
     { const char* e = getenv("SDNQ_HIP_AQ_LAB"); p.lab = e ? atoi(e) : 0; }
 #endif
-    static const int gm_env = (int)aq_env("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);  // tuning aid (1 = n fastest)
-    const int group_m = gm_env < 1 ? 1 : (gm_env > tiles_m ? tiles_m : gm_env);
-    const int pf_wgs = sdnq_internal_take_prefetch((int64_t)WG_PER_CU * aq_cu_count() - tiles, NT, p.pf_ptr, p.pf_lines);
+    const int pf_wgs = sdnq_internal_take_prefetch(pl.prefetch_room, NT, p.pf_ptr, p.pf_lines);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles + pf_wgs)), dim3(NT), LDS_BYTES, s, (const uint16_t*)x, (const uint8_t*)w, (int)ldx, (int)k, (int)m,
                        (int)n, (int)k, tiles_m, tiles_n, group_m, p);
     SDNQ_CHECK_LAUNCH();
@@ -412,7 +464,7 @@ extern "C" int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, i
     if (mm_dtype != SDNQ_MM_I8 && !(mm_dtype == SDNQ_MM_FP8 && fp8_on)) return 0;
     if ((x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) || out_dtype != x_dtype) return 0;
     if (m < min_m || n <= 0 || (n % 8) != 0 || k <= 0 || (k % 128) != 0 || k > 1280) return 0;
-    const int64_t tiles_m = (m + BM - 1) / BM, tiles_n = (n + BN - 1) / BN;
+    const int64_t tiles_m = (m + 63) / 64, tiles_n = (n + 127) / 128;  // (counted on the 64 x 128 tile, whichever geometry runs)
     if (tiles_n > max_tn || k < min_k || k > max_k) return 0;
     if (tiles_m * tiles_n > (int64_t)aq_cu_count()) return 0;  // one round, one workgroup per CU
     return 1;
@@ -432,15 +484,28 @@ extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dty
     AqParams p{};
     p.sb = sb; p.bias = bias; p.out = out; p.ldc = n; p.bias_dtype = bias_dtype;
     hipStream_t s = (hipStream_t)stream;
-#define AQ_NJ(XT, MMV, HB) (k <= 640 ? launch_aq<XT, MMV, HB, 5, 4>(x, b, ldx, m, n, k, p, s) : launch_aq<XT, MMV, HB, 10, 4>(x, b, ldx, m, n, k, p, s))
+    const AqPlan pl = aq_plan(mm_dtype, m, n, k, aq_cu_count());
+#define AQ_G(XT, MMV, HB, NJV) (pl.geometry ? launch_aq<XT, MMV, HB, NJV, 3, 32, 256>(x, b, ldx, m, n, k, pl, p, s) : launch_aq<XT, MMV, HB, NJV, 4, 64, 128>(x, b, ldx, m, n, k, pl, p, s))
+#define AQ_NJ(XT, MMV, HB) (k <= 640 ? AQ_G(XT, MMV, HB, 5) : AQ_G(XT, MMV, HB, 10))
 #define AQ_B(XT, MMV) (bias ? AQ_NJ(XT, MMV, true) : AQ_NJ(XT, MMV, false))
 #define AQ_X(MMV) (x_dtype == SDNQ_BF16 ? AQ_B(SDNQ_BF16, MMV) : AQ_B(SDNQ_F16, MMV))
     return mm_dtype == SDNQ_MM_I8 ? AQ_X(SDNQ_MM_I8) : AQ_X(SDNQ_MM_FP8);
 #undef AQ_X
 #undef AQ_B
 #undef AQ_NJ
+#undef AQ_G
 }
 
 // lab: phase stamps of the one-launch Linear (device buffer of 1024 x 8 uint64, or null to stop).  A C++ symbol internal to the library
 // (tools/aq_lab.py binds its mangled name), not part of the C ABI of include/sdnq_hip.h
 void sdnq_internal_aq_trace(unsigned long long* device_buf) { g_aq_trace.store(device_buf, std::memory_order_relaxed); }
+
+// tests / labs: force the tile geometry of the one-launch Linear (-1 by shape, 0 = 64 x 128, 1 = 32 x 256); internal like the trace hook
+void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry ? 1 : 0), std::memory_order_relaxed); }
+
+// tests: what the launcher would choose for (mm_dtype, m, n, k) on a part with `cus` CUs:
+// out = {geometry, BM, BN, tiles_m, tiles_n, group_m, prefetch room}
+void sdnq_internal_aq_plan(int mm_dtype, long long m, long long n, long long k, int cus, long long* out) {
+    const AqPlan pl = aq_plan(mm_dtype, m, n, k, cus);
+    out[0] = pl.geometry; out[1] = pl.bm; out[2] = pl.bn; out[3] = pl.tiles_m; out[4] = pl.tiles_n; out[5] = pl.group_m; out[6] = pl.prefetch_room;
+}
