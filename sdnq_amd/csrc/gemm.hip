@@ -24,19 +24,10 @@
 //     (linear_int8.py:57-62) and zero-point term f32(rowsum[m]) * sa[m] * zp[n] (linear_int8.py:65-69)
 //     are produced in the epilogue instead of materialising an [M][N] bias in HBM;
 //   * block -> tile map is XCD-aware: the 8 XCDs (private L2s) each walk a contiguous range of tiles.
-#include <atomic>
 #include <vector>
 #include <cstdio>
-#include <cstdlib>
-#include <type_traits>
 
-#include "sdnq_dev.h"
-
-// gemm_ks.hip: the 64 x 80 tile with an in-workgroup K split (8 waves, partial sums reduced through LDS) -- tile id 28
-bool sdnq_internal_ks_eligible(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb);
-bool sdnq_internal_ks_preferred(int64_t m, int64_t n, int64_t k);
-int sdnq_internal_scaled_mm_ks(const void* a, const void* b, const float* sa, const float* sb, const void* bias, int bias_dtype, void* out,
-                               int out_dtype, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc, hipStream_t s);
+#include "gemm_dev.h"
 
 namespace {
 
@@ -242,17 +233,6 @@ template <int N, typename F> __device__ __forceinline__ void static_for_down(F&&
         f(std::integral_constant<int, N - 1>{});
         static_for_down<N - 1>(f);
     }
-}
-
-template <int N, int I = 0, typename F> __device__ __forceinline__ void static_for_up(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_up<N, I + 1>(f);
-    }
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // EPI_LRFAST: EPI_LOWRANK restricted (by the launcher) to what the register-layout low-rank epilogue handles -- rank-32 16-bit factors,
@@ -525,36 +505,16 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-    // L2-aware tile order. (1) block b runs on XCD b % 8 (private 4 MiB L2 each): give every XCD a CONTIGUOUS range of
-    // the tile sequence. (2) the sequence itself is grouped: GROUP_M m-strips are walked together, m fastest, so the
-    // ~32 workgroups resident on one XCD at a time cover a near-square GROUP_M x (32/GROUP_M) patch of tiles and
-    // share both their A strips and their B slabs in that L2 (a 1 x 32 row of tiles would re-fetch every B slab from
-    // MALL/HBM for each m-strip: measured 51% of wave cycles parked on vmcnt/barrier at 16384 x 8192 x 4096).
+    // L2-aware tile order (gemm_dev.h): every XCD walks a contiguous range of the tile sequence, and the sequence is grouped
     const int nwg = hk.tiles_m * hk.tiles_n;
-    int bid = blockIdx.x;
-    if (bid >= nwg) {
-        // a prefetch workgroup (launch_one appends them when the launch leaves workgroup slots free): one dword of every 128-byte line of
-        // the NEXT layers' weights, nothing kept -- they are in the Infinity Cache when their own GEMM asks for them
-        const int t = (bid - nwg) * (int)blockDim.x + (int)threadIdx.x, stride = ((int)gridDim.x - nwg) * (int)blockDim.x;
-#pragma nounroll
-        for (int r = 0; r < 4; ++r) {
-            const uint8_t* base = p.pf_ptr[r];
-            const int lines = p.pf_lines[r];
-            for (int i = t; i < lines; i += stride) {
-                int v;
-                asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(base + (int64_t)i * 128) : "memory");
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if ((int)blockIdx.x >= nwg) {  // a prefetch workgroup (launch_one appends them when the launch leaves workgroup slots free)
+        SDNQ_PREFETCH_LINES((int)threadIdx.x, (int)blockIdx.x - nwg, (int)blockDim.x, (int)gridDim.x - nwg, p);
 #ifdef SDNQ_TRACE
         if (threadIdx.x == 0 && blockIdx.x < 4096) g_trace[blockIdx.x * 8] = 0;  // (not a tile: tools/trace_*.py count rows with an entry stamp)
 #endif
         return;
     }
-    {
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
+    const int bid = xcd_contiguous(blockIdx.x, nwg);
     int tile_m, tile_n;
     // (operands are wave-uniform; __umulhi is selected as a VECTOR multiply, so the quotient is pinned back to a scalar register --
     // left in a VGPR, a tile coordinate / unit index turned the unit-table load into vector loads and every buffer descriptor derived
@@ -569,7 +529,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
         if (tail) tile_n = (int)fdiv((uint32_t)in_g, p.mg_tail);  // (a branch, not a select: only the last group waits for the struct)
         else tile_n = (int)fdiv((uint32_t)in_g, hk.mg_group_m);
         tile_m = first_m + in_g - tile_n * gsz;
-    } else {
+    } else {  // (grouped_tile of gemm_dev.h, kept in this spelling: the helper's `first_m + in_g - tile_n * gsz` orders the scalar code differently)
         const int per_group = hk.group_m * hk.tiles_n;
         const int gid = bid / per_group, first_m = gid * hk.group_m;
         const int gsz = (hk.tiles_m - first_m) < hk.group_m ? (hk.tiles_m - first_m) : hk.group_m;
@@ -1889,17 +1849,6 @@ inline bool pf_hint_pending() {
     if (g_pf_hint.device != current_device()) { g_pf_hint = PrefetchHint{}; return false; }
     return true;
 }
-inline int cu_count() {  // of the CURRENT device (a process may drive different parts / partitions)
-    static std::atomic<int> cus[64];
-    const int dev = current_device();
-    if (dev < 0 || dev >= 64) return 256;
-    int v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
 
 // sdnq_hip_scaled_mm_tile: a dry run of the tile heuristics -- the launcher that WOULD run records its tile here and returns
 struct TileProbe { int bm, bn, threads; };
@@ -1918,33 +1867,24 @@ int launch_one(GemmParams p, hipStream_t s) {
     constexpr int LDS_BYTES = (MAIN > EPIB ? MAIN : EPIB) + ((is_lr<EPI> || is_w8a16<MM>) ? 4 : 2) * BN * 4;  // ring | staging, then the per-channel vectors
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     auto kern = gemm_kernel<MM, OUT_T, EPI, BM, BN, WM, WN, NS, LD, BK, LP>;
-    // (the attribute belongs to the function ON ONE DEVICE: a process that drives several GPUs sets it once per device, not once)
     static std::atomic<uint64_t> attr_devices{0};
-    if (LDS_BYTES > 64 * 1024) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return SDNQ_ERR_LAUNCH;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return SDNQ_ERR_LAUNCH;
-            attr_devices.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    if (LDS_BYTES > 64 * 1024 && !allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
     if (p.lda == 0) p.lda = p.K;
     if (p.ldb == 0) p.ldb = is_w8a16<MM> ? p.K / 2 : p.K;
     if (p.ldc == 0) p.ldc = p.N;
     p.tiles_m = (int)((p.M + BM - 1) / BM);
     p.tiles_n = (int)((p.N + BN - 1) / BN);
     {
-        static const int gm_env = [] { const char* e = getenv("SDNQ_HIP_GROUP_M"); return e ? atoi(e) : 0; }();  // tuning aid
+        static const int gm_env = (int)env_int("SDNQ_HIP_GROUP_M", 0);  // tuning aid
         // near-square patch of ~32 concurrent tiles per XCD: rows*BM ~ cols*BN
         int gm = gm_env > 0 ? gm_env : (BM >= BN ? 6 : 8);
         if (gm > p.tiles_m) gm = p.tiles_m;
         if (gm > 255) gm = 255;  // travels in 8 bits of hk_flags
         p.group_m = gm;
-        static const int swz_env = [] { const char* e = getenv("SDNQ_HIP_SWZ"); return e ? atoi(e) : 7; }();
+        static const int swz_env = (int)env_int("SDNQ_HIP_SWZ", 7);
         p.swz = swz_env;
         auto magic = [](uint64_t d) -> uint32_t { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + d - 1) / d); };
-        static const bool fast_env = [] { const char* e = getenv("SDNQ_HIP_FASTMAP"); return !e || atoi(e) != 0; }();  // A/B aid
+        static const bool fast_env = env_int("SDNQ_HIP_FASTMAP", 1) != 0;  // A/B aid
         const uint64_t nwg = (uint64_t)p.tiles_m * (uint64_t)p.tiles_n, per_group = (uint64_t)gm * (uint64_t)p.tiles_n;
         const uint64_t tail = (uint64_t)(p.tiles_m % gm);
         p.fastmap = fast_env && nwg * (per_group > (uint64_t)gm ? per_group : (uint64_t)gm) <= (1ull << 32);
@@ -1982,7 +1922,7 @@ int launch_one(GemmParams p, hipStream_t s) {
             p.pf_ptr[r] = (const uint8_t*)a0; p.pf_lines[r] = (int)n;
             lines += n;
         }
-        static const int pf_max = [] { const char* e = getenv("SDNQ_HIP_PREFETCH_WGS"); return e ? atoi(e) : 96; }();  // tuning aid
+        static const int pf_max = (int)env_int("SDNQ_HIP_PREFETCH_WGS", 96);  // tuning aid
         int64_t want = (lines + NW * 64 * 4 - 1) / (NW * 64 * 4);  // ~4 lines per thread
         if (want > pf_max) want = pf_max;
         pf_wgs = (int)(want < room ? want : room);
@@ -2002,8 +1942,7 @@ std::atomic<int> g_forced_tile{-2};
 inline int forced_tile() {
     int f = g_forced_tile.load(std::memory_order_relaxed);
     if (f == -2) {
-        const char* e = getenv("SDNQ_HIP_TILE");
-        f = e ? atoi(e) : -1;
+        f = (int)env_int("SDNQ_HIP_TILE", -1);
         g_forced_tile.store(f, std::memory_order_relaxed);
     }
     return f;
@@ -2143,7 +2082,7 @@ int launch_tiles(const GemmParams& p, hipStream_t s) {
     //    (round 4, judged on the conv step: with 150..229 such tiles -- the N = 320 convs, 192 tiles on 256 CUs -- the chip is a quarter idle
     //     and 64x128 tiles win: 16384 x 320 x 2880 -0.08 ms over its 7 launches, x 640 / x 5760 / x 8640 -0.01..-0.03 each;
     //     profiles/r04_conv_tiles_in_step.txt.  From 230 tiles on -- 4096 x 1920: 240, 4096 x 5120: 640 -- the tall tile stays.)
-    static const int tall_min = [] { const char* e = getenv("SDNQ_HIP_TALL_MIN_TILES"); return e ? atoi(e) : 230; }();  // tuning aid
+    static const int tall_min = (int)env_int("SDNQ_HIP_TALL_MIN_TILES", 230);  // tuning aid
     if (p.M >= 2048 && tiles(256, 128) >= tall_min && fits(128)) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_PIPE, 64>(p, s);
     if constexpr (PP_OK<MM, OUT_T, EPI>) {
         //  * a few hundred rows against a wide N and a long K (the text stream of FLUX: 512 x 9216 / 12288 x 3072): ONE round of 256x128
@@ -2237,7 +2176,7 @@ int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr
         pf_ptr[r] = (const uint8_t*)a0; pf_lines[r] = (int)n;
         lines += n;
     }
-    static const int pf_max = [] { const char* e = getenv("SDNQ_HIP_PREFETCH_WGS"); return e ? atoi(e) : 96; }();
+    static const int pf_max = (int)env_int("SDNQ_HIP_PREFETCH_WGS", 96);
     int64_t want = (lines + (int64_t)threads * 4 - 1) / ((int64_t)threads * 4);
     if (want > pf_max) want = pf_max;
     g_pf_hint = PrefetchHint{};
@@ -2422,7 +2361,7 @@ int launch_tiles_w8(const GemmParams& p, hipStream_t s) {
     if (force == 3 || (force < 0 && p.M <= 64) || !fit128) return launch_one<MM, OUT_T, EPI, 64, 64, 64, 32, 4, LD_DMA, 128>(p, s);
     // (round 3 re-sweep on the buffer-load loaders, profiles/r03_w8a16_sweep.txt: 160-240 tiles of 128x128 lose to 64x128 -- 4096 x 640 x 640
     //  12.7 vs 11.4 us, 1024 x 3840 x 1280 20.2 vs 19.2 -- from 480 tiles up they win: 4096 x 1920 x 640 17.2 vs 21.0)
-    static const int t128_min = [] { const char* e = getenv("SDNQ_HIP_W8_T128_MIN"); return e ? atoi(e) : 320; }();  // tuning aid
+    static const int t128_min = (int)env_int("SDNQ_HIP_W8_T128_MIN", 320);  // tuning aid
     // (judged on the STEP, tools/tune_tiles_in_step.py + profiles/r03_tiles_in_step_dequant.txt: the GEGLU projection 1024 x 10240 x 1280 --
     //  640 tiles of 128x128 -- is 0.32 ms per step faster on 64x128 tiles, 12.75 against 13.07 ms; the 4096-row problems are indifferent:
     //  128-row wave tiles only for M >= 2048)

@@ -21,14 +21,8 @@
 // Quantization layout (64 x 128 tile; the 32 x 256 tile: rows 4w .. 4w+3, one pass): wave w owns tile rows 8w .. 8w+7 in two passes of 4 rows; a row is read by a QUARTER wave (16 lanes x 16 bytes
 // = 128 elements per load instruction = one K stage), so the row amax is a reduction inside one 16-lane DPP row (four DPP exchanges,
 // no LDS) and lane l's j-th chunk (8 elements) IS bytes 8 (l & 15) .. +8 of stage j's row: one ds_write_b64.
-#include <atomic>
-#include <cstdlib>
-#include <type_traits>
-
+#include "gemm_dev.h"
 #include "quant8_dev.h"
-#include "sdnq_dev.h"
-
-int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr[4], int pf_lines[4]);  // gemm.hip
 
 namespace {
 
@@ -81,19 +75,6 @@ template <> struct AqMma<SDNQ_MM_FP8> {
     static __device__ __forceinline__ float tof(const acc_t& c, int i) { return c[i]; }
 };
 
-template <int N, int I = 0, typename F> __device__ __forceinline__ void aq_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        aq_static_for<N, I + 1>(f);
-    }
-}
-template <int N> __device__ __forceinline__ void aq_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-#define AQ_TRACE(slot)                                                                                                   \
-    do {                                                                                                                 \
-        if (p.trace != nullptr && threadIdx.x == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-
 // X_T: activation dtype (bf16 / f16) = output dtype; NJ: K stages held (K <= 128 NJ); NSB: weight ring depth; BM x BN: tile geometry
 template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN>
 __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, int ldx, int ldb, int M, int N,
@@ -116,39 +97,14 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    if (bid >= nwg) {  // hosted weight prefetch: one dword of every 128-byte line of the next layers' weights (gemm.hip, launch_one)
-        const int t = (bid - nwg) * NT + tid, stride = ((int)gridDim.x - nwg) * NT;
-#pragma nounroll
-        for (int r = 0; r < 4; ++r) {
-            const uint8_t* base = p.pf_ptr[r];
-            const int lines = p.pf_lines[r];
-            for (int i = t; i < lines; i += stride) {
-                int v;
-                asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(base + (int64_t)i * 128) : "memory");
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int bid = blockIdx.x;
+    if (bid >= nwg) {  // hosted weight prefetch
+        SDNQ_PREFETCH_LINES(tid, bid - nwg, NT, (int)gridDim.x - nwg, p);
         return;
     }
     const unsigned long long t_entry = __builtin_amdgcn_s_memtime();  // (stored with stamp 1: nothing waits for the trace pointer before the loads go out)
-    {   // block b runs on XCD b % 8 (private L2 each): give every XCD a contiguous range of the tile sequence
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    // ... and walk the sequence in groups of `group_m` row blocks, m fastest (gemm.hip's order): the ~20 tiles an XCD holds then share few
-    // weight blocks (the operand the K loop streams: its DMAs mostly hit in L2) and read more distinct activation rows, all of them
-    // requested at once up front.  n fastest -- every column tile of two row blocks per XCD -- ran the K loop at 850 cycles per stage
-    // against 730 for the two-operand loop of gemm.hip: half of its weight pieces missed L2.
     int tile_m, tile_n;
-    {
-        const int per_group = group_m * tiles_n;
-        const int gid = bid / per_group, first_m = gid * group_m;
-        const int gsz = (tiles_m - first_m) < group_m ? (tiles_m - first_m) : group_m;
-        const int in_g = bid - gid * per_group;
-        tile_n = in_g / gsz;
-        tile_m = first_m + in_g - tile_n * gsz;
-    }
+    grouped_tile(xcd_contiguous(bid, nwg), tiles_m, tiles_n, group_m, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nk = K / BK;  // (launcher: K % 128 == 0, K <= 128 NJ)
     const int m_rows = (M - m0) < BM ? (M - m0) : BM, n_lim = (N - n0) < BN ? (N - n0) : BN;
@@ -186,7 +142,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     __builtin_amdgcn_sched_barrier(0);
     SDNQ_KERNARGS_NOW("s"(p_.sb), "s"(p_.bias), "s"(p_.out), "s"(p_.ldc), "s"(p_.bias_dtype), "s"(p_.trace));
     if (p.trace != nullptr && tid == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8] = t_entry;
-    AQ_TRACE(1);
+    SDNQ_PHASE_STAMP(p.trace, 1);
     // per-channel epilogue vectors: requested now (behind the rows and the ring prologue), parked in LDS after the quantization
     float ev_sb = 0.0f;
     u32 ev_bias = 0;  // raw bits: converted when parked (a conversion here would wait for every load in flight)
@@ -204,8 +160,8 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps) {
         // loads return in order: a pass has landed when at most the NJ loads of each later pass and this wave's PPW AHEAD ring pieces are outstanding
-        if (ps == 0) aq_wait_vmcnt<(PS - 1) * NJ + PPW * AHEAD>();
-        else aq_wait_vmcnt<PPW * AHEAD>();
+        if (ps == 0) wait_vmcnt<(PS - 1) * NJ + PPW * AHEAD>();
+        else wait_vmcnt<PPW * AHEAD>();
         // |x| of 16-bit floats orders like the unsigned integer of its low 15 bits: packed integer max, two elements per instruction
         us2 mx = {0, 0};
 #pragma unroll
@@ -279,7 +235,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         if constexpr (HAS_BIAS)
             s_bias[tid] = p.bias_dtype == SDNQ_F32 ? __uint_as_float(ev_bias) : (p.bias_dtype == SDNQ_BF16 ? __uint_as_float(ev_bias << 16) : f16_bits_to_f32((uint16_t)ev_bias));
     }
-    AQ_TRACE(2);
+    SDNQ_PHASE_STAMP(p.trace, 2);
 
     // ---- K loop: weight stages through the ring, activation fragments from the resident image ----------------------------------------
     typename MT::acc_t acc;
@@ -299,11 +255,11 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
         fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
     };
-    aq_wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
+    wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     issueB(AHEAD, AHEAD);              // the ring's last free slot
-    aq_static_for<KS>([&](auto ksc) { read_stage(std::integral_constant<int, 0>{}, ksc, 0, 0); });
+    static_for_up<KS>([&](auto ksc) { read_stage(std::integral_constant<int, 0>{}, ksc, 0, 0); });
     int slot_c = 0;  // ring slot of the stage whose fragments are in registers
 #ifdef SDNQ_AQ_LAB
     const int lab = __builtin_amdgcn_readfirstlane(p.lab);
@@ -312,7 +268,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #endif
     auto half = [&](auto setc, int kt) {
         constexpr int sx = decltype(setc)::value;
-        aq_wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
+        wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads of stage kt have retired: the slot may be refilled
         __builtin_amdgcn_sched_barrier(0);
         if (!(lab & 8)) __builtin_amdgcn_s_barrier();
@@ -320,7 +276,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         const int slot_free = slot_c;
         slot_c = (slot_c + 1 == NSB) ? 0 : slot_c + 1;
         // MFMA ks of stage kt, then read ks of stage kt + 1 (the last sub-step's reads retire under the next barrier's wait; KS <= 4)
-        aq_static_for<KS>([&](auto ksc) {
+        static_for_up<KS>([&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
             if (!(lab & 4)) MT::mma(acc, fb[sx][ks], fa[sx][ks]);
             __builtin_amdgcn_sched_barrier(0);
@@ -334,10 +290,10 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         half(std::integral_constant<int, 0>{}, kt);
         if (kt + 1 < nk) half(std::integral_constant<int, 1>{}, kt + 1);
     }
-    AQ_TRACE(3);
+    SDNQ_PHASE_STAMP(p.trace, 3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing filler DMAs target the ring; the staging area below is the A image
     __syncthreads();                                  // every wave is done with the A image before it becomes the output staging area
-    AQ_TRACE(4);
+    SDNQ_PHASE_STAMP(p.trace, 4);
 
     // ---- epilogue in the MFMA register layout: lane owns row wm*32 + (lane & 31), channels wn*32 + (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5);
     // out = cast(fma(f32(acc) * xs, ws, bias)) (kernel_wrappers.py:132-144); final 16-bit values leave through LDS as 16-byte row pieces
@@ -360,7 +316,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         }
     }
     __syncthreads();
-    AQ_TRACE(5);
+    SDNQ_PHASE_STAMP(p.trace, 5);
     constexpr int PPR = BN * 2 / 16;  // 16-byte pieces per output row
 #pragma unroll
     for (int v = tid; v < BM * PPR; v += NT) {
@@ -370,27 +326,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         __builtin_nontemporal_store((v4i){(int)val.x, (int)val.y, (int)val.z, (int)val.w},
                                     (v4i*)((uint8_t*)p.out + ((int64_t)(m0 + r) * p.ldc + n0 + c * 8) * 2));
     }
-    AQ_TRACE(6);
-}
-
-// which problems take the one-launch route.  Costs that grow with it: tiles_n workgroups repeat the quantization of a row block (VALU
-// time on the critical path of every tile), and a tile keeps its rows resident (K <= 1280).  Wins where the row-quantization launch
-// is a large part of the pair: the one-round projections of the bs = 1 steps.
-inline int64_t aq_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    return e ? atoll(e) : dflt;
-}
-
-inline int aq_cu_count() {  // of the CURRENT device (a process may drive different parts / partitions)
-    static std::atomic<int> cus[64];
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
+    SDNQ_PHASE_STAMP(p.trace, 6);
 }
 
 std::atomic<unsigned long long*> g_aq_trace{nullptr};
@@ -402,8 +338,8 @@ std::atomic<int> g_aq_geometry{-1};  // tests / labs: -1 by shape, 0 = 64 x 128,
 //   at most one tile per CU.  Everything else keeps geometry 0 (64 x 128, 4 ring slots).
 struct AqPlan { int geometry, bm, bn, tiles_m, tiles_n, group_m; int64_t prefetch_room; };
 inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
-    static const int geo_env = (int)aq_env("SDNQ_HIP_FUSED_ROWQUANT_GEOMETRY", -1);  // tuning aid
-    static const int gm_env = (int)aq_env("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);     // tuning aid (1 = n fastest)
+    static const int geo_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GEOMETRY", -1);  // tuning aid
+    static const int gm_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);     // tuning aid (1 = n fastest)
     int geo = g_aq_geometry.load(std::memory_order_relaxed);
     if (geo < 0) geo = geo_env;
     if (geo < 0) geo = (mm_dtype == SDNQ_MM_I8 && k > 640 && (n % 256) == 0 && ((m + 31) / 32) * (n / 256) <= cus) ? 1 : 0;
@@ -426,23 +362,14 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
     constexpr int LDS_BYTES = NJ * BM * BK + NSB * BN * BK + (2 * BN + BM) * 4;
     static_assert(LDS_BYTES <= 160 * 1024 && 2 * LDS_BYTES > 160 * 1024, "LDS budget: one workgroup per CU (aq_plan's prefetch room)");
     auto kern = linear_aq_kernel<X_T, MM, HAS_BIAS, NJ, NSB, BM, BN>;
-    // (the attribute belongs to the function ON ONE DEVICE: a process that drives several GPUs sets it once per device, not once)
     static std::atomic<uint64_t> attr_devices{0};
-    if (LDS_BYTES > 64 * 1024) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return SDNQ_ERR_LAUNCH;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return SDNQ_ERR_LAUNCH;
-            attr_devices.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    if (LDS_BYTES > 64 * 1024 && !allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
     if (pl.bm != BM || pl.bn != BN) return SDNQ_ERR_LAUNCH;
     const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, group_m = pl.group_m;
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     p.trace = g_aq_trace.load(std::memory_order_relaxed);
 #ifdef SDNQ_AQ_LAB
-    { const char* e = getenv("SDNQ_HIP_AQ_LAB"); p.lab = e ? atoi(e) : 0; }
+    p.lab = (int)env_int("SDNQ_HIP_AQ_LAB", 0);
 #endif
     const int pf_wgs = sdnq_internal_take_prefetch(pl.prefetch_room, NT, p.pf_ptr, p.pf_lines);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles + pf_wgs)), dim3(NT), LDS_BYTES, s, (const uint16_t*)x, (const uint8_t*)w, (int)ldx, (int)k, (int)m,
@@ -453,20 +380,23 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
 
 }  // namespace
 
+// which problems take the one-launch route.  Costs that grow with it: tiles_n workgroups repeat the quantization of a row block (VALU
+// time on the critical path of every tile), and a tile keeps its rows resident (K <= 1280).  Wins where the row-quantization launch
+// is a large part of the pair: the one-round projections of the bs = 1 steps.
 extern "C" int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, int out_dtype, int64_t m, int64_t n, int64_t k) {
-    static const int64_t on = aq_env("SDNQ_HIP_FUSED_ROWQUANT", 1), max_tn = aq_env("SDNQ_HIP_FUSED_ROWQUANT_MAX_TILES_N", 12),
-                         min_m = aq_env("SDNQ_HIP_FUSED_ROWQUANT_MIN_M", 33), min_k = aq_env("SDNQ_HIP_FUSED_ROWQUANT_MIN_K", 128),
-                         max_k = aq_env("SDNQ_HIP_FUSED_ROWQUANT_MAX_K", 1280);
+    static const int64_t on = env_int("SDNQ_HIP_FUSED_ROWQUANT", 1), max_tn = env_int("SDNQ_HIP_FUSED_ROWQUANT_MAX_TILES_N", 12),
+                         min_m = env_int("SDNQ_HIP_FUSED_ROWQUANT_MIN_M", 33), min_k = env_int("SDNQ_HIP_FUSED_ROWQUANT_MIN_K", 128),
+                         max_k = env_int("SDNQ_HIP_FUSED_ROWQUANT_MAX_K", 1280);
     // fp8: built and bit-identical, off by default -- its quantization is costlier per element (sign fix-up, clamp, two converts per four
     // codes) and the SDXL fp8 step lost 2 % with it (7.08 -> 7.23 ms, profiles/r05_fused_rowquant_gemm.txt)
-    static const int64_t fp8_on = aq_env("SDNQ_HIP_FUSED_ROWQUANT_FP8", 0);
+    static const int64_t fp8_on = env_int("SDNQ_HIP_FUSED_ROWQUANT_FP8", 0);
     if (!on) return 0;
     if (mm_dtype != SDNQ_MM_I8 && !(mm_dtype == SDNQ_MM_FP8 && fp8_on)) return 0;
     if ((x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) || out_dtype != x_dtype) return 0;
     if (m < min_m || n <= 0 || (n % 8) != 0 || k <= 0 || (k % 128) != 0 || k > 1280) return 0;
     const int64_t tiles_m = (m + 63) / 64, tiles_n = (n + 127) / 128;  // (counted on the 64 x 128 tile, whichever geometry runs)
     if (tiles_n > max_tn || k < min_k || k > max_k) return 0;
-    if (tiles_m * tiles_n > (int64_t)aq_cu_count()) return 0;  // one round, one workgroup per CU
+    if (tiles_m * tiles_n > (int64_t)cu_count()) return 0;  // one round, one workgroup per CU
     return 1;
 }
 
@@ -484,7 +414,7 @@ extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dty
     AqParams p{};
     p.sb = sb; p.bias = bias; p.out = out; p.ldc = n; p.bias_dtype = bias_dtype;
     hipStream_t s = (hipStream_t)stream;
-    const AqPlan pl = aq_plan(mm_dtype, m, n, k, aq_cu_count());
+    const AqPlan pl = aq_plan(mm_dtype, m, n, k, cu_count());
 #define AQ_G(XT, MMV, HB, NJV) (pl.geometry ? launch_aq<XT, MMV, HB, NJV, 3, 32, 256>(x, b, ldx, m, n, k, pl, p, s) : launch_aq<XT, MMV, HB, NJV, 4, 64, 128>(x, b, ldx, m, n, k, pl, p, s))
 #define AQ_NJ(XT, MMV, HB) (k <= 640 ? AQ_G(XT, MMV, HB, 5) : AQ_G(XT, MMV, HB, 10))
 #define AQ_B(XT, MMV) (bias ? AQ_NJ(XT, MMV, true) : AQ_NJ(XT, MMV, false))

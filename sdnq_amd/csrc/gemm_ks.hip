@@ -30,13 +30,7 @@
 // CUs together, and 64 x 80 tiles need 47 MB of that where 64 x 128 tiles need 39 MB.  Two other schedules of the same tile were built
 // and measured slower (same file): the K groups alternating fetch and multiply steps (four issuing waves: 24 B/clk), and sixteen
 // waves with eight dedicated fetch waves (the first stages then land behind the whole prologue: +2 us).
-#include <atomic>
-#include <cstdlib>
-#include <type_traits>
-
-#include "sdnq_dev.h"
-
-int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr[4], int pf_lines[4]);  // gemm.hip
+#include "gemm_dev.h"
 
 namespace {
 
@@ -61,25 +55,18 @@ struct KsParams {
     int pf_early;               // the prefetch loads go out right behind the prologue (else: behind the tile's last stage)
 };
 
-template <int N> __device__ __forceinline__ void ks_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // s_waitcnt vmcnt(n) with the largest immediate of a sorted candidate table that does not exceed `allow` (wave-uniform; waiting for
 // more than necessary is always safe): a balanced tree of scalar compares, four levels for sixteen candidates
 struct KsWait24 { static constexpr int n = 24; static constexpr int c[24] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23}; };
 template <typename T, int LO, int HI> __device__ __forceinline__ void ks_wait_tree(int allow) {
     if constexpr (LO == HI) {
-        ks_wait_vmcnt<T::c[LO]>();
+        wait_vmcnt<T::c[LO]>();
     } else {
         constexpr int MID = (LO + HI + 1) / 2;
         if (allow >= T::c[MID]) ks_wait_tree<T, MID, HI>(allow);
         else ks_wait_tree<T, LO, MID - 1>(allow);
     }
 }
-
-#define KS_TRACE(slot)                                                                                                   \
-    do {                                                                                                                 \
-        if (p.trace != nullptr && threadIdx.x == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
 
 // OUT_T: bf16 / f16 output
 template <int OUT_T, bool HAS_BIAS>
@@ -92,20 +79,8 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {   // block b runs on XCD b % 8 (private L2 each): every XCD walks a contiguous range of the tile sequence ...
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    int tile_m, tile_n;
-    {   // ... in groups of `group_m` row blocks, m fastest (gemm.hip's order): the 32 tiles of an XCD share 8 row blocks x 4 weight blocks
-        const int per_group = group_m * tiles_n;
-        const int gid = bid / per_group, first_m = gid * group_m;
-        const int gsz = (tiles_m - first_m) < group_m ? (tiles_m - first_m) : group_m;
-        const int in_g = bid - gid * per_group;
-        tile_n = in_g / gsz;
-        tile_m = first_m + in_g - tile_n * gsz;
-    }
+    int tile_m, tile_n;  // the 32 tiles of an XCD share 8 row blocks x 4 weight blocks
+    grouped_tile(xcd_contiguous(blockIdx.x, nwg), tiles_m, tiles_n, group_m, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nk = K / BK;  // (launcher: K % 128 == 0)
     const int m_rows = (M - m0) < BM ? (M - m0) : BM, n_lim = (N - n0) < BN ? (N - n0) : BN;
@@ -165,7 +140,7 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
     const bool pf_early = p_.pf_early != 0;
     if (pf_early) prefetch_next();
     if (p.trace != nullptr && tid == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8] = t_entry;
-    KS_TRACE(1);
+    SDNQ_PHASE_STAMP(p.trace, 1);
 
     // ---- K loop: iteration t = stages 2t (K group 0) and 2t + 1 (K group 1); ONE barrier per two stages ---------------------------------
     const int grp = wave >> 2, w4 = wave & 3;  // K group; rows 16 w4 .. +16 of the tile
@@ -189,7 +164,7 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (t == 0) KS_TRACE(2);
+        if (t == 0) SDNQ_PHASE_STAMP(p.trace, 2);
         const int st = 2 * t + grp;
         v4i xa0, xa1, wf0[5], wf1[5];
         const bool mine = st < nk;  // (odd stage count: group 1 has no stage in the last iteration)
@@ -220,10 +195,10 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
             for (int i = 0; i < 5; ++i) acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf1[i], xa1, acc[i], 0, 0, 0);
         }
     }
-    KS_TRACE(3);
+    SDNQ_PHASE_STAMP(p.trace, 3);
     // (the vector piece is older than every stage the loop waited for from iteration 3 on; a shorter loop waits here: everything but
     //  the four prefetch loads)
-    if (niter <= 3) { if (pf_early) ks_wait_vmcnt<0>(); else ks_wait_vmcnt<4>(); }
+    if (niter <= 3) { if (pf_early) wait_vmcnt<0>(); else wait_vmcnt<4>(); }
     // ---- the two K groups meet: group 0 finishes channel blocks 0-2, group 1 blocks 3-4; each hands the other its partial sums of the
     // blocks it does not finish (lane-linear 16-byte stores: [wave of the group][block][lane])
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -255,7 +230,7 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    KS_TRACE(4);
+    SDNQ_PHASE_STAMP(p.trace, 4);
     // epilogue in the MFMA register layout: lane owns row 16 w4 + (lane & 15), channels 16 i + 4 (lane >> 4) + 0..3;
     // out = cast(fma(f32(acc) * sa, sb, bias)) (kernel_wrappers.py:132-144); the final 16-bit values leave through LDS as 16-byte row pieces
     {
@@ -284,7 +259,7 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    KS_TRACE(5);
+    SDNQ_PHASE_STAMP(p.trace, 5);
     constexpr int PPR = BN * 2 / 16;  // 16-byte pieces per output row
 #pragma unroll
     for (int v = tid; v < BM * PPR; v += NT) {
@@ -294,19 +269,7 @@ __global__ __launch_bounds__(NT) void gemm_ks_kernel(const uint8_t* __restrict__
         __builtin_nontemporal_store(val,
                                     (v4i*)((uint8_t*)p.out + ((int64_t)(m0 + r) * p.ldc + n0 + c * 8) * 2));
     }
-    KS_TRACE(6);
-}
-
-inline int ks_cu_count() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    static std::atomic<int> cus[64];
-    int v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
+    SDNQ_PHASE_STAMP(p.trace, 6);
 }
 
 std::atomic<unsigned long long*> g_ks_trace{nullptr};
@@ -314,22 +277,16 @@ std::atomic<unsigned long long*> g_ks_trace{nullptr};
 template <int OUT_T, bool HAS_BIAS>
 int launch_ks(const void* a, const void* b, int64_t lda, int64_t ldb, int64_t m, int64_t n, int64_t k, KsParams p, hipStream_t s) {
     auto kern = gemm_ks_kernel<OUT_T, HAS_BIAS>;
-    static std::atomic<uint64_t> attr_devices{0};  // (the attribute belongs to the function ON ONE DEVICE)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return SDNQ_ERR_LAUNCH;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return SDNQ_ERR_LAUNCH;
-        attr_devices.fetch_or(bit, std::memory_order_release);
-    }
+    static std::atomic<uint64_t> attr_devices{0};
+    if (!allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
     const int tiles_m = (int)((m + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     p.trace = g_ks_trace.load(std::memory_order_relaxed);
-    static const int gm_env = [] { const char* e = getenv("SDNQ_HIP_KS_GROUP_M"); return e ? atoi(e) : 8; }();  // tuning aid
+    static const int gm_env = (int)env_int("SDNQ_HIP_KS_GROUP_M", 8);  // tuning aid
     const int group_m = gm_env < 1 ? 1 : (gm_env > tiles_m ? tiles_m : gm_env);
-    static const int pro_env = [] { const char* e = getenv("SDNQ_HIP_KS_PRO"); const int v = e ? atoi(e) : 6; return v < 2 ? 2 : (v > 6 ? 6 : v); }();  // tuning aid
+    static const int pro_env = [] { const int v = (int)env_int("SDNQ_HIP_KS_PRO", 6); return v < 2 ? 2 : (v > 6 ? 6 : v); }();  // tuning aid
     p.pro = pro_env;
-    static const int pf_env = [] { const char* e = getenv("SDNQ_HIP_KS_PF"); return e ? atoi(e) : 1; }();  // 0 off, 1 behind the last stage, 2 behind the prologue
+    static const int pf_env = (int)env_int("SDNQ_HIP_KS_PF", 1);  // 0 off, 1 behind the last stage, 2 behind the prologue
     p.pf_early = pf_env == 2;
     // the pending prefetch hint rides inside the tile workgroups: thread t of the launch touches line t of each range
     sdnq_internal_take_prefetch(1 << 20, NT, p.pf_ptr, p.pf_lines);
@@ -359,9 +316,9 @@ bool sdnq_internal_ks_eligible(int64_t m, int64_t n, int64_t k, int64_t lda, int
 // launches, this one fills the chip and its in-tile prefetch burst costs more than it brings); it wins when weights come from HBM
 // (same step without the prefetch: 7.85 -> 7.61 ms).  profiles/r06_ksplit_lab.txt
 bool sdnq_internal_ks_preferred(int64_t m, int64_t n, int64_t k) {
-    static const int on = [] { const char* e = getenv("SDNQ_HIP_KSPLIT"); return e ? atoi(e) : 0; }();
+    static const int on = (int)env_int("SDNQ_HIP_KSPLIT", 0);
     if (!on) return false;
-    const int64_t cus = ks_cu_count();
+    const int64_t cus = cu_count();
     const int64_t t80 = ((m + 63) / 64) * ((n + 79) / 80), t128 = ((m + 63) / 64) * ((n + 127) / 128);
     return (n % 80) == 0 && t80 <= cus && t80 * 5 >= cus * 4 && t128 < t80 && k >= 512;
 }

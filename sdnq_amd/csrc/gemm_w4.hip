@@ -21,13 +21,7 @@
 //
 // Tile 64 x 128, eight waves of 32 x 32 on v_mfma_i32_32x32x32_i8, K stages of 256 columns (full 128-byte lines of every operand):
 // 16 + 16 + 8 one-KiB LDS-DMA pieces per stage = 5 per wave, 3-stage ring + the int8 image (152 KB: one workgroup per CU).
-#include <atomic>
-#include <cstdlib>
-#include <type_traits>
-
-#include "sdnq_dev.h"
-
-int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr[4], int pf_lines[4]);  // gemm.hip
+#include "gemm_dev.h"
 
 namespace {
 
@@ -49,8 +43,6 @@ struct W4Params {
     const uint8_t* pf_ptr[4];  // weight prefetch hosted by this launch (sdnq_hip_prefetch_hint)
     int pf_lines[4];
 };
-
-template <int N> __device__ __forceinline__ void w4_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // 8 packed bytes (16 four-bit codes, element j = nibble j) -> the 16 int8 values, through the 16-entry table t (entry c = byte c & 3 of
 // dword c >> 2).  The same look-up as requant_lut4_kernel (dequant.hip), on whole dwords: nibble split (even / odd elements), two
@@ -90,34 +82,13 @@ __global__ __launch_bounds__(NT) void gemm_w4_kernel(const uint8_t* __restrict__
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    if (bid >= nwg) {  // hosted weight prefetch: one dword of every 128-byte line of the next layers' weights (gemm.hip, launch_one)
-        const int t = (bid - nwg) * NT + tid, stride = ((int)gridDim.x - nwg) * NT;
-#pragma nounroll
-        for (int r = 0; r < 4; ++r) {
-            const uint8_t* base = p.pf_ptr[r];
-            const int lines = p.pf_lines[r];
-            for (int i = t; i < lines; i += stride) {
-                int v;
-                asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(base + (int64_t)i * 128) : "memory");
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int bid = blockIdx.x;
+    if (bid >= nwg) {  // hosted weight prefetch
+        SDNQ_PREFETCH_LINES(tid, bid - nwg, NT, (int)gridDim.x - nwg, p);
         return;
     }
-    {   // block b runs on XCD b % 8 (private L2 each): every XCD walks a contiguous range of the tile sequence, groups of row blocks, m fastest
-        const int q = nwg / 8, r = nwg % 8, xcd = bid % 8, j = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
     int tile_m, tile_n;
-    {
-        const int per_group = group_m * tiles_n;
-        const int gid = bid / per_group, first_m = gid * group_m;
-        const int gsz = (tiles_m - first_m) < group_m ? (tiles_m - first_m) : group_m;
-        const int in_g = bid - gid * per_group;
-        tile_n = in_g / gsz;
-        tile_m = first_m + in_g - tile_n * gsz;
-    }
+    grouped_tile(xcd_contiguous(bid, nwg), tiles_m, tiles_n, group_m, tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nk = (K + SK - 1) / SK;              // stages; the last one holds 128 columns when K % 256 == 128 (launcher: K % 128 == 0)
     const int last_ks = (K % SK) ? 4 : 8;          // K sub-steps (32 columns) of the last stage
@@ -196,9 +167,9 @@ __global__ __launch_bounds__(NT) void gemm_w4_kernel(const uint8_t* __restrict__
         // stage kt has landed (this wave's pieces; the barrier makes it everybody's): the stages requested behind it stay in flight
         // (the epilogue vectors' loads sit between the prologue's pieces and the stages requested inside the loop)
         constexpr int EV = HAS_BIAS ? 3 : 2;
-        if (kt == 0 && issued >= 2) w4_wait_vmcnt<PPW + EV>();
-        else if (issued - kt - 1 >= 1) w4_wait_vmcnt<PPW>();
-        else w4_wait_vmcnt<0>();
+        if (kt == 0 && issued >= 2) wait_vmcnt<PPW + EV>();
+        else if (issued - kt - 1 >= 1) wait_vmcnt<PPW>();
+        else wait_vmcnt<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads of stage kt - 1 (ring and w8) have retired
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -284,43 +255,20 @@ __global__ __launch_bounds__(NT) void gemm_w4_kernel(const uint8_t* __restrict__
     }
 }
 
-inline int w4_cu_count() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    static std::atomic<int> cus[64];
-    int v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-
 template <int OUT_T, bool HAS_BIAS>
 int launch_w4(const void* a, const void* codes, const void* lut, int64_t lda, int64_t m, int64_t n, int64_t k, W4Params p, hipStream_t s) {
     auto kern = gemm_w4_kernel<OUT_T, HAS_BIAS>;
-    static std::atomic<uint64_t> attr_devices{0};  // (the attribute belongs to the function ON ONE DEVICE)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return SDNQ_ERR_LAUNCH;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_devices.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return SDNQ_ERR_LAUNCH;
-        attr_devices.fetch_or(bit, std::memory_order_release);
-    }
+    static std::atomic<uint64_t> attr_devices{0};
+    if (!allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
     const int tiles_m = (int)((m + BM - 1) / BM), tiles_n = (int)((n + BN - 1) / BN);
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     const int group_m = tiles_m < 8 ? tiles_m : 8;
-    const int64_t slots = w4_cu_count();  // one workgroup per CU (120 KB of LDS)
+    const int64_t slots = cu_count();  // one workgroup per CU (120 KB of LDS)
     const int pf_wgs = sdnq_internal_take_prefetch(tiles < slots ? slots - tiles : 0, NT, p.pf_ptr, p.pf_lines);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles + pf_wgs)), dim3(NT), LDS_BYTES, s, (const uint8_t*)a, (const uint8_t*)codes, (const uint8_t*)lut, (int)lda, (int)m,
                        (int)n, (int)k, tiles_m, tiles_n, group_m, p);
     SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
-}
-
-inline int64_t w4_env(const char* name, int64_t dflt) {
-    const char* e = getenv(name);
-    return e ? atoll(e) : dflt;
 }
 
 }  // namespace
@@ -330,8 +278,8 @@ extern "C" int sdnq_hip_scaled_mm_w4_supported(int mm_dtype, int out_dtype, int6
     // 1024 x 1280 x 1280 10.4 vs 12.4 us (the 232 c x c projections of an SDXL step), 1024 x 3840 x 1280 19.7 vs 19.7; it loses at
     // K = 5120 (31.9 vs 28.9), N = 10240 (48.0 vs 35.1) and from 2048 rows on (19.1 vs 15.3) -- every row block of 64 rows repeats the
     // expansion, and the expand / multiply phases of a stage do not overlap yet
-    static const int64_t on = w4_env("SDNQ_HIP_FUSED_LUT4", 1), max_m = w4_env("SDNQ_HIP_FUSED_LUT4_MAX_M", 1024), min_m = w4_env("SDNQ_HIP_FUSED_LUT4_MIN_M", 33),
-                         max_k = w4_env("SDNQ_HIP_FUSED_LUT4_MAX_K", 1280), max_n = w4_env("SDNQ_HIP_FUSED_LUT4_MAX_N", 3840);
+    static const int64_t on = env_int("SDNQ_HIP_FUSED_LUT4", 1), max_m = env_int("SDNQ_HIP_FUSED_LUT4_MAX_M", 1024), min_m = env_int("SDNQ_HIP_FUSED_LUT4_MIN_M", 33),
+                         max_k = env_int("SDNQ_HIP_FUSED_LUT4_MAX_K", 1280), max_n = env_int("SDNQ_HIP_FUSED_LUT4_MAX_N", 3840);
     if (!on || mm_dtype != SDNQ_MM_I8) return 0;
     if (out_dtype != SDNQ_BF16 && out_dtype != SDNQ_F16) return 0;
     if (m < min_m || m > max_m || n <= 0 || n > max_n || (n % 8) != 0 || k < 128 || k > max_k || (k % 128) != 0) return 0;
