@@ -48,9 +48,10 @@ UNITS = (
     ("dequant", _PRELOAD, None),
     ("quantize", "", None),
     ("conv", _PRELOAD, None),
-    # attention.hip: keep the MFMA accumulators in VGPRs (the softmax rescales / reads them with VALU every block; in AGPR form
-    # the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
+    # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them
+    # with VALU every block; in AGPR form the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),
+    ("attention_var", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_bwd", "", None),
     ("parallel", "", None),
 )

@@ -12,68 +12,41 @@
 //
 // Blocks are 32 queries x 32 keys, the block of the forward kernels and of the fixtures.  One wave per workgroup, all matmuls on the
 // matrix cores (v_mfma_i32_32x32x32_i8 for Q.K^T, dS.K and Q^T.dS; the bf16 / f16 32x32x16 MFMA for dO.V^T and dO^T.P).
-// MFMA operand / result layouts used below (lane l = 32 g + i):
-//   32x32x32 i8:   A row i, bytes k = 16 g .. 16 g + 15;  B column i, the same k
-//   32x32x16 16-bit: A row i, elements k = 8 g .. 8 g + 7;  B column i, the same k
-//   result:        column i, register r <-> row 8 (r >> 2) + 4 g + (r & 3)
-// K codes arrive in the fragment order of sdnq_hip_attn_prepare: 1-KiB tile per (32-key block, 32-channel step), lane (g, rho) holds
-// bytes [32 kk + 16 g, +16) of key pi(rho), pi = swap bits 2 and 3.  With K as the A operand of Q.K^T, register r of lane (g, q) is the
-// score of key 16 (r >> 3) + 8 g + (r & 7) (= sigma(g, r)); with K as the B operand, of query 8 (r >> 2) + 4 g + (r & 3) (= tau(g, r)).
-// A contraction may take its k index in any order common to both operands: the dS tiles feed the next MFMA straight from the
+// Operand layouts, the K fragment order and its row permutation pi = attn_kpi: attn_dev.h.  With K as the A operand of Q.K^T, register r of
+// lane (g, q) is the score of key 16 (r >> 3) + 8 g + (r & 7) (= sigma(g, r)); with K as the B operand, of query 8 (r >> 2) + 4 g + (r & 3)
+// (= tau(g, r)).  A contraction may take its k index in any order common to both operands: the dS tiles feed the next MFMA straight from the
 // accumulator registers, and the other operand (K^T, Q^T, dO^T) is staged in LDS in that same order.
 
-#include "../../include/sdnq_hip.h"
-#include "sdnq_dev.h"
+#include "attn_dev.h"
 
 namespace {
 
-struct BStrides {  // element strides of [batch][heads][tokens][channels]; `heads` splits a linear batch*heads index
-    int64_t b, h, n, heads;
-    __device__ __forceinline__ int64_t at(int64_t head_lin, int64_t tok) const {
-        int64_t zb, hh;
-        divmod(head_lin, heads, zb, hh);
-        return zb * b + hh * h + tok * n;
-    }
-};
-
 struct BwdParams {
     const int8_t* qq; const float* qs; const int8_t* kq; const float* ks;
-    const void* v; BStrides vst;               // value dtype, d_src channels
-    const void* gv; BStrides gvst;             // dO in the value dtype (the matmul operand)
-    const void* out; BStrides ost;             // out and dO in the grad dtype (delta)
-    const void* g; BStrides gst;
+    const void* v; Strides vst;               // value dtype, d_src channels
+    const void* gv; Strides gvst;             // dO in the value dtype (the matmul operand)
+    const void* out; Strides ost;             // out and dO in the grad dtype (delta)
+    const void* g; Strides gst;
     const void* lse; int lse_dtype;
     float* delta;
-    const void* mask; int mask_dtype; int64_t ms_z, ms_h, ms_q;
-    void* dq; BStrides dqst; int dq_ch;
-    void* dk; BStrides dkst; int dk_ch;
-    void* dv; BStrides dvst;
+    AttnMask m;
+    void* dq; Strides dqst; int dq_ch;
+    void* dk; Strides dkst; int dk_ch;
+    void* dv; Strides dvst;
     int grad_dtype;
     int64_t qh, kh, qn, kn, knp;
     int d_src, causal;
     float sm_scale, log2_sm_scale;
 };
 
-__device__ __forceinline__ int kpi(int rho) { return (rho & 0x13) | ((rho & 4) << 1) | ((rho & 8) >> 1); }
-
-__device__ __forceinline__ float ld_any(const void* p, int64_t i, int dt) {
-    return dt == SDNQ_F32 ? ((const float*)p)[i] : (dt == SDNQ_BF16 ? bf16_bits_to_f32(((const uint16_t*)p)[i]) : f16_bits_to_f32(((const uint16_t*)p)[i]));
-}
-
-__device__ __forceinline__ void st_any(void* p, int64_t i, float v, int dt) {
-    if (dt == SDNQ_F32) ((float*)p)[i] = v;
-    else if (dt == SDNQ_BF16) ((uint16_t*)p)[i] = f32_to_bf16_bits(v);
-    else ((uint16_t*)p)[i] = f32_to_f16_bits(v);
-}
-
 // mask / causal / key tail of one score (triton_atten_backward.py:170-178)
 __device__ __forceinline__ float attn_bwd_mask(const BwdParams& p, float qk, int64_t z, int64_t h, int64_t q, int64_t key) {
     if (p.causal && key > q) return -__builtin_inff();
     if (key >= p.kn) return -__builtin_inff();
-    if (p.mask != nullptr) {
-        const int64_t i = z * p.ms_z + h * p.ms_h + q * p.ms_q + key;
-        if (p.mask_dtype == -1) return ((const int8_t*)p.mask)[i] != 0 ? qk : -__builtin_inff();
-        return qk + ld_any(p.mask, i, p.mask_dtype);
+    if (p.m.mask != nullptr) {
+        const int64_t i = z * p.m.ms_z + h * p.m.ms_h + q * p.m.ms_q + key;
+        if (p.m.mask_dtype == -1) return ((const int8_t*)p.m.mask)[i] != 0 ? qk : -__builtin_inff();
+        return qk + ld_rt(p.m.mask, i, p.m.mask_dtype);
     }
     return qk;
 }
@@ -84,25 +57,13 @@ __device__ __forceinline__ v4i ld_row8(const void* base, int64_t off, int c0, in
     return *(const v4i*)((const uint16_t*)base + off + c0);
 }
 
-template <int V_T>
-__device__ __forceinline__ v16f mfma16(const v4i& a, const v4i& b, const v16f& c) {
-    if constexpr (V_T == SDNQ_BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float max_pair(float m) {  // the other 16 scores of a row / column live in lane ^ 32
-    const u32 mb = __float_as_uint(m);
-    const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-    return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
-}
-
 // per-(row, block) int8 of 16 values of this lane + 16 of lane ^ 32 (triton_atten_backward.py:200-204 / 431-435): s = max|x| / 127
 // (1 where <= 2e-38), code = floor(fma(x, 1 / s, 0.5)); returns s, the codes as the k = 16 bytes of an i8 MFMA operand (byte j = x[j])
 __device__ __forceinline__ float quant_block(const float (&x)[16], v4i& codes) {
     float mx = 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, __builtin_fabsf(x[r]));
-    mx = max_pair(mx);
+    mx = attn_max32(mx);
     float s = mx * (float)(1.0 / 127.0);
     if (s <= 2e-38f) s = 1.0f;
     const float inv = 1.0f / s;
@@ -151,9 +112,9 @@ __global__ __launch_bounds__(64) void attn_lse_kernel(const BwdParams p, int64_t
             t[r] = attn_bwd_mask(p, qk, z, h, qrow, key);
             mb = fmaxf(mb, t[r]);
         }
-        const float m_ij = fmaxf(m_i, max_pair(mb));
+        const float m_ij = fmaxf(m_i, attn_max32(mb));
         float alpha, sub;
-        if (p.mask != nullptr) {  // triton_atten.py:299-301
+        if (p.m.mask != nullptr) {  // triton_atten.py:299-301
             alpha = __builtin_amdgcn_exp2f((m_i == -__builtin_inff() && m_ij == -__builtin_inff()) ? 0.0f : m_i - m_ij);
             sub = m_ij == -__builtin_inff() ? 0.0f : m_ij;
         } else {
@@ -169,8 +130,8 @@ __global__ __launch_bounds__(64) void attn_lse_kernel(const BwdParams p, int64_t
     }
     if (qi >= p.qn || g != 0) return;
     float lse = m_i + __builtin_log2f(l_i);  // :329
-    if (p.mask != nullptr && lse == -__builtin_inff()) lse = 0.0f;
-    st_any((void*)p.lse, head_lin * p.qn + qi, lse, p.lse_dtype);
+    if (p.m.mask != nullptr && lse == -__builtin_inff()) lse = 0.0f;
+    st_rt((void*)p.lse, head_lin * p.qn + qi, lse, p.lse_dtype);
 }
 
 // ---- delta = sum(out * dO): one thread per query row ------------------------------------------------------------------------------
@@ -181,7 +142,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const BwdParams p, int6
     const int64_t oo = p.ost.at(head_lin, q), go = p.gst.at(head_lin, q);
     float acc = 0.0f;
     for (int c = 0; c < p.d_src; ++c)
-        acc += round_rt(ld_any(p.out, oo + c, p.grad_dtype) * ld_any(p.g, go + c, p.grad_dtype), p.grad_dtype);
+        acc += round_rt(ld_rt(p.out, oo + c, p.grad_dtype) * ld_rt(p.g, go + c, p.grad_dtype), p.grad_dtype);
     p.delta[row] = acc;
 }
 
@@ -204,10 +165,10 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const BwdParams p, int6
 #pragma unroll
     for (int s = 0; s < KS; ++s) dof[s] = ld_row8(p.gv, go, 16 * s + 8 * g, p.d_src, true);
     const float qsc = p.qs[head_lin * p.qn + qrow];
-    const float lse = ld_any(p.lse, head_lin * p.qn + qrow, p.lse_dtype), delta = p.delta[head_lin * p.qn + qrow];
+    const float lse = ld_rt(p.lse, head_lin * p.qn + qrow, p.lse_dtype), delta = p.delta[head_lin * p.qn + qrow];
     const int8_t* kbase = p.kq + kv_lin * p.knp * D;
     const float* ksr = p.ks + kv_lin * p.knp;
-    const int kkey = kpi(ql);  // key (inside the block) of this lane's K fragment row / V row
+    const int kkey = attn_kpi(ql);  // key (inside the block) of this lane's K fragment row / V row
     const int kpos = 16 * ((kkey >> 3) & 1) + 8 * (kkey >> 4) + (kkey & 7);
     v16f acc[KK];
 #pragma unroll
@@ -233,7 +194,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const BwdParams p, int6
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[r] = 0.0f;
 #pragma unroll
-        for (int st = 0; st < KS; ++st) dp = mfma16<V_T>(ld_row8(p.v, vo, 16 * st + 8 * g, p.d_src, vok), dof[st], dp);
+        for (int st = 0; st < KS; ++st) dp = attn_mfma16<V_T>(ld_row8(p.v, vo, 16 * st + 8 * g, p.d_src, vok), dof[st], dp);
         __syncthreads();  // the previous block's K^T reads are done
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
@@ -274,7 +235,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const BwdParams p, int6
             const int c0 = 32 * cb + 8 * t4 + 4 * g;
             if (c0 >= p.dq_ch) continue;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) st_any(p.dq, oo + c0 + u, acc[cb][4 * t4 + u], p.grad_dtype);
+            for (int u = 0; u < 4; ++u) st_rt(p.dq, oo + c0 + u, acc[cb][4 * t4 + u], p.grad_dtype);
         }
 }
 
@@ -289,7 +250,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(const BwdParams p, int
     int64_t z, kvh;
     divmod(kv_lin, p.kh, z, kvh);
     const int ratio = (int)(p.qh / p.kh);
-    const int kkey = kpi(ql);
+    const int kkey = attn_kpi(ql);
     const int64_t key = key0 + kkey;
     const bool kok = key < p.kn;
     const bool want_k = p.dk != nullptr, want_v = p.dv != nullptr;
@@ -349,7 +310,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(const BwdParams p, int
             if (want_k) {
                 const int64_t go = p.gvst.at(head_lin, qrow_a);
 #pragma unroll
-                for (int st = 0; st < KS; ++st) dp = mfma16<V_T>(ld_row8(p.gv, go, 16 * st + 8 * g, p.d_src, true), vb[st], dp);
+                for (int st = 0; st < KS; ++st) dp = attn_mfma16<V_T>(ld_row8(p.gv, go, 16 * st + 8 * g, p.d_src, true), vb[st], dp);
             }
             float pr[16], ds[16];
 #pragma unroll
@@ -360,7 +321,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(const BwdParams p, int
                 const float qsc = p.qs[head_lin * p.qn + qc];
                 float qk = (((float)s[r] * qsc) * ksc) * p.log2_sm_scale;  // :387
                 qk = attn_bwd_mask(p, qk, z, h, qc, key);
-                const float lse = ld_any(p.lse, head_lin * p.qn + qc, p.lse_dtype);
+                const float lse = ld_rt(p.lse, head_lin * p.qn + qc, p.lse_dtype);
                 pr[r] = qok ? __builtin_amdgcn_exp2f(qk - lse) : 0.0f;     // :406-408 (rows past the queries contribute nothing)
                 ds[r] = ((pr[r] * (dp[r] - p.delta[head_lin * p.qn + qc])) * p.sm_scale) * qsc;  // :428-430
             }
@@ -388,7 +349,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(const BwdParams p, int
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
-                    for (int cb = 0; cb < KK; ++cb) dv[cb] = mfma16<V_T>(*(const v4i*)(ot + (32 * cb + ql) * 32 + 16 * c + 8 * g), pf[c], dv[cb]);
+                    for (int cb = 0; cb < KK; ++cb) dv[cb] = attn_mfma16<V_T>(*(const v4i*)(ot + (32 * cb + ql) * 32 + 16 * c + 8 * g), pf[c], dv[cb]);
             }
         }
     }
@@ -400,33 +361,25 @@ __global__ __launch_bounds__(64) void attn_bwd_dkv_kernel(const BwdParams p, int
             const int c0 = 32 * cb + 8 * t4 + 4 * g;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (want_k && c0 < p.dk_ch) st_any(p.dk, p.dkst.at(kv_lin, key) + c0 + u, dk[cb][4 * t4 + u], p.grad_dtype);
-                if (want_v && c0 < p.d_src) st_any(p.dv, p.dvst.at(kv_lin, key) + c0 + u, dv[cb][4 * t4 + u], p.grad_dtype);
+                if (want_k && c0 < p.dk_ch) st_rt(p.dk, p.dkst.at(kv_lin, key) + c0 + u, dk[cb][4 * t4 + u], p.grad_dtype);
+                if (want_v && c0 < p.d_src) st_rt(p.dv, p.dvst.at(kv_lin, key) + c0 + u, dv[cb][4 * t4 + u], p.grad_dtype);
             }
         }
 }
-
-bool set_strides(const int64_t* st, int64_t heads, int64_t len, int64_t ch, BStrides& o) {
-    o.heads = heads;
-    if (st) { o.b = st[0]; o.h = st[1]; o.n = st[2]; } else { o.b = heads * len * ch; o.h = len * ch; o.n = ch; }
-    return o.b % 8 == 0 && o.h % 8 == 0 && o.n % 8 == 0;  // 16-byte rows of 16-bit elements
-}
-
-bool float_ok(int dt) { return dt == SDNQ_F32 || dt == SDNQ_BF16 || dt == SDNQ_F16; }
 
 int fill_common(BwdParams& p, const void* qq, const float* qs, const void* kq, const float* ks, float sm_scale, int is_causal, const void* mask,
                 int mask_dtype, int64_t ms_b, int64_t ms_h, int64_t ms_q, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len,
                 int64_t kv_len, int64_t head_dim) {
     if (!qq || !qs || !kq || !ks) return SDNQ_ERR_NULL;
-    if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || q_len <= 0 || kv_len <= 0 || q_heads % kv_heads) return SDNQ_ERR_SHAPE;
-    if (head_dim < 8 || head_dim > 128 || head_dim % 8) return SDNQ_ERR_UNSUPPORTED;
-    if (mask && mask_dtype != -1 && !float_ok(mask_dtype)) return SDNQ_ERR_DTYPE;
+    if (!shape_ok(batch, q_heads, kv_heads, q_len, kv_len, 1)) return SDNQ_ERR_SHAPE;  // (a head dim <= 0 is the next line's)
+    if (attn_padded_dim(head_dim) == 0) return SDNQ_ERR_UNSUPPORTED;
+    if (!attn_mask_ok(mask, mask_dtype)) return SDNQ_ERR_DTYPE;
     if (((uintptr_t)qq | (uintptr_t)kq) % 16) return SDNQ_ERR_ALIGN;
     p.qq = (const int8_t*)qq; p.qs = qs; p.kq = (const int8_t*)kq; p.ks = ks;
     p.qh = q_heads; p.kh = kv_heads; p.qn = q_len; p.kn = kv_len; p.knp = (kv_len + 31) / 32 * 32;
     p.d_src = (int)head_dim; p.causal = is_causal ? 1 : 0;
-    p.sm_scale = sm_scale; p.log2_sm_scale = sm_scale * 1.4426950408889634f;  // triton_atten_backward.py:88
-    p.mask = mask; p.mask_dtype = mask_dtype; p.ms_z = ms_b; p.ms_h = ms_h; p.ms_q = ms_q;
+    p.sm_scale = sm_scale; p.log2_sm_scale = sm_scale * ATTN_LOG2E;  // triton_atten_backward.py:88
+    p.m = {mask, mask_dtype, ms_b, ms_h, ms_q};
     return SDNQ_OK;
 }
 
@@ -446,7 +399,7 @@ extern "C" int sdnq_hip_attn_lse(const void* qq, const float* qs, const void* kq
     const int64_t qblocks = (q_len + 31) / 32;
     const dim3 grid((unsigned)(batch * q_heads * qblocks)), block(64);
     hipStream_t s = (hipStream_t)stream;
-    if (head_dim <= 64) hipLaunchKernelGGL((attn_lse_kernel<64>), grid, block, 0, s, p, qblocks);
+    if (attn_padded_dim(head_dim) == 64) hipLaunchKernelGGL((attn_lse_kernel<64>), grid, block, 0, s, p, qblocks);
     else hipLaunchKernelGGL((attn_lse_kernel<128>), grid, block, 0, s, p, qblocks);
     SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
@@ -466,15 +419,15 @@ extern "C" int sdnq_hip_attn_bwd(const void* qq, const float* qs, const void* kq
     if (!v || !out || !grad || !grad_v || !lse || !delta) return SDNQ_ERR_NULL;
     if (v_dtype != SDNQ_BF16 && v_dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;
     if (!float_ok(grad_dtype)) return SDNQ_ERR_DTYPE;
-    const int64_t dp = head_dim <= 64 ? 64 : 128;
+    const int64_t dp = attn_padded_dim(head_dim);
     if ((dq && (dq_channels != head_dim && dq_channels != dp)) || (dk && (dk_channels != head_dim && dk_channels != dp))) return SDNQ_ERR_SHAPE;
     if (((uintptr_t)v | (uintptr_t)grad_v) % 16) return SDNQ_ERR_ALIGN;
-    if (!set_strides(v_strides, kv_heads, kv_len, head_dim, p.vst) || !set_strides(grad_v_strides, q_heads, q_len, head_dim, p.gvst)) return SDNQ_ERR_ALIGN;
-    set_strides(out_strides, q_heads, q_len, head_dim, p.ost);
-    set_strides(grad_strides, q_heads, q_len, head_dim, p.gst);
-    set_strides(dq_strides, q_heads, q_len, dq_channels, p.dqst);
-    set_strides(dk_strides, kv_heads, kv_len, dk_channels, p.dkst);
-    set_strides(dv_strides, kv_heads, kv_len, head_dim, p.dvst);
+    if (!attn_set_strides(v_strides, kv_heads, kv_len, head_dim, p.vst) || !attn_set_strides(grad_v_strides, q_heads, q_len, head_dim, p.gvst)) return SDNQ_ERR_ALIGN;
+    attn_set_strides(out_strides, q_heads, q_len, head_dim, p.ost);
+    attn_set_strides(grad_strides, q_heads, q_len, head_dim, p.gst);
+    attn_set_strides(dq_strides, q_heads, q_len, dq_channels, p.dqst);
+    attn_set_strides(dk_strides, kv_heads, kv_len, dk_channels, p.dkst);
+    attn_set_strides(dv_strides, kv_heads, kv_len, head_dim, p.dvst);
     p.v = v; p.gv = grad_v; p.out = out; p.g = grad; p.lse = lse; p.lse_dtype = grad_dtype; p.delta = delta; p.grad_dtype = grad_dtype;
     p.dq = dq; p.dq_ch = (int)dq_channels; p.dk = dk; p.dk_ch = (int)dk_channels; p.dv = dv;
     hipStream_t s = (hipStream_t)stream;

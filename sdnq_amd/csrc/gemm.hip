@@ -255,10 +255,6 @@ __device__ __forceinline__ float acc_times_sa(float a, float sa) {
     else return a * sa;
 }
 
-__device__ __forceinline__ float ldf_rt(const void* p, int64_t i, int dt) {
-    return dt == SDNQ_F32 ? ((const float*)p)[i] : (dt == SDNQ_BF16 ? bf16_bits_to_f32(((const uint16_t*)p)[i]) : f16_bits_to_f32(((const uint16_t*)p)[i]));
-}
-
 // One MFMA operand fragment (the K-contiguous bytes of tile row `r` this lane feeds to K sub-step `ks`) and the MFMA on it.
 template <int MM> struct FragOps {
     typedef v4i frag_t;   // activation-side fragment
@@ -739,7 +735,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
         const int64_t gn = n0 + li;
         if constexpr (!is_float_mm<MM> || is_w8a16<MM>) s_sb[i] = tv.sb[li];
         if constexpr (is_w8a16<MM>) s_zp[i] = p.zp ? p.zp[gn] : -128.0f * tv.sb[li];  // additive constant of the row's dequantization
-        if constexpr (EPI == EPI_BIAS1D || is_lr<EPI>) s_bias[i] = tv.bias ? ldf_rt(tv.bias, tv.bias0 + li, p.bias_dtype) : 0.0f;
+        if constexpr (EPI == EPI_BIAS1D || is_lr<EPI>) s_bias[i] = tv.bias ? ld_rt(tv.bias, tv.bias0 + li, p.bias_dtype) : 0.0f;
         if constexpr (is_lr<EPI>) { s_zp[i] = p.zp ? p.zp[gn] : 0.0f; s_wcs[i] = p.wcs ? p.wcs[gn] : 0.0f; }
     }
 
@@ -1671,7 +1667,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                 } else if constexpr (EPI == EPI_BIAS1D) {
                     res = fmaf(vv, sb4[e], s_biasq[c8 + 4 * h + e]);
                 } else if constexpr (EPI == EPI_BIAS2D) {
-                    res = fmaf(vv, sb4[e], ldf_rt(p.bias, gm * p.ld_bias + gn0 + 4 * h + e, p.bias_dtype));
+                    res = fmaf(vv, sb4[e], ld_rt(p.bias, gm * p.ld_bias + gn0 + 4 * h + e, p.bias_dtype));
                 } else {
                     // bias2d = cast_svd(f32(bias[n]) + sum_r t[m][r]*up[n][r]) (linear_int8.py:57-62), then the zero-point
                     // term f32(rowsum)*sa*zp[n] + bias2d (linear_int8.py:65-69), all f32 into the single-rounding fma
@@ -1687,7 +1683,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                             } else {  // f32 factors or a rank that is not a multiple of 16: plain fma chain
                                 float sacc = 0.0f;
                                 for (int rr = 0; rr < p.rank; ++rr)
-                                    sacc = fmaf(ldf_rt(p.lr_t, gm * p.rank + rr, p.bias_dtype), ldf_rt(p.lr_up, (n0 + cn) * p.rank + rr, p.bias_dtype), sacc);
+                                    sacc = fmaf(ld_rt(p.lr_t, gm * p.rank + rr, p.bias_dtype), ld_rt(p.lr_up, (n0 + cn) * p.rank + rr, p.bias_dtype), sacc);
                                 bv = round_rt(has ? sacc + bv : sacc, p.bias_dtype);
                             }
                             has = true;
@@ -1787,7 +1783,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                         } else {
                             int64_t gn = n0 + cn;
                             if (gn >= hk.N) gn = hk.N - 1;
-                            res = fmaf(vv, sbn, ldf_rt(p.bias, gm * p.ld_bias + gn, p.bias_dtype));  // EPI_BIAS2D
+                            res = fmaf(vv, sbn, ld_rt(p.bias, gm * p.ld_bias + gn, p.bias_dtype));  // EPI_BIAS2D
                         }
                     }
                     o[e] = res;

@@ -98,6 +98,15 @@ template <> struct FT<SDNQ_F16> {
 __device__ __forceinline__ float round_rt(float v, int dt) {
     return dt == SDNQ_F32 ? v : (dt == SDNQ_BF16 ? FT<SDNQ_BF16>::round(v) : FT<SDNQ_F16>::round(v));
 }
+// load / store of element i in a dtype chosen at run time
+__device__ __forceinline__ float ld_rt(const void* p, int64_t i, int dt) {
+    return dt == SDNQ_F32 ? ((const float*)p)[i] : (dt == SDNQ_BF16 ? bf16_bits_to_f32(((const uint16_t*)p)[i]) : f16_bits_to_f32(((const uint16_t*)p)[i]));
+}
+__device__ __forceinline__ void st_rt(void* p, int64_t i, float v, int dt) {
+    if (dt == SDNQ_F32) ((float*)p)[i] = v;
+    else if (dt == SDNQ_BF16) ((uint16_t*)p)[i] = f32_to_bf16_bits(v);
+    else ((uint16_t*)p)[i] = f32_to_f16_bits(v);
+}
 
 // two floats -> one dword of 16-bit elements (low half = a), round-to-nearest-even: ONE v_cvt_pk_bf16_f32 on gfx950 when written as a
 // vector conversion (converting the halves separately and OR-ing them costs a convert per element plus the merge)

@@ -135,6 +135,57 @@ def test_attention_argument_validation_without_gpu():
     assert att(p, p, p, 1, 1, 2, 2, 8, 200, 64, *tail, p, 1, None, None, 0, None) == -1        # > 128 keys need the workspace
     assert att(p, p, p, 1, 1, 2, 2, 8, 200, 64, *tail, p, 1, None, p, 100, None) == -3         # ... of the advertised size
     assert att(p, p + 8, p, 1, 1, 2, 2, 8, 8, 64, *tail, p, 1, None, None, 0, None) == -4      # key rows not 16-byte aligned
+    # the format variants, the lse pass and the backward: every case breaks exactly ONE rule of an otherwise valid call
+    def rc(fn, base, **broken):
+        return fn(*{**base, **broken}.values())
+    shape = dict(batch=1, qh=2, kh=2, qn=8, kn=8, d=64)
+    mask = dict(mask=None, mask_dtype=0, ms_b=0, ms_h=0, ms_q=0)
+    pex = lib.sdnq_hip_attn_prepare_ex
+    a = dict(q=p, k=p, v=p, dtype=1, **shape, smooth=1, had=0, qst=None, kst=None, vst=None, qk=0, pv=-1, qq=p, qs=p, kq=p, ks=p, vt=p, vs=p,
+             kmean=p, stream=None)
+    assert rc(pex, a, q=None) == -1 and rc(pex, a, kmean=None) == -1   # NULL query; smooth_k without the channel-mean buffer
+    assert rc(pex, a, qk=2) == -2                                      # Q.K^T format neither int8 nor fp8
+    assert rc(pex, a, pv=7) == -2                                      # unknown P.V format
+    assert rc(pex, a, pv=0, vs=None) == -1                             # quantized P.V without value scales
+    assert rc(pex, a, qh=3) == -3 and rc(pex, a, kn=0) == -3
+    assert rc(pex, a, d=136) == -5 and rc(pex, a, d=60) == -5
+    assert rc(pex, a, had=48) == -3
+    assert rc(pex, a, q=p + 2) == -4 and rc(pex, a, qst=bad) == -4
+    assert rc(pex, a, dtype=0) == -5                                   # float32 inputs: not built
+    fex = lib.sdnq_hip_attn_fwd_ex
+    a = dict(qq=p, qs=p, kq=p, ks=p, vt=p, vs=p, v_dtype=1, qk=0, pv=-1, sm_scale=0.125, causal=0, **mask, out=p, out_dtype=1, ost=None,
+             **shape, stream=None)
+    assert rc(fex, a, out=None) == -1
+    assert rc(fex, a, qk=2) == -2 and rc(fex, a, pv=7) == -2
+    assert rc(fex, a, pv=0, vs=None) == -1
+    assert rc(fex, a, qh=3) == -3 and rc(fex, a, kn=0) == -3
+    assert rc(fex, a, d=136) == -5 and rc(fex, a, d=60) == -5
+    assert rc(fex, a, qq=p + 2) == -4 and rc(fex, a, out=p + 2) == -4
+    odd = (ctypes.c_int64 * 3)(1024, 516, 66)                          # output rows need 8 bytes only: a token stride of 68 is valid here,
+    assert rc(fex, a, ost=odd) == -4                                   # one of 66 elements is not
+    assert rc(fex, a, mask=p, mask_dtype=5) == -2
+    assert rc(fex, a, out_dtype=5) == -2
+    assert rc(fex, a, v_dtype=0) == -2                                 # f32 value operand
+    lse = lib.sdnq_hip_attn_lse
+    a = dict(qq=p, qs=p, kq=p, ks=p, sm_scale=0.125, causal=0, **mask, lse=p, lse_dtype=1, **shape, stream=None)
+    assert rc(lse, a, qq=None) == -1 and rc(lse, a, lse=None) == -1
+    assert rc(lse, a, qh=3) == -3 and rc(lse, a, kn=0) == -3
+    assert rc(lse, a, d=136) == -5 and rc(lse, a, d=60) == -5
+    assert rc(lse, a, qq=p + 2) == -4
+    assert rc(lse, a, mask=p, mask_dtype=5) == -2
+    assert rc(lse, a, lse_dtype=5) == -2
+    bwd = lib.sdnq_hip_attn_bwd
+    a = dict(qq=p, qs=p, kq=p, ks=p, v=p, vst=None, v_dtype=1, out=p, ost=None, grad=p, gst=None, grad_dtype=1, grad_v=p, gvst=None, lse=p,
+             sm_scale=0.125, causal=0, **mask, delta=p, dq=p, dqst=None, dq_ch=64, dk=p, dkst=None, dk_ch=64, dv=p, dvst=None, **shape,
+             stream=None)
+    assert rc(bwd, a, kq=None) == -1 and rc(bwd, a, delta=None) == -1
+    assert rc(bwd, a, qh=3) == -3 and rc(bwd, a, kn=0) == -3
+    assert rc(bwd, a, d=136, dq_ch=136, dk_ch=136) == -5 and rc(bwd, a, d=60, dq_ch=60, dk_ch=60) == -5
+    assert rc(bwd, a, v=p + 2) == -4 and rc(bwd, a, vst=bad) == -4
+    assert rc(bwd, a, mask=p, mask_dtype=5) == -2
+    assert rc(bwd, a, grad_dtype=5) == -2
+    assert rc(bwd, a, v_dtype=0) == -2                                 # f32 value operand
+    assert rc(bwd, a, d=40, dq_ch=48, dk_ch=40) == -3                  # dQ channels: neither head_dim nor the padded head dim
 
 
 def test_bf16_uint8_matmul_argument_validation_without_gpu():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The attention formats side by side (graph-replayed, whole call: prepare + forward): the default configuration on its tuned kernels against
-fp8 Q.K^T and the quantized P.V formats on the plain kernel of csrc/attention.hip (round 6), and torch's SDPA.  us per call."""
+fp8 Q.K^T and the quantized P.V formats on the plain kernel of csrc/attention_var.hip (round 6), and torch's SDPA.  us per call."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
