@@ -26,10 +26,16 @@
 
 namespace {
 
-// Tile geometries (template parameters BM x BN of the kernel; BK, the wave count and the 32x32 accumulator per wave are common):
-//   64 x 128, 4 ring slots : waves 2 x 4; a wave quantizes 8 rows in two passes; 16-KB weight stages; tiles_n workgroups repeat a row block
-//   32 x 256, 3 ring slots : waves 1 x 8; a wave quantizes 4 rows in one pass (half the ingest and the arithmetic in front of the K loop,
-//                            half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280
+// Tile geometries (template parameters BM x BN of the kernel and its ring depth; BK, the wave count and the 32x32 MFMA are common):
+//   0: 64 x 128, 4 ring slots : waves 2 x 4; a wave quantizes 8 rows in two passes; 16-KB weight stages; tiles_n workgroups repeat a row block
+//   1: 32 x 256, 3 ring slots : waves 1 x 8; a wave quantizes 4 rows in one pass (half the ingest and the arithmetic in front of the K loop,
+//                               half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280
+// and two "tall" forms for K <= 640 (five stages held) where the 64 x 128 tiles of a problem outnumber the CUs:
+//   2: 64 x 128, 2 ring slots : the tile of geometry 0 on a thin ring: 40 KB image + 32 KB ring, so TWO workgroups share a CU (the second
+//                               one hides the first one's stage waits, as in the two-launch GEMM's 3 slots x 2 workgroups) and
+//                               2 x CUs tiles are resident at once
+//   3: 128 x 128, 3 ring slots: waves 2 x 4 with TWO 32 x 32 accumulators each (rows 64 wm .. + 64); a wave quantizes 16 rows in four
+//                               passes; 80 KB image + 48 KB ring, one workgroup per CU, half the tiles
 constexpr int BK = 128, NW = 8, NT = NW * 64;
 
 struct AqParams {
@@ -82,11 +88,12 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     SDNQ_KERNARGS_NOW("s"(x), "s"(w), "s"(ldx), "s"(ldb), "s"(M), "s"(N), "s"(K), "s"(tiles_m), "s"(tiles_n), "s"(group_m));
     const AqParams& p = p_;
     typedef AqMma<MM> MT;
-    static_assert(BM % 32 == 0 && BN % 32 == 0 && (BM / 32) * (BN / 32) == NW, "one 32x32 accumulator per wave");
+    constexpr int NACC = (BM / 32) * (BN / 32) / NW;  // 32x32 accumulators of a wave: consecutive row blocks of one column block
+    static_assert(BM % 32 == 0 && BN % 32 == 0 && NACC * NW == (BM / 32) * (BN / 32) && NACC >= 1 && NACC <= 2, "one or two 32x32 accumulators per wave");
     constexpr int A_STAGE = BM * BK, B_STAGE = BN * BK;
     constexpr int PS = BM / (4 * NW);   // quantization passes of a wave: 4 rows (one per quarter wave) each
     constexpr int PPW = BN / (8 * NW);  // 1-KB ring pieces (8 weight rows) of a stage that one wave moves
-    static_assert(PS >= 1 && PS <= 2 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
+    static_assert(PS >= 1 && PS <= 4 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t* const ldsA = lds;                       // [NJ][BM rows][128 B] quantized activation rows, resident
     uint8_t* const ldsB = lds + NJ * A_STAGE;        // [NSB][BN rows][128 B] weight ring
@@ -160,8 +167,9 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps) {
         // loads return in order: a pass has landed when at most the NJ loads of each later pass and this wave's PPW AHEAD ring pieces are outstanding
-        if (ps == 0) wait_vmcnt<(PS - 1) * NJ + PPW * AHEAD>();
-        else wait_vmcnt<PPW * AHEAD>();
+        static_for_up<PS>([&](auto pc) {
+            if (decltype(pc)::value == ps) wait_vmcnt<(PS - 1 - decltype(pc)::value) * NJ + PPW * AHEAD>();
+        });
         // |x| of 16-bit floats orders like the unsigned integer of its low 15 bits: packed integer max, two elements per instruction
         us2 mx = {0, 0};
 #pragma unroll
@@ -238,10 +246,12 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     SDNQ_PHASE_STAMP(p.trace, 2);
 
     // ---- K loop: weight stages through the ring, activation fragments from the resident image ----------------------------------------
-    typename MT::acc_t acc;
+    typename MT::acc_t acc[NACC];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0;
-    const int wm = wave / (BN / 32), wn = wave % (BN / 32);
+    for (int a = 0; a < NACC; ++a)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[a][e] = 0;
+    const int wm = (wave / (BN / 32)) * NACC, wn = wave % (BN / 32);  // first 32-row block, 32-column block of the wave
     const int frow = lane & 31, fgrp = lane >> 5;
     constexpr int KS = BK / MT::KB;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's codes and scales are in LDS before the first barrier lets anyone read them
@@ -249,10 +259,11 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // registers when its barrier falls, so the MFMAs start at once; dealt out between them are the fragment reads of stage kt + 1 (which that
     // barrier published) and the DMA pieces of stage kt + NSB into the slot stage kt has just vacated -- NSB - 1 stages in flight behind the
     // landed one.  Two register sets, so the loop is unrolled by two.
-    typename MT::frag_t fa[2][KS], fb[2][KS];
+    typename MT::frag_t fa[2][NACC][KS], fb[2][KS];
     auto read_stage = [&](auto setc, auto ksc, int st, int slot) {
         constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
-        fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
         fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
     };
     wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
@@ -278,7 +289,10 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         // MFMA ks of stage kt, then read ks of stage kt + 1 (the last sub-step's reads retire under the next barrier's wait; KS <= 4)
         static_for_up<KS>([&](auto ksc) {
             constexpr int ks = decltype(ksc)::value;
-            if (!(lab & 4)) MT::mma(acc, fb[sx][ks], fa[sx][ks]);
+            if (!(lab & 4)) {
+#pragma unroll
+                for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fb[sx][ks], fa[sx][a][ks]);
+            }
             __builtin_amdgcn_sched_barrier(0);
             if (!(lab & 2)) read_stage(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1, slot_c);
             if constexpr (ks == 0) { if (!(lab & 1)) issueB(kt + NSB, slot_free); }
@@ -299,8 +313,9 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // out = cast(fma(f32(acc) * xs, ws, bias)) (kernel_wrappers.py:132-144); final 16-bit values leave through LDS as 16-byte row pieces
     constexpr int OUT_ROW = BN * 2 + 16;
     static_assert(BM * OUT_ROW <= NJ * A_STAGE + NSB * B_STAGE, "output staging fits the operand area");
-    {
-        const int ml = wm * 32 + frow;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+        const int ml = (wm + a) * 32 + frow;
         const float sa = s_xs[ml];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -308,7 +323,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
             float o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float vv = MT::tof(acc, 4 * q + e) * sa;
+                const float vv = MT::tof(acc[a], 4 * q + e) * sa;
                 if constexpr (HAS_BIAS) o[e] = fmaf(vv, s_sb[nl0 + e], s_bias[nl0 + e]);
                 else o[e] = vv * s_sb[nl0 + e];
             }
@@ -330,41 +345,61 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 }
 
 std::atomic<unsigned long long*> g_aq_trace{nullptr};
-std::atomic<int> g_aq_geometry{-1};  // tests / labs: -1 by shape, 0 = 64 x 128, 1 = 32 x 256
+std::atomic<int> g_aq_geometry{-1};  // tests / labs: -1 by shape, else a geometry id of the table above
 
-// The launcher's choices for one problem, in one place (tests/test_gemm_aq_plan.py holds the table this implements).
+constexpr int64_t AQ_TALL_MAX_K = 640;
+
+// The launcher's choices for one problem, in one place (tests/test_gemm_aq_plan.py and test_gemm_aq_plan_tall.py hold the table this implements).
 //   geometry 1 (32 x 256, 3 ring slots) where the front of the 64 x 128 tile -- ingest + quantization of 64 rows x K, repeated by every
 //   column tile -- outweighs its K loop: int8, K of more than 5 stages, N a multiple of 256 (no column tile half empty), and one round:
-//   at most one tile per CU.  Everything else keeps geometry 0 (64 x 128, 4 ring slots).
-struct AqPlan { int geometry, bm, bn, tiles_m, tiles_n, group_m; int64_t prefetch_room; };
+//   at most one tile per CU.
+//   a tall geometry (2 or 3: int8, K of at most 5 stages) where one round of 64 x 128 tiles, one per CU, does NOT cover the problem but
+//   one round of the tall form does: at most `resident` tiles per CU.
+//   Everything else keeps geometry 0 (64 x 128, 4 ring slots).
+// A forced tall geometry on a problem it has no instantiation for (fp8, K > 640) falls back to the shape rule.
+struct AqPlan { int geometry, bm, bn, tiles_m, tiles_n, group_m, resident; int64_t prefetch_room; };
 inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
     static const int geo_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GEOMETRY", -1);  // tuning aid
     static const int gm_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);     // tuning aid (1 = n fastest)
+    static const int gm_tall_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M_TALL", 8);  // the same for geometries 2 and 3
+    // the tall form the shape rule picks: 2 (3 lost in the step; the variable is how that was measured)
+    static const int tall = env_int("SDNQ_HIP_FUSED_ROWQUANT_TALL_GEOMETRY", 2) == 3 ? 3 : 2;
+    struct Geo { int bm, bn, resident; };
+    static constexpr Geo GEOS[4] = {{64, 128, 1}, {32, 256, 1}, {64, 128, 2}, {128, 128, 1}};
+    const bool tall_ok = mm_dtype == SDNQ_MM_I8 && k <= AQ_TALL_MAX_K;
+    auto tiles_of = [&](int g) { return ((m + GEOS[g].bm - 1) / GEOS[g].bm) * ((n + GEOS[g].bn - 1) / GEOS[g].bn); };
     int geo = g_aq_geometry.load(std::memory_order_relaxed);
     if (geo < 0) geo = geo_env;
-    if (geo < 0) geo = (mm_dtype == SDNQ_MM_I8 && k > 640 && (n % 256) == 0 && ((m + 31) / 32) * (n / 256) <= cus) ? 1 : 0;
+    if (geo > 3 || (geo >= 2 && !tall_ok)) geo = -1;
+    if (geo < 0) {
+        if (mm_dtype == SDNQ_MM_I8 && k > 640 && (n % 256) == 0 && ((m + 31) / 32) * (n / 256) <= cus) geo = 1;
+        else if (tall_ok && tiles_of(0) > cus && tiles_of(tall) <= (int64_t)GEOS[tall].resident * cus) geo = tall;
+        else geo = 0;
+    }
     AqPlan pl;
-    pl.geometry = geo ? 1 : 0;
-    pl.bm = geo ? 32 : 64;
-    pl.bn = geo ? 256 : 128;
+    pl.geometry = geo;
+    pl.bm = GEOS[geo].bm;
+    pl.bn = GEOS[geo].bn;
+    pl.resident = GEOS[geo].resident;
     pl.tiles_m = (int)((m + pl.bm - 1) / pl.bm);
     pl.tiles_n = (int)((n + pl.bn - 1) / pl.bn);
-    // the walk groups 8 row blocks in either geometry.  32 x 256 at 1024 x 1280 x 1280: a group is 40 tiles = the 20 of two XCDs, each
+    // the walk groups 8 row blocks in every geometry.  32 x 256 at 1024 x 1280 x 1280: a group is 40 tiles = the 20 of two XCDs, each
     // 8 row blocks x 2.5 weight blocks; in the step 8 blocks ran 7.02 ms, 16 (the same ROWS as 8 of 64) 7.08, 2 / 4 / 6 7.04
-    const int gm = gm_env < 1 ? 1 : gm_env;
+    const int gm_e = geo >= 2 ? gm_tall_env : gm_env;
+    const int gm = gm_e < 1 ? 1 : gm_e;
     pl.group_m = gm > pl.tiles_m ? pl.tiles_m : gm;
-    pl.prefetch_room = (int64_t)cus - (int64_t)pl.tiles_m * pl.tiles_n;  // one workgroup per CU in either geometry (LDS)
+    pl.prefetch_room = (int64_t)pl.resident * cus - (int64_t)pl.tiles_m * pl.tiles_n;  // workgroup slots (LDS) the tiles leave free
     return pl;
 }
 
-template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN>
+template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN, int RESIDENT = 1>
 int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, int64_t k, const AqPlan& pl, AqParams p, hipStream_t s) {
     constexpr int LDS_BYTES = NJ * BM * BK + NSB * BN * BK + (2 * BN + BM) * 4;
-    static_assert(LDS_BYTES <= 160 * 1024 && 2 * LDS_BYTES > 160 * 1024, "LDS budget: one workgroup per CU (aq_plan's prefetch room)");
+    static_assert(RESIDENT * LDS_BYTES <= 160 * 1024 && (RESIDENT + 1) * LDS_BYTES > 160 * 1024, "LDS budget: exactly RESIDENT workgroups per CU (aq_plan's prefetch room)");
     auto kern = linear_aq_kernel<X_T, MM, HAS_BIAS, NJ, NSB, BM, BN>;
     static std::atomic<uint64_t> attr_devices{0};
     if (LDS_BYTES > 64 * 1024 && !allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
-    if (pl.bm != BM || pl.bn != BN) return SDNQ_ERR_LAUNCH;
+    if (pl.bm != BM || pl.bn != BN || pl.resident != RESIDENT) return SDNQ_ERR_LAUNCH;
     const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, group_m = pl.group_m;
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     p.trace = g_aq_trace.load(std::memory_order_relaxed);
@@ -382,7 +417,9 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
 
 // which problems take the one-launch route.  Costs that grow with it: tiles_n workgroups repeat the quantization of a row block (VALU
 // time on the critical path of every tile), and a tile keeps its rows resident (K <= 1280).  Wins where the row-quantization launch
-// is a large part of the pair: the one-round projections of the bs = 1 steps.
+// is a large part of the pair: the one-round projections of the bs = 1 steps.  The rule: every tile of the problem resident at once --
+// at most one 64 x 128 tile per CU, or, where those outnumber the CUs, a problem that aq_plan gives a tall geometry (int8, K <= 640,
+// at most two co-resident tiles per CU: 4096 x 640 x 640 of the SDXL step).  A second round of tiles loses to the two launches.
 extern "C" int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, int out_dtype, int64_t m, int64_t n, int64_t k) {
     static const int64_t on = env_int("SDNQ_HIP_FUSED_ROWQUANT", 1), max_tn = env_int("SDNQ_HIP_FUSED_ROWQUANT_MAX_TILES_N", 12),
                          min_m = env_int("SDNQ_HIP_FUSED_ROWQUANT_MIN_M", 33), min_k = env_int("SDNQ_HIP_FUSED_ROWQUANT_MIN_K", 128),
@@ -396,7 +433,7 @@ extern "C" int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, i
     if (m < min_m || n <= 0 || (n % 8) != 0 || k <= 0 || (k % 128) != 0 || k > 1280) return 0;
     const int64_t tiles_m = (m + 63) / 64, tiles_n = (n + 127) / 128;  // (counted on the 64 x 128 tile, whichever geometry runs)
     if (tiles_n > max_tn || k < min_k || k > max_k) return 0;
-    if (tiles_m * tiles_n > (int64_t)cu_count()) return 0;  // one round, one workgroup per CU
+    if (tiles_m * tiles_n > (int64_t)cu_count() && aq_plan(mm_dtype, m, n, k, cu_count()).geometry < 2) return 0;  // one round
     return 1;
 }
 
@@ -409,29 +446,39 @@ extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dty
     if (bias && (bias_dtype < 0 || bias_dtype > 2)) return SDNQ_ERR_DTYPE;
     if (m <= 0 || n <= 0 || k <= 0 || ldx < k || (n % 8) != 0) return SDNQ_ERR_SHAPE;
     if ((k % 128) != 0 || k > 1280) return SDNQ_ERR_UNSUPPORTED;
-    if (m > 0x7fffffffll / 2 || n > 0x7fffffffll || ldx * 2 * 64 > 0x7fffffffll || k * 128 > 0x7fffffffll) return SDNQ_ERR_SHAPE;
+    if (m > 0x7fffffffll / 2 || n > 0x7fffffffll || ldx * 2 * 128 > 0x7fffffffll || k * 128 > 0x7fffffffll) return SDNQ_ERR_SHAPE;
     if (((uintptr_t)x % 16) || ((uintptr_t)b % 16) || ((uintptr_t)out % 16) || ((ldx * 2) % 16)) return SDNQ_ERR_ALIGN;
     AqParams p{};
     p.sb = sb; p.bias = bias; p.out = out; p.ldc = n; p.bias_dtype = bias_dtype;
     hipStream_t s = (hipStream_t)stream;
     const AqPlan pl = aq_plan(mm_dtype, m, n, k, cu_count());
-#define AQ_G(XT, MMV, HB, NJV) (pl.geometry ? launch_aq<XT, MMV, HB, NJV, 3, 32, 256>(x, b, ldx, m, n, k, pl, p, s) : launch_aq<XT, MMV, HB, NJV, 4, 64, 128>(x, b, ldx, m, n, k, pl, p, s))
+#define AQ_L(XT, MMV, HB, NJV, ...) launch_aq<XT, MMV, HB, NJV, __VA_ARGS__>(x, b, ldx, m, n, k, pl, p, s)
+#define AQ_G(XT, MMV, HB, NJV) (pl.geometry == 1 ? AQ_L(XT, MMV, HB, NJV, 3, 32, 256) : AQ_L(XT, MMV, HB, NJV, 4, 64, 128))
 #define AQ_NJ(XT, MMV, HB) (k <= 640 ? AQ_G(XT, MMV, HB, 5) : AQ_G(XT, MMV, HB, 10))
 #define AQ_B(XT, MMV) (bias ? AQ_NJ(XT, MMV, true) : AQ_NJ(XT, MMV, false))
 #define AQ_X(MMV) (x_dtype == SDNQ_BF16 ? AQ_B(SDNQ_BF16, MMV) : AQ_B(SDNQ_F16, MMV))
+    // the tall geometries: int8, five stages (aq_plan hands them out for nothing else)
+#define AQ_TB(XT, ...) (bias ? AQ_L(XT, SDNQ_MM_I8, true, 5, __VA_ARGS__) : AQ_L(XT, SDNQ_MM_I8, false, 5, __VA_ARGS__))
+#define AQ_T(...) (x_dtype == SDNQ_BF16 ? AQ_TB(SDNQ_BF16, __VA_ARGS__) : AQ_TB(SDNQ_F16, __VA_ARGS__))
+    if (pl.geometry == 2) return AQ_T(2, 64, 128, 2);
+    if (pl.geometry == 3) return AQ_T(3, 128, 128, 1);
     return mm_dtype == SDNQ_MM_I8 ? AQ_X(SDNQ_MM_I8) : AQ_X(SDNQ_MM_FP8);
+#undef AQ_T
+#undef AQ_TB
 #undef AQ_X
 #undef AQ_B
 #undef AQ_NJ
 #undef AQ_G
+#undef AQ_L
 }
 
 // lab: phase stamps of the one-launch Linear (device buffer of 1024 x 8 uint64, or null to stop).  A C++ symbol internal to the library
 // (tools/aq_lab.py binds its mangled name), not part of the C ABI of include/sdnq_hip.h
 void sdnq_internal_aq_trace(unsigned long long* device_buf) { g_aq_trace.store(device_buf, std::memory_order_relaxed); }
 
-// tests / labs: force the tile geometry of the one-launch Linear (-1 by shape, 0 = 64 x 128, 1 = 32 x 256); internal like the trace hook
-void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry ? 1 : 0), std::memory_order_relaxed); }
+// tests / labs: force the tile geometry of the one-launch Linear (-1 by shape, 0 = 64 x 128, 1 = 32 x 256, 2 = 64 x 128 on two ring
+// slots, 3 = 128 x 128; any other value = 1, as before the tall forms); internal like the trace hook
+void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry <= 3 ? geometry : 1), std::memory_order_relaxed); }
 
 // tests: what the launcher would choose for (mm_dtype, m, n, k) on a part with `cus` CUs:
 // out = {geometry, BM, BN, tiles_m, tiles_n, group_m, prefetch room}
