@@ -717,6 +717,23 @@ int sdnq_hip_attn_bwd(const void* qq, const float* qs, const void* kq, const flo
                       void* dv, const int64_t* dv_strides, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len,
                       int64_t kv_len, int64_t head_dim, sdnq_stream_t stream);
 
+/* ---- training Linear: column-wise int8 quantization with transposed codes ---------------------------------------------------------
+ * replaces quantize_int_mm(.., dim=0) (quant_utils.py:265-273) as the int8 training matmuls call it: on the weight of grad_input and on
+ * the flattened input of grad_weight (training/layers/linear/linear_int8/linear_int8_dynamic.py:27-28, linear_int8_dynamic_ckpt.py:22-26),
+ * and quantize_int_mm(grad_output.t(), dim=-1) of grad_weight, which is the same reduction over the rows of grad_output.
+ *     xs[c] = amax_r|x[r][c]| / 127 ;  xq_t[c][r] = int8(clamp(round_half_even(x[r][c] / xs[c]), -128, 127))
+ * in float32 with a correctly rounded division -- the arithmetic of sdnq_hip_rowquant, along the other axis.  A column whose amax is 0
+ * gets scale 0 and codes 0 (the reference casts a NaN there).
+ * x: [R][C] of x_dtype (SDNQ_F32 / SDNQ_BF16 / SDNQ_F16), row stride ldx elements, C % 8 == 0.  xq_t: [C] rows of ld_t bytes, ld_t >= R and
+ * ld_t % 16 == 0; bytes [R, ld_t) of every row are written as zeros, so xq_t is an operand of sdnq_hip_scaled_mm with k = ld_t for any R.
+ * xs: [C] f32.  colsum: optional [C] f32 = sum_r x[r][c] (grad_bias = grad_output.sum(dim=0), linear_int8_dynamic.py:153, before its
+ * rounding to the dtype), float32 accumulation in a fixed order: the same bits on every call; NULL to skip.
+ * workspace: sdnq_hip_colquant_t_workspace_bytes(r, c) bytes (< 0: SdnqStatus), 16-byte aligned, owned by the caller until the stream
+ * has run the call; a smaller one: SDNQ_ERR_SHAPE.  Two launches, no atomics. */
+int64_t sdnq_hip_colquant_t_workspace_bytes(int64_t r, int64_t c);
+int sdnq_hip_colquant_t(const void* x, int x_dtype, int64_t r, int64_t c, int64_t ldx, void* xq_t, int64_t ld_t, float* xs, float* colsum,
+                        void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

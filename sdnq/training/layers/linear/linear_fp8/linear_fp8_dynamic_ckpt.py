@@ -1,0 +1,2 @@
+"""sdnq.training.layers.linear.linear_fp8.linear_fp8_dynamic_ckpt of the import-name drop-in: not built, the name raises NotImplementedError."""
+from sdnq_amd.training import fp8_matmul_dynamic_with_backward_ckpt  # noqa: F401

@@ -1,0 +1,1 @@
+"""sdnq.training.layers.linear.linear_uint8 of the import-name drop-in (see sdnq/training/__init__.py)."""

@@ -53,6 +53,7 @@ UNITS = (
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_var", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_bwd", "", None),
+    ("colquant", "", None),
     ("parallel", "", None),
 )
 

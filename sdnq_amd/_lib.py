@@ -38,6 +38,7 @@ EXPORTS = [
     "sdnq_hip_scaled_mm_tile", "sdnq_hip_lut4_build", "sdnq_hip_scaled_mm_w4", "sdnq_hip_scaled_mm_w4_supported",
     "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding", "sdnq_hip_quantize_codebook",
     "sdnq_hip_dequant_loss", "sdnq_hip_dequant_loss_workspace_bytes", "sdnq_hip_attn_lse", "sdnq_hip_attn_bwd",
+    "sdnq_hip_colquant_t", "sdnq_hip_colquant_t_workspace_bytes",
 ]
 
 
@@ -181,10 +182,13 @@ def _declare(lib):
     lib.sdnq_hip_scaled_mm_w4_supported.argtypes = [i32, i32, i64, i64, i64]
     lib.sdnq_hip_rowquant_f16.argtypes = [vp, i32, i64, i64, i64, vp, vp, vp]
     lib.sdnq_hip_scaled_mm_f16.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, vp, i32, i64, i64, i64, vp]
+    lib.sdnq_hip_colquant_t.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, vp, vp, i64, vp]
+    lib.sdnq_hip_colquant_t_workspace_bytes.argtypes = [i64, i64]
     for name in EXPORTS:
         if name not in ("sdnq_hip_strerror", "sdnq_hip_set_tile_override"):
             getattr(lib, name).restype = c.c_int
     lib.sdnq_hip_attn_workspace_bytes.restype = c.c_int64
+    lib.sdnq_hip_colquant_t_workspace_bytes.restype = c.c_int64
 
 
 def load():

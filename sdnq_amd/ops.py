@@ -207,6 +207,27 @@ def rowquant(x2d: torch.Tensor, mm: int, hadamard_group: int = 0, want_rowsum: b
     return xq, xs, rowsum, xrot
 
 
+def colquant_t(x2d: torch.Tensor, want_colsum: bool = False):
+    """sdnq_hip_colquant_t: int8-quantize x2d [R,C] per COLUMN and return the codes transposed -- (xq_t [C, ld_t] int8 with
+    ld_t = R rounded up to 16 and columns [R, ld_t) zero, xs [C,1] f32, colsum [C] f32 | None): the operand of a scaled matmul that
+    reduces over the rows of x2d (the int8 training Linear's grad_input and grad_weight)."""
+    _require_cuda(x2d)
+    assert x2d.ndim == 2 and x2d.stride(1) == 1
+    r, c = x2d.shape
+    lib = _lib.load()
+    nbytes = lib.sdnq_hip_colquant_t_workspace_bytes(r, c)
+    if nbytes < 0:
+        check(int(nbytes), "colquant_t")
+    ld_t = (r + 15) // 16 * 16
+    xq_t = torch.empty((c, ld_t), device=x2d.device, dtype=torch.int8)
+    xs = torch.empty((c, 1), device=x2d.device, dtype=torch.float32)
+    colsum = torch.empty((c,), device=x2d.device, dtype=torch.float32) if want_colsum else None
+    ws = torch.empty((nbytes,), device=x2d.device, dtype=torch.uint8)  # stream-ordered reuse by the caching allocator
+    check(lib.sdnq_hip_colquant_t(x2d.data_ptr(), float_code(x2d.dtype), r, c, x2d.stride(0), xq_t.data_ptr(), ld_t, xs.data_ptr(),
+                                  _ptr(colsum), ws.data_ptr(), nbytes, _stream(x2d)), "colquant_t")
+    return xq_t, xs, colsum
+
+
 def rowquant_lp(x2d: torch.Tensor, mm: int, hadamard_group: int = 0, want_rowsum: bool = False, want_xrot: bool = False):
     """sdnq_hip_rowquant_lp: the activation quantization carried out in x2d's own 16-bit dtype (dequantize_fp32=False layers).
     Returns (xq, xs [M,1] f32 holding dtype-representable values, rowsum | None, xrot | None)."""
