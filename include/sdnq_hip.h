@@ -734,6 +734,35 @@ int64_t sdnq_hip_colquant_t_workspace_bytes(int64_t r, int64_t c);
 int sdnq_hip_colquant_t(const void* x, int x_dtype, int64_t r, int64_t c, int64_t ldx, void* xq_t, int64_t ld_t, float* xs, float* colsum,
                         void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* ---- optimizer: the fused AdamW step ------------------------------------------------------------------------------------------------
+ * replaces, for one parameter tensor, the chain SDNQOptimizer.step runs for AdamW (optim/optimizer.py:97-139): get_param_grad
+ * (optim/utils.py:26-43), adam_update with its two lerp_buffer_stochastic_ (optim/adamw.py:54-73, optim/utils.py:120-135),
+ * apply_norm_to_update_ in the modes "none" and "clip" (optim/utils.py:139-151), update_param_ without Kahan sum and caution
+ * (optim/utils.py:47-91) and copy_stochastic_ (optim/utils.py:95-116).  In float32, in the reference's order of operations:
+ *     g = clamp(nan_to_num(grad) / *grad_scale, -clip, clip) ;  m = lerp(m, g, w1) ;  v = lerp(v, g * g, w2)          (w = 1 - beta)
+ *     u = clamp(nan_to_num((m / bc1) * rsqrt(v / bc2)), -clip, clip)                                                  (bc = 1 - beta^step)
+ *     p = nan_to_num(param) * decay + (-lr) * u                                                  (decay = 1 - lr * weight_decay, or 1)
+ * and param, m, v are rounded to their storage.  The caller computes w1, w2, bc1, bc2 and decay in double and passes their float
+ * values, as torch does with a Python scalar.  grad_scale: one float32 in device memory, or NULL (no division).
+ * sdnq_hip_adamw_step: param, grad, exp_avg, exp_avg_sq are `numel` contiguous elements of `dtype` (SDNQ_F32 / SDNQ_BF16 / SDNQ_F16),
+ *   16-byte aligned; any numel > 0.  sr_param / sr_state: round the 16-bit parameter / state stochastically (copy_stochastic_'s bit
+ *   trick) instead of to nearest even; ignored for float32.
+ * sdnq_hip_adamw_step_q8: the state is uint8 codes with a float32 scale and zero point per 32 consecutive elements (numel % 32 == 0)
+ *   -- what SDNQTensor.from_float(.., weights_dtype="uint8", group_size=32) holds for a tensor whose last dimension is a multiple of
+ *   32 (quantizer.py:186-219, quant_utils.py:10-19, 28-56) and what sdnq_hip_quantize_weight writes for it: codes [numel],
+ *   scale / zero point [numel / 32].  The state is dequantized (dequantizer.py: addcmul(zero_point, q, scale)), updated and quantized
+ *   again inside the launch; sr_state adds 0.1 * a standard normal to the quotient before it is rounded
+ *   (quantize_weight(use_stochastic_rounding=True)).  A group whose values are all equal gets scale 0 and codes 0.
+ * Random numbers come from Philox4x32-10 keyed by `seed`, with the counter (element index / 8, stream, offset): for one (seed, offset)
+ * the result is a function of the element index alone.  One launch each, no workspace, no atomics; the same bits on every call. */
+int sdnq_hip_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int dtype, int64_t numel, float lr, float w1,
+                        float w2, float bc1, float bc2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
+                        uint64_t seed, uint64_t offset, sdnq_stream_t stream);
+int sdnq_hip_adamw_step_q8(void* param, const void* grad, int dtype, int64_t numel, void* exp_avg_q, float* exp_avg_scale,
+                           float* exp_avg_zp, void* exp_avg_sq_q, float* exp_avg_sq_scale, float* exp_avg_sq_zp, float lr, float w1,
+                           float w2, float bc1, float bc2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
+                           uint64_t seed, uint64_t offset, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

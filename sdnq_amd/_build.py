@@ -54,6 +54,7 @@ UNITS = (
     ("attention_var", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_bwd", "", None),
     ("colquant", "", None),
+    ("optim", "", None),
     ("parallel", "", None),
 )
 

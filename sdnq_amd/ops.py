@@ -1121,3 +1121,55 @@ def quantize_weight(weight2d: torch.Tensor, weights_dtype: str, group_size: int,
     else:
         codes = raw.view(ent["torch_dtype"]) if ent["torch_dtype"].itemsize == raw.element_size() else raw
     return codes, scale, zp
+
+
+def _adamw_tail(p: torch.Tensor, lr, betas, step, weight_decay, clip, grad_scale, sr_param, sr_state, seed, offset):
+    """The scalar arguments the two AdamW entry points share: Python doubles here, rounded to float32 by the binding, as torch
+    rounds a Python scalar that meets a float32 tensor."""
+    b1, b2 = betas
+    decay = 1.0 - lr * weight_decay if weight_decay != 0 else 1.0
+    return (float(lr), 1.0 - b1, 1.0 - b2, 1.0 - b1 ** step, 1.0 - b2 ** step, float(clip), decay, _ptr(grad_scale),
+            int(bool(sr_param)), int(bool(sr_state)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _stream(p))
+
+
+def _adamw_check(p: torch.Tensor, g: torch.Tensor, grad_scale) -> None:
+    _require_cuda(p, g, grad_scale)
+    if g.dtype != p.dtype or g.shape != p.shape:
+        raise _lib.SdnqHipError(f"adamw_step: grad must have the parameter's dtype and shape (got {g.dtype} {tuple(g.shape)} for "
+                                f"{p.dtype} {tuple(p.shape)})")
+    if not p.is_contiguous() or not g.is_contiguous():
+        raise _lib.SdnqHipError("adamw_step: param and grad must be contiguous")
+    if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1):
+        raise _lib.SdnqHipError("adamw_step: grad_scale must be one float32 element on the device")
+
+
+def adamw_step(p: torch.Tensor, g: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *, step: int, lr: float,
+               betas=(0.9, 0.999), weight_decay: float = 0.01, clip: float = 1.0, grad_scale: torch.Tensor | None = None,
+               sr_param: bool = False, sr_state: bool = False, seed: int = 0, offset: int = 0) -> None:
+    """sdnq_hip_adamw_step: one fused AdamW update of `p` in place, with dense state in p's dtype.  `step` counts from 1."""
+    _adamw_check(p, g, grad_scale)
+    for t in (exp_avg, exp_avg_sq):
+        _require_cuda(t)
+        if t.dtype != p.dtype or t.numel() != p.numel() or not t.is_contiguous():
+            raise _lib.SdnqHipError("adamw_step: dense state must be contiguous, of the parameter's dtype and size")
+    check(_lib.load().sdnq_hip_adamw_step(p.data_ptr(), g.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float_code(p.dtype),
+                                          p.numel(), *_adamw_tail(p, lr, betas, step, weight_decay, clip, grad_scale, sr_param,
+                                                                  sr_state, seed, offset)), "adamw_step")
+
+
+def adamw_step_q8(p: torch.Tensor, g: torch.Tensor, exp_avg, exp_avg_sq, *, step: int, lr: float, betas=(0.9, 0.999),
+                  weight_decay: float = 0.01, clip: float = 1.0, grad_scale: torch.Tensor | None = None, sr_param: bool = False,
+                  sr_state: bool = False, seed: int = 0, offset: int = 0) -> None:
+    """sdnq_hip_adamw_step_q8: the same with uint8 state; exp_avg / exp_avg_sq are (codes uint8 [numel], scale f32 [numel / 32],
+    zero_point f32 [numel / 32]) triples, updated in place."""
+    _adamw_check(p, g, grad_scale)
+    ptrs = []
+    for q, s, z in (exp_avg, exp_avg_sq):
+        _require_cuda(q, s, z)
+        if (q.dtype != torch.uint8 or q.numel() != p.numel() or s.dtype != torch.float32 or z.dtype != torch.float32
+                or s.numel() * 32 != p.numel() or z.numel() != s.numel() or not (q.is_contiguous() and s.is_contiguous() and z.is_contiguous())):
+            raise _lib.SdnqHipError("adamw_step_q8: state must be contiguous uint8 codes [numel] with float32 scale and zero point [numel / 32]")
+        ptrs += [q.data_ptr(), s.data_ptr(), z.data_ptr()]
+    check(_lib.load().sdnq_hip_adamw_step_q8(p.data_ptr(), g.data_ptr(), float_code(p.dtype), p.numel(), *ptrs,
+                                             *_adamw_tail(p, lr, betas, step, weight_decay, clip, grad_scale, sr_param, sr_state,
+                                                          seed, offset)), "adamw_step_q8")
