@@ -41,11 +41,14 @@ UNITS = (
     ("rowquant", "-DSDNQ_PRELOAD_ROWQUANT " + _PRELOAD, "SDNQ_PRELOAD_ROWQUANT"),
     # gemm.hip: the same for the GEMM kernel's 14 leading scalar arguments (tile mapping, operand descriptors, prologue DMAs)
     ("gemm", "-DSDNQ_PRELOAD_GEMM " + _PRELOAD, "SDNQ_PRELOAD_GEMM"),
-    # the other kernels with scalar arguments (lowrank_down, linear_float, conv_pixel_amax, ...) get theirs preloaded as well
+    # the other kernels with scalar arguments get theirs preloaded as well: the GEMM variants, the weight-side units (dequant.hip's
+    # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax, ...
     ("gemm_aq", _PRELOAD, None),
     ("gemm_ks", _PRELOAD, None),
     ("gemm_w4", _PRELOAD, None),
     ("dequant", _PRELOAD, None),
+    ("skinny", _PRELOAD, None),
+    ("linear_float", _PRELOAD, None),
     ("quantize", "", None),
     ("conv", _PRELOAD, None),
     # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them

@@ -2319,9 +2319,9 @@ extern "C" int sdnq_hip_scaled_mm_f16(const void* a, const void* b, const float*
 #undef F16S_EPI
 }
 
-// internal (used by sdnq_hip_linear_float in dequant.hip): out[M][N] = cast(x[M][K] . w[N][K]^T + bias), all of `dtype`
+// internal (gemm_dev.h; used by sdnq_hip_linear_float in linear_float.hip): out[M][N] = cast(x[M][K] . w[N][K]^T + bias), all of `dtype`
 int sdnq_float_gemm(const void* x, const void* w, const void* bias, int dtype, void* out, int64_t m, int64_t n, int64_t k,
-                    int64_t ldx, hipStream_t s, void* const* outs = nullptr, int n_outs = 0, int64_t seg_n = 0, int64_t ldc = 0) {
+                    int64_t ldx, hipStream_t s, void* const* outs, int n_outs, int64_t seg_n, int64_t ldc) {
     const int eb = (dtype == SDNQ_F32) ? 4 : 2;
     GemmParams p{};
     p.ldc = ldc;

@@ -258,3 +258,13 @@ __device__ __forceinline__ v4f had256_group(const uint2& raw, const float (&hf)[
     return y;
 }
 
+
+// host: the rule every entry point with a `hadamard_group` applies.  log2 of the group, 0 for no rotation (group 0), -1 for a group that
+// is not a power of two in 4..512 or does not divide k
+static inline int hadamard_log2(int group, int64_t k) {
+    if (group == 0) return 0;
+    if (group < 4 || group > 512 || (group & (group - 1)) || (k % group) != 0) return -1;
+    int log2g = 2;
+    while ((1 << log2g) < group) ++log2g;
+    return log2g;
+}

@@ -483,12 +483,6 @@ __global__ __launch_bounds__(256) void hadamard_kernel(const void* __restrict__ 
     }
 }
 
-int ilog2(int64_t v) {
-    int l = 0;
-    while ((1LL << l) < v) ++l;
-    return l;
-}
-
 }  // namespace
 
 extern "C" int sdnq_hip_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int mm_dtype,
@@ -501,14 +495,9 @@ extern "C" int sdnq_hip_rowquant(const void* x, int x_dtype, int64_t m, int64_t 
     if (x_dtype < 0 || x_dtype > 2) return SDNQ_ERR_DTYPE;
     const int eb = (x_dtype == SDNQ_F32) ? 4 : 2;
     if (((uintptr_t)x % 16) || ((ldx * eb) % 16) || ((uintptr_t)xq % 8)) return SDNQ_ERR_ALIGN;
-    int log2g = 0;
-    if (hadamard_group != 0) {
-        log2g = ilog2(hadamard_group);
-        if ((1 << log2g) != hadamard_group || hadamard_group < 4 || hadamard_group > 512 || (k % hadamard_group) != 0)
-            return SDNQ_ERR_SHAPE;
-        if (hadamard_group < 8 && false) return SDNQ_ERR_UNSUPPORTED;
-        if (xrot && ((uintptr_t)xrot % 16)) return SDNQ_ERR_ALIGN;
-    }
+    const int log2g = hadamard_log2(hadamard_group, k);
+    if (log2g < 0) return SDNQ_ERR_SHAPE;
+    if (log2g && xrot && ((uintptr_t)xrot % 16)) return SDNQ_ERR_ALIGN;
     if (rowsum && mm_dtype != SDNQ_MM_I8) return SDNQ_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     static const int had_mfma = [] { const char* e = getenv("SDNQ_HIP_HADAMARD_MFMA"); return e ? atoi(e) : 1; }();  // 0: always the FWHT (A/B aid)
@@ -602,13 +591,9 @@ static int rowquant_lp_impl(const void* x, int x_dtype, int64_t m, int64_t k, in
     if (mm_dtype != SDNQ_MM_I8 && mm_dtype != SDNQ_MM_FP8) return SDNQ_ERR_DTYPE;
     if (x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;  // float32 scales: sdnq_hip_rowquant
     if (((uintptr_t)x % 16) || ((ldx * 2) % 16) || ((uintptr_t)xq % 8)) return SDNQ_ERR_ALIGN;
-    int log2g = 0;
-    if (hadamard_group != 0) {
-        log2g = ilog2(hadamard_group);
-        if ((1 << log2g) != hadamard_group || hadamard_group < 4 || hadamard_group > 512 || (k % hadamard_group) != 0)
-            return SDNQ_ERR_SHAPE;
-        if (xrot && ((uintptr_t)xrot % 16)) return SDNQ_ERR_ALIGN;
-    }
+    const int log2g = hadamard_log2(hadamard_group, k);
+    if (log2g < 0) return SDNQ_ERR_SHAPE;
+    if (log2g && xrot && ((uintptr_t)xrot % 16)) return SDNQ_ERR_ALIGN;
     if (rowsum && mm_dtype != SDNQ_MM_I8) return SDNQ_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int row_blocks = (int)((m + 3) / 4);
@@ -696,9 +681,8 @@ extern "C" int sdnq_hip_hadamard(const void* x, int dtype, int64_t rows, int64_t
     if (!x || !y) return SDNQ_ERR_NULL;
     if (rows <= 0 || k <= 0 || (k % 8) != 0 || ldx < k || ldy < k) return SDNQ_ERR_SHAPE;
     if (dtype < 0 || dtype > 2) return SDNQ_ERR_DTYPE;
-    const int log2g = ilog2(hadamard_group);
-    if ((1 << log2g) != hadamard_group || hadamard_group < 4 || hadamard_group > 512 || (k % hadamard_group) != 0)
-        return SDNQ_ERR_SHAPE;
+    const int log2g = hadamard_log2(hadamard_group, k);
+    if (log2g <= 0) return SDNQ_ERR_SHAPE;  // a rotation is what was asked for: group 0 is no group
     const int eb = (dtype == SDNQ_F32) ? 4 : 2;
     if (((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((ldx * eb) % 16) || ((ldy * eb) % 16)) return SDNQ_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;

@@ -80,6 +80,75 @@ def test_argument_validation_without_gpu():
     assert lfs(p, p, None, 1, p, 40, 32, 32, 16, 32, None) == -3                                   # ldx < K
 
 
+def test_weight_side_argument_validation_without_gpu():
+    """The entry points on an SdnqWeight (dequant.hip, skinny.hip) validate before any launch; every value below is the status the
+    library returned before these entry points were moved into units of their own."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(4096)
+    p = ctypes.addressof(buf)
+    p += (-p) % 16
+
+    keep = []  # the structs, alive until the test ends (sdnq_hip_embedding takes the address as an integer)
+
+    def weight(**kw):
+        f = dict(weight=p, scale=p, zero_point=None, svd_up=None, svd_down=None, n=16, k=64, group_size=64, svd_rank=0, svd_dtype=0,
+                 storage=0, kind=0, bits=4, exponent=0, mantissa=0, native_float=0)   # packed int4, one group per row
+        f.update(kw)
+        keep.append(_lib.SdnqWeight(**f))
+        return ctypes.byref(keep[-1])
+
+    int8 = dict(storage=2, bits=8)
+    svd = dict(svd_up=p, svd_down=p, svd_rank=32, svd_dtype=1)
+    sk = lib.sdnq_hip_linear_skinny
+    assert sk(weight(), 0, None, None, 1, p, 1, 64, None) == -1                        # NULL x
+    assert sk(weight(), 0, p, None, 7, p, 1, 64, None) == -2                           # dtype
+    assert sk(weight(), 0, p, None, 1, p, 0, 64, None) == -3                           # m = 0
+    assert sk(weight(), 0, p, None, 1, p, 65, 64, None) == -3                          # m > 64
+    assert sk(weight(), 0, p, None, 1, p, 1, 32, None) == -3                           # ldx < K
+    assert sk(weight(**svd), 0, p, None, 1, p, 1, 64, None) == -5                      # SVD factors
+    assert sk(weight(), 48, p, None, 1, p, 1, 64, None) == -3                          # Hadamard group not a power of two
+    assert sk(weight(), 1024, p, None, 1, p, 1, 64, None) == -3                        # Hadamard group > 512
+    assert sk(weight(k=96, group_size=32), 64, p, None, 1, p, 1, 96, None) == -3       # Hadamard group does not divide K
+    assert sk(weight(), 0, p + 2, None, 1, p, 1, 64, None) == -4                       # misaligned x
+    ss = lib.sdnq_hip_linear_skinny_svd
+    assert ss(weight(**int8, **svd), None, p, None, 1, p, 1, 64, None) == -1           # NULL svd_down_t
+    assert ss(weight(**int8, **svd), p, p, None, 0, p, 1, 64, None) == -2              # float32 activations
+    assert ss(weight(**int8, **svd), p, p, None, 2, p, 1, 64, None) == -2              # svd_dtype != dtype
+    assert ss(weight(bits=6, **svd), p, p, None, 1, p, 1, 64, None) == -5              # packed 6-bit codes
+    assert ss(weight(**int8, **svd), p, p, None, 1, p, 5, 64, None) == -3              # m > 4
+    assert ss(weight(k=48, group_size=48, **int8, **svd), p, p, None, 1, p, 1, 48, None) == -3   # K % 32
+    assert ss(weight(**int8, **dict(svd, svd_rank=24)), p, p, None, 1, p, 1, 64, None) == -3     # rank % 16
+    assert ss(weight(**int8, **svd), p + 2, p, None, 1, p, 1, 64, None) == -4          # misaligned svd_down_t
+    assert lib.sdnq_hip_requant(weight(**int8), 0, None, p, None) == -1                # NULL output
+    assert lib.sdnq_hip_requant(weight(**int8), 0, p + 4, p, None) == -4               # misaligned wq
+    assert lib.sdnq_hip_requant(weight(**int8), 5, p, p, None) == -2                   # mm dtype
+    assert lib.sdnq_hip_requant_ws(weight(**int8), 0, None, p, 0, None) == -1
+    assert lib.sdnq_hip_requant_ws(weight(**int8), 0, p + 4, p, 0, None) == -4
+    assert lib.sdnq_hip_requant_ws(weight(**int8), 5, p, p, 1, None) == -2
+    assert lib.sdnq_hip_requant_asym(weight(**int8), None, p, p, None) == -1
+    assert lib.sdnq_hip_requant_asym(weight(**int8), p + 4, p, p, None) == -4
+    assert lib.sdnq_hip_lut4_build(weight(), 0, p, 0, None, None) == -1                # NULL lut
+    assert lib.sdnq_hip_lut4_build(weight(**int8), 0, p, 0, p, None) == -5             # tables exist for packed 4-bit codes only
+    fp8 = dict(storage=2, kind=2, bits=8, native_float=1)
+    assert lib.sdnq_hip_unpack_mm(weight(**fp8), 0, p, None) == -2                     # int8 operand from float codes
+    assert lib.sdnq_hip_unpack_mm(weight(**int8), 1, p, None) == -2                    # fp8 operand from integer codes
+    assert lib.sdnq_hip_unpack_mm(weight(**int8), 2, p, None) == -2                    # float16 operand from integer codes
+    assert lib.sdnq_hip_unpack_mm(weight(**int8), 7, p, None) == -2                    # mm dtype
+    emb = lib.sdnq_hip_embedding
+    addr = lambda ref: ctypes.addressof(ref._obj)
+    assert emb(addr(weight(positions=2, group_size=32)), 0, p, 1, 4, 0, 1.0, p, 1, None) == -3   # conv weight
+    assert emb(addr(weight()), 0, p, 5, 4, 0, 1.0, p, 1, None) == -2                   # ids dtype
+    assert emb(addr(weight()), 0, p, 1, -1, 0, 1.0, p, 1, None) == -3                  # n_ids < 0
+    assert emb(addr(weight()), 48, p, 1, 4, 0, 1.0, p, 1, None) == -3                  # Hadamard group
+    assert emb(addr(weight()), 0, p, 1, 0, 0, 1.0, p, 1, None) == 0                    # nothing to gather: no launch
+    loss = lib.sdnq_hip_dequant_loss
+    assert loss(weight(), 0, p, 1, 32, p, p, 4096, None) == -3                         # ld_ref < K
+    assert loss(weight(), 0, p, 1, 64, p, p, 8, None) == -8                            # workspace of 1 partial, 4 workgroups
+    assert loss(weight(), 0, p + 2, 1, 64, p, p, 4096, None) == -4                     # misaligned ref
+    assert lib.sdnq_hip_dequant_loss_workspace_bytes(0, 64) == -3
+    assert lib.sdnq_hip_dequant_loss_workspace_bytes(16, 64) == 32                     # one double per workgroup
+
+
 def test_prefetch_argument_validation_without_gpu():
     lib = _lib.load()
     buf = ctypes.create_string_buffer(4096)

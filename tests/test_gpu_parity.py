@@ -472,7 +472,7 @@ def test_accelerate_repoints_a_foreign_module(gpu_device):
 
 @pytest.mark.parametrize("wdt,gs", [("int8", -1), ("int4", 32), ("uint4", 64), ("int6", 32), ("uint2", 16), ("int3", 32), ("fp8", -1),
                                     ("float6_e3m2fn", 32), ("uint7", 128), ("int5", -1)])
-@pytest.mark.parametrize("m", [1, 5, 32])
+@pytest.mark.parametrize("m", [1, 2, 3, 5, 32])  # every rows-per-launch bucket of the generic (1 / 2 / 4 / 8) and the fast kernel (1 / 2 / 4)
 def test_fused_skinny_matches_dequant_then_linear(wdt, gs, m, gpu_device):
     """M <= 32: the fused unpack+scale+GEMV kernel equals dequantize -> float linear (dequantizer.py:204 + F.linear)."""
     import sdnq_amd
