@@ -12,6 +12,15 @@ floating-point GEMMs (Hadamard, SVD, fp8, bf16 linear), whose summation order is
 
 Conventions: float tensors are float32 ndarrays holding values representable in the tagged dtype
 ("f32" | "bf16" | "f16"); weights/scales are ndarrays in the reference's LOGICAL state_dict layouts.
+
+The AdamW step of sdnq_amd.optim (adamw_step, adamw_step_q8 and the stochastic stores at the end of this file; pinned bit for bit to
+tests/golden/optim_adamw_* by tests/test_optim_oracle.py).  Which random word serves which element -- the contract in the header of csrc/optim.hip, restated:
+
+  Philox4x32-10 with key (seed low, seed high) and counter (e8 low, e8 high | stream << 28, offset low, offset high), e8 = element
+  index // 8.  Streams: 0 the parameter, 1 exp_avg, 2 exp_avg_sq.
+  16-bit stochastic rounding: element e (0..7) of the eight takes half e & 1 (0: the low 16 bits) of word e >> 1 of its stream's call.
+  uint8 state: eight words -- words 0-3 from stream 1 (exp_avg) or 2 (exp_avg_sq), words 4-7 from stream 3 or 4; pair (w[2i], w[2i+1])
+  serves elements 2i (cosine) and 2i + 1 (sine) of the eight through Box-Muller on 24-bit uniforms.
 """
 from __future__ import annotations
 
@@ -97,6 +106,10 @@ def lib():
         L.orc_scaled_mm_fp8.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]
         L.orc_linear_float.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp]
         L.orc_lowrank_bias.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp]
+        L.orc_adamw_step.argtypes = [vp] * 4 + [i64, i32] + [f32] * 7 + [vp] * 6
+        L.orc_adamw_step_q8.argtypes = [vp] * 8 + [i64, i32] + [f32] * 7 + [vp] * 12
+        L.orc_philox4x32_10.argtypes = [vp, vp, i64, vp]
+        L.orc_stochastic_codes.argtypes = [vp, vp, i64, vp, vp, vp, vp]
         L.orc_num_threads.restype = i32
         L.orc_set_num_threads.argtypes = [i32]
         _lib = L
@@ -1087,3 +1100,109 @@ def attention(q: np.ndarray, k: np.ndarray, v: np.ndarray, tag: str, is_causal: 
     if want_intermediates:
         return out, dict(q_q=qq, q_scale=qs, k_q=kq, k_scale=ks, v_q=vals["v_q"], v_scale=vals["v_scale"])
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the AdamW step of sdnq_amd.optim (csrc/optim.hip): the float32 chain, the random bits, the two stochastic stores
+# ------------------------------------------------------------------------------------------------
+SR_STEP = {"bf16": 1 << 16, "f16": 1 << 13}
+_FMAX = {"f32": float(np.finfo(np.float32).max), "bf16": float(np.uint32(0x7f7f0000).view(np.float32)), "f16": 65504.0}
+
+
+def adamw_scalars(step: int, lr: float, betas=(0.9, 0.999), weight_decay: float = 0.01, clip: float = 1.0):
+    """(lr, 1 - beta1, 1 - beta2, 1 - beta1^t, 1 - beta2^t, clip, decay): the Python doubles sdnq_amd.ops._adamw_tail passes; ctypes
+    rounds each to float32 (to nearest), as the binding of the kernel does."""
+    b1, b2 = betas
+    decay = 1.0 - lr * weight_decay if weight_decay != 0 else 1.0
+    return (float(lr), 1.0 - b1, 1.0 - b2, 1.0 - b1 ** step, 1.0 - b2 ** step, float(clip), decay)
+
+
+def _gs(grad_scale):
+    return None if grad_scale is None else np.array([grad_scale], dtype=np.float32)
+
+
+def adamw_step(p, g, exp_avg, exp_avg_sq, tag: str, *, step: int, lr: float, betas=(0.9, 0.999), weight_decay: float = 0.01,
+               clip: float = 1.0, grad_scale=None) -> dict:
+    """One AdamW step with dense state.  Inputs: float32 arrays holding values of `tag`.  Returns the UNROUNDED float32 "p", "exp_avg",
+    "exp_avg_sq", the update "u" and "u_raw" (u in front of its clamp); round_dtype / stochastic_round_bits give what is stored."""
+    p, g, m, v = (_c(a, np.float32).reshape(-1) for a in (p, g, exp_avg, exp_avg_sq))
+    out = {k: np.empty_like(p) for k in ("p", "exp_avg", "exp_avg_sq", "u", "u_raw")}
+    gs = _gs(grad_scale)
+    lib().orc_adamw_step(_p(p), _p(g), _p(m), _p(v), p.size, _DT[tag], *adamw_scalars(step, lr, betas, weight_decay, clip), _p(gs),
+                         *(_p(out[k]) for k in ("p", "exp_avg", "exp_avg_sq", "u", "u_raw")))
+    return out
+
+
+def adamw_step_q8(p, g, exp_avg, exp_avg_sq, tag: str, *, step: int, lr: float, betas=(0.9, 0.999), weight_decay: float = 0.01,
+                  clip: float = 1.0, grad_scale=None) -> dict:
+    """The same with uint8 state: exp_avg / exp_avg_sq are (codes uint8 [numel], scale f32 [numel / 32], zero point f32 [numel / 32]).
+    Returns what adamw_step returns (the float32 state in front of its quantization) and the new "exp_avg_q", "exp_avg_scale",
+    "exp_avg_zp" (and the same with exp_avg_sq): deterministic codes, a group with scale 0 has codes 0."""
+    p, g = (_c(a, np.float32).reshape(-1) for a in (p, g))
+    n = p.size
+    st = [(_c(q, np.uint8).reshape(-1), _c(s, np.float32).reshape(-1), _c(z, np.float32).reshape(-1)) for q, s, z in (exp_avg, exp_avg_sq)]
+    assert n % 32 == 0 and all(q.size == n and s.size == n // 32 and z.size == n // 32 for q, s, z in st)
+    out = {k: np.empty_like(p) for k in ("p", "exp_avg", "exp_avg_sq", "u", "u_raw")}
+    for key in ("exp_avg", "exp_avg_sq"):
+        out[key + "_q"] = np.empty(n, dtype=np.uint8)
+        out[key + "_scale"], out[key + "_zp"] = np.empty(n // 32, dtype=np.float32), np.empty(n // 32, dtype=np.float32)
+    gs = _gs(grad_scale)
+    rc = lib().orc_adamw_step_q8(_p(p), _p(g), *(_p(a) for a in st[0]), *(_p(a) for a in st[1]), n, _DT[tag],
+                                 *adamw_scalars(step, lr, betas, weight_decay, clip), _p(gs),
+                                 *(_p(out[k]) for k in ("p", "exp_avg", "exp_avg_sq", "u", "u_raw")),
+                                 *(_p(out[k + part]) for k in ("exp_avg", "exp_avg_sq") for part in ("_q", "_scale", "_zp")))
+    assert rc == 0
+    return out
+
+
+def philox4x32_10(counter, key) -> np.ndarray:
+    """Philox4x32-10 of counters [..., 4] under one key [2] (uint32 words) -> [..., 4] uint32."""
+    counter, key = _c(counter, np.uint32), _c(key, np.uint32)
+    assert counter.shape[-1] == 4 and key.shape == (2,)
+    out = np.empty_like(counter)
+    lib().orc_philox4x32_10(_p(counter), _p(key), counter.size // 4, _p(out))
+    return out
+
+
+def adamw_words(numel: int, seed: int, offset: int, stream: int) -> np.ndarray:
+    """The four words of every eight elements of a tensor of `numel` elements: uint32 [ceil(numel / 8), 4]."""
+    e8 = np.arange((numel + 7) // 8, dtype=np.uint64)
+    ctr = np.empty((e8.size, 4), dtype=np.uint32)
+    ctr[:, 0] = (e8 & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    ctr[:, 1] = (e8 >> np.uint64(32)).astype(np.uint32) | np.uint32(stream << 28)
+    ctr[:, 2], ctr[:, 3] = offset & 0xFFFFFFFF, (offset >> 32) & 0xFFFFFFFF
+    return philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32))
+
+
+def adamw_halves(numel: int, seed: int, offset: int, stream: int) -> np.ndarray:
+    """The 16 random bits of every element for the stochastic 16-bit store of `stream`: uint32 [numel], each below 2^16."""
+    w = adamw_words(numel, seed, offset, stream)
+    halves = np.stack([w & np.uint32(0xFFFF), w >> np.uint32(16)], axis=-1)  # [n8, word, half]: element e = word e >> 1, half e & 1
+    return halves.reshape(-1)[:numel]
+
+
+def stochastic_round_bits(x, r16, tag: str) -> np.ndarray:
+    """copy_stochastic_ (optim/utils.py:113-116) of float32 `x` to a 16-bit dtype with the given random integers: the float32 bits plus
+    (r16 & (step - 1)), masked to the dtype's mantissa, clamped to the finite range (a NaN stays one), then the dtype's ordinary
+    rounding, which moves float16 subnormals only.  Returned as float32."""
+    x = _c(x, np.float32)
+    step = np.uint32(SR_STEP[tag])
+    r = _c(r16, np.uint32).reshape(x.shape) & (step - np.uint32(1))
+    y = ((x.view(np.uint32) + r) & ~(step - np.uint32(1))).view(np.float32)
+    with np.errstate(invalid="ignore"):
+        y = np.clip(y, np.float32(-_FMAX[tag]), np.float32(_FMAX[tag]))  # np.clip keeps NaN
+    return round_dtype(y, tag)
+
+
+def stochastic_codes(x, seed: int, offset: int, streams) -> tuple:
+    """quantize_weight(x, "uint8", use_stochastic_rounding=True) per group of 32 with the kernel's words: `streams` = (1, 3) for
+    exp_avg, (2, 4) for exp_avg_sq.  (codes uint8, scale, zero point, margin): margin is the distance, in code units and in double,
+    of q + 0.1 z from the nearest boundary between two codes (1 where no boundary is near: outside [0, 255], or an all-equal group)."""
+    x = _c(x, np.float32).reshape(-1)
+    n = x.size
+    assert n % 32 == 0
+    w = np.ascontiguousarray(np.concatenate([adamw_words(n, seed, offset, streams[0]), adamw_words(n, seed, offset, streams[1])], axis=1))
+    code, margin = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.float64)
+    scale, zp = np.empty(n // 32, dtype=np.float32), np.empty(n // 32, dtype=np.float32)
+    assert lib().orc_stochastic_codes(_p(x), _p(w), n, _p(code), _p(scale), _p(zp), _p(margin)) == 0
+    return code, scale, zp, margin

@@ -10,12 +10,13 @@ quantized state, ``optim_adamw_<name>_deq.npz`` with the dequantized values: tog
   quantized state:  exp_avg_q1..3 (uint8 [R, G, 32]), exp_avg_scale1..3, exp_avg_zp1..3 (float32 [R, G, 1]), exp_avg_deq1..3 (float32,
                     SDNQTensor.dequantize()), and the same with exp_avg_sq
   the json: the options the optimizer was made with, `grad_scale` (a float, given to the optimizer as a float32 tensor) and what was
-  planted in the gradients.
+  planted in the gradients (and, for the cases with `planted_param`, in the parameter).
 ``optim_adamw_defaults.json`` records `SDNQOptimizer.apply_group_defaults({})` and the sorted `_group_keys` of the reference's AdamW.
 
 Shapes are chosen against the geometry of csrc/optim.hip (a lane owns 8 elements, a block 2048, a uint8 group is four lanes):
 [37, 24] = 888 elements (not a multiple of 8 x 64), [83] (a tail of 3), [130, 160] = 20 800 elements (>= the reference's 16 384 below
-which state stays dense; 650 groups: not a whole number of 256-lane blocks).
+which state stays dense; 650 groups: not a whole number of 256-lane blocks), [2055] (one whole block and a tail of 7), [65, 64] = 4160
+elements (two blocks and two groups; quantized_buffers_minimum_numel lowered to 1024).
 
 Usage:  python tests/golden/make_golden_optim.py [case ...]
         python tests/golden/make_golden_optim.py --verify     # stored inputs -> the reference's AdamW -> stored outputs, bit for bit
@@ -35,6 +36,13 @@ from sdnq.optim import AdamW  # noqa: E402  (the reference)
 from sdnq.optim.optimizer import SDNQOptimizer  # noqa: E402
 
 STEPS = 3
+# plants of the later cases, by flat index; "max" and "tiny" are the dtype's largest finite value and smallest subnormal.  Inside the
+# first lane, across the lane boundary 7 | 8, and in the tail 2048..2054 of a [2055] tensor
+PARAM_PLANTS = {1: "max", 2: "-0.0", 6: "inf", 7: "nan", 8: "-inf", 9: "tiny", 10: "-max",
+                2048: "nan", 2049: "inf", 2050: "-0.0", 2051: "max", 2053: "tiny", 2054: "-inf"}
+GRAD_PLANTS = {0: "nan", 3: "0.0", 4: "inf", 7: "tiny", 8: "-inf", 15: "nan", 16: "inf",
+               2047: "0.0", 2048: "inf", 2052: "tiny", 2053: "nan", 2054: "0.0"}
+Q8_GRAD_PLANTS = {0: "nan", 5: "inf", 8: "-inf", 31: "inf", 32: "nan", 2047: "inf", 2048: "nan", 4127: "-inf"}
 CASES = [
     dict(name="dense_f32", dtype="f32", shape=(37, 24), opts=dict(lr=1e-3)),
     dict(name="dense_bf16_gradscale", dtype="bf16", shape=(37, 24), opts=dict(lr=0.05), grad_scale=3.0),
@@ -43,10 +51,34 @@ CASES = [
     dict(name="q8_f32_zero_group", dtype="f32", shape=(130, 160), opts=dict(lr=1e-3, use_quantized_buffers=True), zero_group=True),
     dict(name="q8_bf16_nodecay_nonorm", dtype="bf16", shape=(130, 160),
          opts=dict(lr=0.05, use_quantized_buffers=True, weight_decay=0.0, final_norm_mode="none")),
+    # 1 - beta >= 0.5 (the other branch of lerp), a clip below 1, special values in the PARAMETER: [2055] is one block and a tail of 7
+    dict(name="dense_f16_lowclip", dtype="f16", shape=(2055,), plants=True,
+         opts=dict(lr=0.02, betas=(0.4, 0.3), clip_threshold=(0.25, 1e-3, 1e-3), weight_decay=0.0)),
+    dict(name="dense_bf16_fastbetas", dtype="bf16", shape=(2055,), plants=True, opts=dict(betas=(0.4, 0.3))),
+    # [65, 64] = 4160 elements: two blocks and two groups
+    dict(name="q8_f16_fastbetas", dtype="f16", shape=(65, 64), grad_plants=Q8_GRAD_PLANTS, zero_group=[(64, 1)],
+         opts=dict(lr=0.02, betas=(0.4, 0.3), clip_threshold=(0.25, 1e-3, 1e-3), use_quantized_buffers=True,
+                   quantized_buffers_minimum_numel=1024)),
 ]
 # where the special values go (flat indices / (row, group) pairs): inside the first lane, across a lane boundary and in the tail
 NONFINITE = {0: float("nan"), 5: float("inf"), 8: float("-inf"), 401: float("inf"), 886: float("nan"), 887: float("-inf")}
 ZERO_GROUPS = [(0, 0), (64, 2), (129, 4)]
+
+
+def plant(t, plants):
+    """Write `plants` ({flat index: name of a value}) into tensor `t` of the case's dtype, in place."""
+    tiny = {torch.float16: 2.0 ** -24, torch.bfloat16: 2.0 ** -133, torch.float32: 2.0 ** -149}[t.dtype]
+    named = {"max": torch.finfo(t.dtype).max, "tiny": tiny}
+    flat = t.view(-1)
+    for i, what in plants.items():
+        mag = what.lstrip("-")
+        flat[i] = (-1.0 if what.startswith("-") else 1.0) * (named[mag] if mag in named else float(mag))
+    return t
+
+
+def zero_groups_of(case):
+    z = case.get("zero_group")
+    return ZERO_GROUPS if z is True else (z or None)
 
 
 def make_inputs(case):
@@ -55,6 +87,8 @@ def make_inputs(case):
     dt = G.TORCH_DT[case["dtype"]]
     shape = case["shape"]
     p0 = (torch.randn(*shape, generator=g) * 0.5).to(dt)
+    if case.get("plants"):
+        plant(p0, PARAM_PLANTS)
     grads = []
     for _ in range(STEPS):
         gr = torch.randn(*shape, generator=g) * 0.5 * (1.0 + torch.rand(*shape[:-1], 1, generator=g)) * case.get("grad_scale", 1.0)
@@ -63,9 +97,12 @@ def make_inputs(case):
             for i, val in NONFINITE.items():
                 flat[i] = val
         if case.get("zero_group"):
-            for r, gi in ZERO_GROUPS:
+            for r, gi in zero_groups_of(case):
                 gr[r, gi * 32:(gi + 1) * 32] = 0.0
-        grads.append(gr.to(dt))
+        gr = gr.to(dt)
+        if case.get("plants") or case.get("grad_plants"):
+            plant(gr, case.get("grad_plants") or GRAD_PLANTS)
+        grads.append(gr)
     return p0, grads
 
 
@@ -113,7 +150,11 @@ def run_case(case):
                 quantized=bool(case["opts"].get("use_quantized_buffers")), grad_scale=case.get("grad_scale"),
                 options={k: jsonable(v) for k, v in group.items() if k != "params"},
                 nonfinite={str(k): str(v) for k, v in NONFINITE.items()} if case.get("nonfinite") else None,
-                zero_groups=ZERO_GROUPS if case.get("zero_group") else None, tensors=info)
+                zero_groups=zero_groups_of(case), tensors=info)
+    if case.get("plants"):
+        meta["planted_param"] = {str(k): v for k, v in PARAM_PLANTS.items()}
+    if case.get("plants") or case.get("grad_plants"):
+        meta["planted_grad"] = {str(k): v for k, v in (case.get("grad_plants") or GRAD_PLANTS).items()}
     # the dequantized values go to a file of their own: with them one file of a float32 [130, 160] case passes 1 MiB
     deq = {k: out.pop(k) for k in [k for k in out if "_deq" in k]}
     np.savez_compressed(os.path.join(HERE, f"optim_adamw_{case['name']}.npz"), **out)

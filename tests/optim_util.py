@@ -13,6 +13,9 @@ Every scalar (1 - beta, 1 - beta^t, 1 - lr wd) is the Python double; nothing is 
 
 Error measure of the tests: distance(a, ref) = max |a - ref| / max |ref| per tensor.  `REL_ULP[dtype]` is one unit in the last place of
 the dtype relative to a power of two: the largest relative size of one ulp at the tensor's magnitude scale.
+
+At the end: the fixtures through the float32 oracle (oracle/oracle.py: adamw_step, adamw_step_q8), which reproduces them bit for bit
+(tests/test_optim_oracle.py) and which tests/test_optim_exact_gpu.py holds the kernel to.
 """
 import json
 import os
@@ -173,3 +176,50 @@ def deq_excess(deq, ref_deq, ref_scale, shape):
     ref = ref_deq.double().reshape(shape)
     slack = 2.0 ** -20 * torch.maximum(ref.abs(), 255.0 * step)
     return int(((deq.double().reshape(shape) - ref).abs() > step + slack).sum())
+
+
+# ---- the float32 oracle (oracle/oracle.py: adamw_step, adamw_step_q8) on the fixtures -----------------------------------------------------
+def f32_array(t):
+    """A float tensor of any of the three dtypes as a flat float32 ndarray (exact)."""
+    return t.detach().cpu().float().contiguous().view(-1).numpy()
+
+
+def bit_array(t):
+    """The bit patterns of a tensor, flat: uint16 / uint32 / uint8 ndarray (so that -0.0 differs from 0.0 and a NaN compares)."""
+    t = t.detach().cpu().contiguous().view(-1)
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()]).numpy().view({1: np.uint8, 2: np.uint16, 4: np.uint32}[t.element_size()])
+
+
+def stored_bits(x, tag):
+    """The bits that a deterministic store of float32 ndarray `x` to dtype `tag` leaves (oracle.round_dtype's rounding)."""
+    from oracle import oracle as O
+    return O.to_bits(x, tag).view(np.uint32 if tag == "f32" else np.uint16).reshape(-1)
+
+
+def oracle_options(meta, i):
+    """The keyword arguments of oracle.adamw_step / sdnq_amd.ops.adamw_step for step i of a fixture."""
+    o = meta["options"]
+    clips = o["clip_threshold"]
+    return dict(step=i, lr=o["lr"], betas=tuple(o["betas"]), weight_decay=o["weight_decay"],
+                clip=clips if isinstance(clips, (int, float)) else clips[0], grad_scale=meta["grad_scale"])
+
+
+_ORACLE = {}
+
+
+def oracle_fixture_step(name, i):
+    """Step i of fixture `name` by the float32 oracle, from the fixture's own state in front of it: what oracle.adamw_step /
+    adamw_step_q8 return (flat float32 ndarrays, unrounded).  Computed once and shared: treat as read-only."""
+    if (name, i) not in _ORACLE:
+        from oracle import oracle as O
+        meta, t = load(name)
+        s = state_before(meta, t, i)
+        p, g = f32_array(t[f"p{i - 1}"]), f32_array(t[f"g{i}"])
+        if meta["quantized"]:
+            st = [(s[k + "_q"].reshape(-1).numpy(), s[k + "_scale"].reshape(-1).numpy(), s[k + "_zp"].reshape(-1).numpy())
+                  for k in ("exp_avg", "exp_avg_sq")]
+            _ORACLE[(name, i)] = O.adamw_step_q8(p, g, st[0], st[1], meta["dtype"], **oracle_options(meta, i))
+        else:
+            _ORACLE[(name, i)] = O.adamw_step(p, g, f32_array(s["exp_avg"]), f32_array(s["exp_avg_sq"]), meta["dtype"],
+                                              **oracle_options(meta, i))
+    return _ORACLE[(name, i)]

@@ -1,6 +1,8 @@
 """The fused AdamW step on the MI355X (sdnq_amd.optim, csrc/optim.hip) against the reference's fixtures (tests/golden/optim_adamw_*) and
 the float64 restatement of tests/optim_util.py.  The bounds are worked out in the tests' docstrings; the measured distances are printed
-before they are asserted (profiles/optim_adamw_accuracy.md has the reference's side of them)."""
+before they are asserted (profiles/optim_adamw_accuracy.md has both sides of them).  These tests check what the step and its stochastic
+rounding are FOR (distances, unbiasedness); which bits they produce -- state bit-equal to the float32 oracle, the parameter within the
+interval the 1-ulp rsqrt leaves, stochastic stores predicted from (seed, offset, element, stream) -- is tests/test_optim_exact_gpu.py."""
 import math
 import os
 import sys
