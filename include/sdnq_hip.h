@@ -763,6 +763,41 @@ int sdnq_hip_adamw_step_q8(void* param, const void* grad, int dtype, int64_t num
                            float w2, float bc1, float bc2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
                            uint64_t seed, uint64_t offset, sdnq_stream_t stream);
 
+/* ---- transposed convolutions: GEMM + col2im -------------------------------------------------------------------------------------------
+ * replaces quantized_conv_transpose_{1,2,3}d_forward (layers/conv/forward.py:85-99): F.conv_transposeNd(x, dequantize(W), bias, stride,
+ * padding, output_padding, groups, dilation) on a weight [C_in][C_out / groups][k...].  Per conv group the product
+ * cols[(b, l)][(co, kpos)] = sum_ci x[b][ci][l] * W[ci][co][kpos] is a float GEMM (M = B * L, K = C_in / groups, N = P = C_out / groups *
+ * prod(k)) stored in float32; every output element then gathers the taps that reach it, so a 16-bit result is rounded once.
+ *
+ * sdnq_hip_dequant_convt: SDNQDequantizer.__call__ on such a weight (dequantizer.py:63-84: w.to(scale.dtype) * scale or
+ *   addcmul(zero_point, w, scale), the cast), written into the GEMM's weight operand out [groups][P][C_in / groups] of out_dtype
+ *   (K contiguous).  w: weight = the stored codes in element order [C_in][P] (every storage format of sdnq_hip_dequant), n = C_in, k = P,
+ *   positions = prod(k); group_size is not read.  scale_groups <= 1: scale / zero_point are [P], one per column (the reduction over C_in
+ *   of quantizer.py:129-133); scale_groups = G > 1: the square grouped layout of quantizer.py:210-214, scale / zero_point
+ *   [C_in][G][prod(k)], column (co, kpos) of row ci takes entry [ci][co % G][kpos].  scale_dtype as in sdnq_hip_dequant (the product is
+ *   rounded to a 16-bit scale dtype before the cast).  P % 16 == 0 and (C_in / groups) % 16 == 0; no SVD factors, no codebook
+ *   (SDNQ_ERR_UNSUPPORTED).
+ *
+ * sdnq_hip_linear_float_f32out(_strided): sdnq_hip_linear_float(_strided) without a bias and with the float32 accumulators stored
+ *   unrounded: out [M][ldc] float32 (4-byte aligned; the matrix-core tiles need 16-byte aligned rows and n % 8 == 0, else the few-row
+ *   kernel runs), x / wd of `dtype`.
+ *
+ * sdnq_hip_col2im: out[b][co][od][oh][ow] = cast(bias[co] + sum over the taps (kd, kh, kw), ascending, with
+ *   (o + pad - k * dil) % stride == 0 on every axis and the quotient i inside the input, of cols[(b, id, ih, iw)][co * prod(k) + kpos])
+ *   -- float32 accumulation, one rounding, no atomics: one thread per output element.  cols: float32 rows of ldcols elements
+ *   (>= channels * prod(k); the groups of a grouped layer are consecutive column ranges), bias NULL or [channels] of `dtype`, out of
+ *   `dtype`.  1-D and 2-D layers pass 1 for the leading axes (stride 1, padding 0, dilation 1).  The output extent is given, not derived
+ *   (output_padding); on every axis it lies in [base, base + max(stride, dilation)) with base = (in - 1) * stride - 2 * pad +
+ *   dil * (k - 1) + 1, as torch requires (SDNQ_ERR_SHAPE otherwise). */
+int sdnq_hip_dequant_convt(const SdnqWeight* w, int groups, int scale_groups, void* out, int out_dtype, sdnq_stream_t stream);
+int sdnq_hip_linear_float_f32out(const void* x, const void* wd, int dtype, float* out, int64_t m, int64_t n, int64_t k, int64_t ldx,
+                                 sdnq_stream_t stream);
+int sdnq_hip_linear_float_f32out_strided(const void* x, const void* wd, int dtype, float* out, int64_t m, int64_t n, int64_t k,
+                                         int64_t ldx, int64_t ldc, sdnq_stream_t stream);
+int sdnq_hip_col2im(const float* cols, int64_t ldcols, const void* bias, int dtype, void* out, int batch, int channels, int in_d,
+                    int in_h, int in_w, int out_d, int out_h, int out_w, int kd, int kh, int kw, int stride_d, int stride_h,
+                    int stride_w, int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ UNITS = (
     ("linear_float", _PRELOAD, None),
     ("quantize", "", None),
     ("conv", _PRELOAD, None),
+    ("convt", "", None),
     # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them
     # with VALU every block; in AGPR form the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),

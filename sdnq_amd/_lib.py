@@ -39,6 +39,7 @@ EXPORTS = [
     "sdnq_hip_rowquant_f16", "sdnq_hip_scaled_mm_f16", "sdnq_hip_embedding", "sdnq_hip_quantize_codebook",
     "sdnq_hip_dequant_loss", "sdnq_hip_dequant_loss_workspace_bytes", "sdnq_hip_attn_lse", "sdnq_hip_attn_bwd",
     "sdnq_hip_colquant_t", "sdnq_hip_colquant_t_workspace_bytes", "sdnq_hip_adamw_step", "sdnq_hip_adamw_step_q8",
+    "sdnq_hip_dequant_convt", "sdnq_hip_linear_float_f32out", "sdnq_hip_linear_float_f32out_strided", "sdnq_hip_col2im",
 ]
 
 
@@ -188,6 +189,10 @@ def _declare(lib):
     adamw_tail = [f32] * 7 + [vp, i32, i32, u64, u64, vp]  # lr, w1, w2, bc1, bc2, clip, decay, grad_scale, sr_param, sr_state, seed, offset, stream
     lib.sdnq_hip_adamw_step.argtypes = [vp, vp, vp, vp, i32, i64] + adamw_tail
     lib.sdnq_hip_adamw_step_q8.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, vp, vp] + adamw_tail
+    lib.sdnq_hip_dequant_convt.argtypes = [c.POINTER(SdnqWeight), i32, i32, vp, i32, vp]
+    lib.sdnq_hip_linear_float_f32out.argtypes = [vp, vp, i32, vp, i64, i64, i64, i64, vp]
+    lib.sdnq_hip_linear_float_f32out_strided.argtypes = [vp, vp, i32, vp, i64, i64, i64, i64, i64, vp]
+    lib.sdnq_hip_col2im.argtypes = [vp, i64, vp, i32, vp] + [i32] * 20 + [vp]
     for name in EXPORTS:
         if name not in ("sdnq_hip_strerror", "sdnq_hip_set_tile_override"):
             getattr(lib, name).restype = c.c_int

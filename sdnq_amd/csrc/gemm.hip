@@ -2338,6 +2338,19 @@ int sdnq_float_gemm(const void* x, const void* w, const void* bias, int dtype, v
 #undef FG
 }
 
+// internal (gemm_dev.h; used by sdnq_hip_linear_float_f32out in linear_float.hip): out[M][ldc] (float32) = x[M][K] . w[N][K]^T, x and w of
+// `dtype` -- the tiles sdnq_float_gemm picks, storing the float32 accumulators unrounded
+int sdnq_float_gemm_f32out(const void* x, const void* w, int dtype, float* out, int64_t m, int64_t n, int64_t k, int64_t ldx, int64_t ldc,
+                           hipStream_t s) {
+    if (dtype == SDNQ_F32) return sdnq_float_gemm(x, w, nullptr, dtype, out, m, n, k, ldx, s, nullptr, 0, 0, ldc);
+    GemmParams p{};
+    p.ldc = ldc;
+    p.a = (const uint8_t*)x; p.b = (const uint8_t*)w; p.out = out;
+    p.M = m; p.N = n; p.K = k * 2; p.lda = ldx * 2; p.ldb = k * 2; p.bias_ndim = 0; p.bias_dtype = SDNQ_F32;
+    if (dtype == SDNQ_BF16) return launch_tiles<MM_BF16, SDNQ_F32, EPI_NONE>(p, s);
+    return launch_tiles<MM_F16, SDNQ_F32, EPI_NONE>(p, s);
+}
+
 // tile choice of the fused dequantize GEMM: wave tiles with two activation sub-tiles per weight sub-tile (the 22-VALU conversion of
 // a weight fragment is shared by two MFMAs), 128-byte activation rows / 64-byte weight rows per stage
 template <int MM, int OUT_T, int EPI>

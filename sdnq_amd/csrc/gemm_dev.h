@@ -21,6 +21,9 @@ int sdnq_internal_take_prefetch(int64_t room, int threads, const uint8_t* pf_ptr
 // gemm.hip: the float MFMA GEMM behind sdnq_hip_linear_float (linear_float.hip) and sdnq_hip_linear_float_multi
 int sdnq_float_gemm(const void* x, const void* w, const void* bias, int dtype, void* out, int64_t m, int64_t n, int64_t k,
                     int64_t ldx, hipStream_t s, void* const* outs = nullptr, int n_outs = 0, int64_t seg_n = 0, int64_t ldc = 0);
+// gemm.hip: the same kernels with a float32 store and no bias (sdnq_hip_linear_float_f32out: the cols of a transposed convolution)
+int sdnq_float_gemm_f32out(const void* x, const void* w, int dtype, float* out, int64_t m, int64_t n, int64_t k, int64_t ldx, int64_t ldc,
+                           hipStream_t s);
 // gemm_ks.hip: the 64 x 80 tile with an in-workgroup K split (8 waves, partial sums reduced through LDS) -- tile id 28 of gemm.hip
 bool sdnq_internal_ks_eligible(int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb);
 bool sdnq_internal_ks_preferred(int64_t m, int64_t n, int64_t k);

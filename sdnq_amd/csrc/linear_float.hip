@@ -3,6 +3,8 @@
 //   sdnq_hip_linear_float(_strided) <- torch.nn.functional.linear on the dequantized weight
 //                                      (layers/linear/forward.py:25-26; M<32 branch linear_int8.py:102-103): linear_float_kernel for a
 //                                      few rows, the MFMA GEMM of gemm.hip (sdnq_float_gemm) beyond 32
+//   sdnq_hip_linear_float_f32out(_strided) <- the same product with the float32 accumulators stored unrounded and no bias: the `cols`
+//                                      of a transposed convolution (convt.hip), rounded once after the taps are added
 //   sdnq_hip_lowrank_down           <- t = torch.mm(x, svd_down), the inner product of the SVD branch (linear_int8.py:60):
 //                                      lowrank_down_kernel on the matrix cores, linear_float_kernel for float32
 #include "gemm_dev.h"  // sdnq_float_gemm
@@ -11,7 +13,8 @@ namespace {
 
 // out[m][n] = cast( sum_k x[m][k] * w[n][k] + bias[n] ), fp32 accumulate.
 // One wave per output channel n and a chunk of MC activation rows; lanes stride K in 16-byte vectors.
-template <int T_ID, int MC>
+// O_ID: the output element type (T_ID; SDNQ_F32 for the float32 store of sdnq_hip_linear_float_f32out).
+template <int T_ID, int MC, int O_ID = T_ID>
 __global__ __launch_bounds__(256) void linear_float_kernel(const void* __restrict__ x, const void* __restrict__ w,
                                                            const void* __restrict__ bias, void* __restrict__ out, int64_t M,
                                                            int64_t N, int64_t K, int64_t ldx, int64_t ldc) {
@@ -43,7 +46,7 @@ __global__ __launch_bounds__(256) void linear_float_kernel(const void* __restric
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if (lane == 0 && m0 + i < M) {
             if (bias) s += FT<T_ID>::load(bias, n);
-            FT<T_ID>::store(out, (m0 + i) * ldc + n, s);
+            FT<O_ID>::store(out, (m0 + i) * ldc + n, s);
         }
     }
 }
@@ -192,6 +195,33 @@ extern "C" int sdnq_hip_linear_float_strided(const void* x, const void* wd, cons
 extern "C" int sdnq_hip_linear_float(const void* x, const void* wd, const void* bias, int dtype, void* out, int64_t m,
                                      int64_t n, int64_t k, int64_t ldx, sdnq_stream_t stream) {
     return sdnq_hip_linear_float_strided(x, wd, bias, dtype, out, m, n, k, ldx, n, stream);
+}
+
+extern "C" int sdnq_hip_linear_float_f32out_strided(const void* x, const void* wd, int dtype, float* out, int64_t m, int64_t n, int64_t k,
+                                                    int64_t ldx, int64_t ldc, sdnq_stream_t stream) {
+    if (!x || !wd || !out) return SDNQ_ERR_NULL;
+    if (dtype < 0 || dtype > 2) return SDNQ_ERR_DTYPE;
+    const int eb = (dtype == SDNQ_F32) ? 4 : 2;
+    if (m <= 0 || n <= 0 || k <= 0 || ldx < k || ldc < n || ((k * eb) % 16) != 0) return SDNQ_ERR_SHAPE;
+    if (((uintptr_t)x % 16) || ((uintptr_t)wd % 16) || ((ldx * eb) % 16) || ((uintptr_t)out % 4)) return SDNQ_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    if (m > 32 && (n % 8) == 0 && ((uintptr_t)out % 16) == 0 && ((ldc * 4) % 16) == 0)
+        return sdnq_float_gemm_f32out(x, wd, dtype, out, m, n, k, ldx, ldc, s);
+    constexpr int MC = 8;
+    dim3 grid((unsigned)((n + 3) / 4), (unsigned)((m + MC - 1) / MC)), block(256);
+    const void* nobias = nullptr;
+    switch (dtype) {
+        case SDNQ_F32: hipLaunchKernelGGL((linear_float_kernel<SDNQ_F32, MC>), grid, block, 0, s, x, wd, nobias, (void*)out, m, n, k, ldx, ldc); break;
+        case SDNQ_BF16: hipLaunchKernelGGL((linear_float_kernel<SDNQ_BF16, MC, SDNQ_F32>), grid, block, 0, s, x, wd, nobias, (void*)out, m, n, k, ldx, ldc); break;
+        default: hipLaunchKernelGGL((linear_float_kernel<SDNQ_F16, MC, SDNQ_F32>), grid, block, 0, s, x, wd, nobias, (void*)out, m, n, k, ldx, ldc); break;
+    }
+    SDNQ_CHECK_LAUNCH();
+    return SDNQ_OK;
+}
+
+extern "C" int sdnq_hip_linear_float_f32out(const void* x, const void* wd, int dtype, float* out, int64_t m, int64_t n, int64_t k,
+                                            int64_t ldx, sdnq_stream_t stream) {
+    return sdnq_hip_linear_float_f32out_strided(x, wd, dtype, out, m, n, k, ldx, n, stream);
 }
 
 extern "C" int sdnq_hip_lowrank_down(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* svd_down,

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .common import conv_types, dtype_dict, embedding_types, linear_types
+from .common import conv_transpose_types, conv_types, dtype_dict, embedding_types, linear_types
 
 
 @dataclass
@@ -101,7 +101,8 @@ class SDNQDequantizer:
 
     def quant_weight(self, weight, scale, zero_point=None, svd_up=None, svd_down=None) -> ops.QuantWeight:
         if self.layer_class_name not in linear_types and self.layer_class_name not in conv_types and self.layer_class_name not in embedding_types:
-            raise NotImplementedError(f"{self.layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X")
+            raise NotImplementedError(f"{self.layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding weights have the [N][K] kernel layout "
+                                      "(transposed convolutions: ops.make_convt_weight)")
         n, k, pos = self.out_features, self.in_features, self.kernel_positions
         group = self.group_size if self.group_size > 0 else k // pos
         return ops.make_quant_weight(self.weights_dtype, weight, scale, zero_point, svd_up, svd_down, n, k, group,
@@ -136,6 +137,16 @@ class SDNQDequantizer:
         reference returns, dequantizer.py:28-29/65-66)."""
         if dtype is None:
             dtype = self.result_dtype
+        if self.layer_class_name in conv_transpose_types:
+            # [C_in, C_out / groups, *kernel] (dequantizer.py:63-84): the GEMM-operand kernel of the forward, its [P][C_in] result transposed back
+            if svd_up is not None or self.use_hadamard or self.use_codebook:
+                raise NotImplementedError("SVD factors, Hadamard rotation and codebooks on transposed convolutions are not built")
+            shape = tuple(int(d) for d in self.original_shape)
+            kprod = 1
+            for d in shape[2:]:
+                kprod *= d
+            qw = ops.make_convt_weight(self.weights_dtype, weight, scale, zero_point, shape[0], shape[1] * kprod, kprod)
+            return ops.dequant_convt(qw, dtype, 1)[0].t().contiguous().view(shape)
         qw = self.quant_weight(weight, scale, zero_point, svd_up, svd_down)
         had = self.hadamard_group_size if (self.use_hadamard and not non_hadamard) else 0
         w = ops.dequant(qw, dtype, had)

@@ -11,10 +11,10 @@ def get_forward_func(layer_class_name: str, quantized_matmul_dtype: str, use_qua
     if layer_class_name in embedding_types:  # forward.py:7-9
         from .embedding import quantized_embedding_forward
         return quantized_embedding_forward
-    if layer_class_name in conv_transpose_types:
-        raise NotImplementedError(
-            f"{layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X (transposed "
-            "convolutions are outside SURVEY 8)")
+    if layer_class_name in conv_transpose_types:  # forward.py:29-37: by dimensionality; never a quantized matmul (quantizer.py:133)
+        from . import conv_transpose
+        return {"1": conv_transpose.quantized_conv_transpose_1d_forward, "2": conv_transpose.quantized_conv_transpose_2d_forward,
+                "3": conv_transpose.quantized_conv_transpose_3d_forward}[layer_class_name[-2]]
     if layer_class_name in conv_types:  # forward.py:10-28
         from . import conv
         if use_quantized_matmul:

@@ -96,9 +96,12 @@ class SDNQLayer(torch.nn.Module):
 def _traceable(layer) -> bool:
     """Layers that trace as sdnq_hip:: operators under torch.compile: Linear (one or two operators, torch_ops.layer_plan) and the conv
     layers (one opaque layer_forward operator each -- round 4: a compiled UNet has no graph breaks at its 49 quantized convs) and the
-    embeddings (one layer_forward operator: the gather-dequantize launch)."""
+    embeddings (one layer_forward operator: the gather-dequantize launch) and the transposed convs called with one argument (one layer_forward
+    operator; a call with output_size= takes the eager forward)."""
     dq = layer.__dict__.get("sdnq_dequantizer")
     return dq is not None and dq.layer_class_name in ("Linear", "SDNQLinear", "Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d",
+                                                      "ConvTranspose1d", "ConvTranspose2d", "ConvTranspose3d", "SDNQConvTranspose1d",
+                                                      "SDNQConvTranspose2d", "SDNQConvTranspose3d",
                                                       "Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding")
 
 
@@ -118,11 +121,24 @@ class SDNQConv3d(SDNQLayer, torch.nn.Conv3d):
     original_class: torch.nn.Conv3d
 
 
+class SDNQConvTranspose1d(SDNQLayer, torch.nn.ConvTranspose1d):
+    original_class: torch.nn.ConvTranspose1d
+
+
+class SDNQConvTranspose2d(SDNQLayer, torch.nn.ConvTranspose2d):
+    original_class: torch.nn.ConvTranspose2d
+
+
+class SDNQConvTranspose3d(SDNQLayer, torch.nn.ConvTranspose3d):
+    original_class: torch.nn.ConvTranspose3d
+
+
 class SDNQEmbedding(SDNQLayer, torch.nn.Embedding):
     original_class: torch.nn.Embedding
 
 
-torch.serialization.add_safe_globals([SDNQLayer, SDNQLinear, SDNQConv1d, SDNQConv2d, SDNQConv3d, SDNQEmbedding])
+torch.serialization.add_safe_globals([SDNQLayer, SDNQLinear, SDNQConv1d, SDNQConv2d, SDNQConv3d, SDNQConvTranspose1d, SDNQConvTranspose2d,
+                                      SDNQConvTranspose3d, SDNQEmbedding])
 
 
 def get_sdnq_wrapper_class(original_layer: torch.nn.Module, forward_func: Callable) -> SDNQLayer:
@@ -135,7 +151,12 @@ def get_sdnq_wrapper_class(original_layer: torch.nn.Module, forward_func: Callab
         return SDNQConv2d(original_layer, forward_func)
     if name == "Conv3d":
         return SDNQConv3d(original_layer, forward_func)
+    if name == "ConvTranspose1d":  # layers/__init__.py:51-58
+        return SDNQConvTranspose1d(original_layer, forward_func)
+    if name == "ConvTranspose2d":
+        return SDNQConvTranspose2d(original_layer, forward_func)
+    if name == "ConvTranspose3d":
+        return SDNQConvTranspose3d(original_layer, forward_func)
     if name in ("Embedding", "Gemma4TextScaledWordEmbedding"):
         return SDNQEmbedding(original_layer, forward_func)
-    # transposed conv wrappers are not built
     return SDNQLayer(original_layer, forward_func)

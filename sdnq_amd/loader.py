@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from .common import dtype_dict
+from .common import conv_transpose_types, dtype_dict
 from .dequantizer import SDNQDequantizer
 from .forward import get_forward_func
 from .quantizer import check_quantized_matmul_is_allowed
@@ -85,7 +85,7 @@ def _end_step(_module=None, _args=None, _output=None):
 
 @torch.no_grad()
 def accelerate(model: torch.nn.Module) -> AccelerateResult:
-    """Route every quantized Linear (and Conv1d / Conv2d / Conv3d, any ``groups``) of ``model`` that the HIP forwards compute
+    """Route every quantized Linear (and Conv1d / Conv2d / Conv3d / ConvTranspose1d / 2d / 3d, any ``groups``) of ``model`` that the HIP forwards compute
     through them.  NEVER turns a working model into a failing one: support is decided per module here, before anything is
     re-pointed (`support.unsupported_reason`, the predicate the forwards themselves use); an SDNQ layer in a configuration this
     package does not build keeps the ``forward_func`` it came with -- on a reference-built model that is the reference's own
@@ -525,7 +525,7 @@ def apply_sdnq_options_to_model(model: torch.nn.Module, dtype: torch.dtype | Non
         cls = getattr(getattr(module, "sdnq_dequantizer", None), "layer_class_name", None)
         if cls is None:
             continue
-        conv = cls in ("Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d")
+        conv = cls in ("Conv1d", "Conv2d", "Conv3d", "SDNQConv1d", "SDNQConv2d", "SDNQConv3d") or cls in conv_transpose_types
         emb = cls in ("Embedding", "SDNQEmbedding", "Gemma4TextScaledWordEmbedding")
         if not (conv or emb or cls in ("Linear", "SDNQLinear")):
             continue

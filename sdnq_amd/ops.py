@@ -624,6 +624,89 @@ def dequant(qw: QuantWeight, out_dtype: torch.dtype, hadamard_group: int = 0, us
     return out
 
 
+def make_convt_weight(weights_dtype: str, weight: torch.Tensor, scale: torch.Tensor, zero_point, c_in: int, p_cols: int, kprod: int) -> QuantWeight:
+    """The stored tensors of a transposed-conv layer ([C_in, C_out / groups, *kernel] codes or their packed form, element order
+    [C_in][P]) as the descriptor sdnq_hip_dequant_convt reads: n = C_in, k = P = C_out / groups * prod(kernel), positions = prod(kernel).
+    scale / zero_point: [1, C_out / groups, *kernel] (one per column, P values) or the square grouped layout
+    [C_in, 1, num_groups, *kernel] (C_in * num_groups * prod(kernel) values) -- `QuantWeight.group_size` holds num_groups (1: per column)."""
+    _require_cuda(weight, scale)
+    storage, kind, bits, ebits, mbits, native = _storage_kind(weights_dtype)
+    w_phys = weight if weight.is_contiguous() else weight.contiguous()
+    if w_phys.dtype in (torch.int64, torch.bool):
+        w_phys = w_phys.to(torch.uint8)
+    scale_dtype = scale.dtype
+    if scale_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise _lib.SdnqHipError(f"scale must be float32, bfloat16 or float16, got {scale_dtype}")
+    if scale_dtype != torch.float32 and bits > 8:
+        raise _lib.SdnqHipError("16-bit scales with formats wider than 8 bits are not built (the codes are not exact in the scale dtype)")
+    if zero_point is not None and zero_point.dtype != scale_dtype:
+        raise _lib.SdnqHipError("scale and zero_point must share one dtype (loader.py:277-280 casts both)")
+    sc = scale.to(torch.float32).contiguous().view(-1)
+    if sc.numel() == p_cols and (scale.ndim < 1 or scale.shape[0] == 1):
+        num_groups = 1
+    elif sc.numel() % (c_in * kprod) == 0 and scale.shape[0] == c_in:
+        num_groups = sc.numel() // (c_in * kprod)
+    else:
+        raise _lib.SdnqHipError(f"scale of shape {tuple(scale.shape)} is neither [1, P] nor [C_in, 1, groups, *kernel] for C_in = {c_in}, P = {p_cols}")
+    zp = None
+    if zero_point is not None:
+        zp = zero_point.to(torch.float32).contiguous().view(-1)
+        if zp.numel() != sc.numel():
+            raise _lib.SdnqHipError("zero_point size mismatch")
+    d = SdnqWeight(weight=_ptr(w_phys), scale=_ptr(sc), zero_point=_ptr(zp), svd_up=None, svd_down=None, n=c_in, k=p_cols,
+                   group_size=p_cols, svd_rank=0, svd_dtype=0, storage=storage, kind=kind, bits=bits, exponent=ebits, mantissa=mbits,
+                   native_float=native, positions=kprod, scale_dtype=float_code(scale_dtype))
+    return QuantWeight(desc=d, n=c_in, k=p_cols, group_size=num_groups, keep=(w_phys, sc, zp, None, None), scale_dtype=scale_dtype)
+
+
+def dequant_convt(qw: QuantWeight, out_dtype: torch.dtype, groups: int = 1) -> torch.Tensor:
+    """sdnq_hip_dequant_convt: the dequantized weight of a transposed conv as the float GEMM's operand [groups, P, C_in / groups]."""
+    dev = qw.keep[0].device
+    if qw.n % groups:
+        raise _lib.SdnqHipError(f"groups={groups} does not divide the {qw.n} input channels")
+    out = torch.empty((groups, qw.k, qw.n // groups), device=dev, dtype=out_dtype)
+    check(_lib.load().sdnq_hip_dequant_convt(ctypes.byref(qw.desc), groups, qw.group_size, out.data_ptr(), float_code(out_dtype),
+                                             _stream(out)), "dequant_convt")
+    return out
+
+
+def linear_float_f32_into(x2d: torch.Tensor, w: torch.Tensor, out: torch.Tensor, col0: int) -> None:
+    """sdnq_hip_linear_float_f32out_strided: x2d (a column slice [M, K]) . w[N, K]^T, unrounded, into columns col0 .. col0 + N of the
+    row-major float32 `out` [M, C]."""
+    _require_cuda(x2d, w, out)
+    m, k = x2d.shape
+    n = w.shape[0]
+    assert w.is_contiguous() and x2d.stride(1) == 1 and w.dtype == x2d.dtype and out.dtype == torch.float32 and out.is_contiguous()
+    assert 0 <= col0 and col0 + n <= out.shape[1] and out.shape[0] == m and w.shape[1] == k
+    check(_lib.load().sdnq_hip_linear_float_f32out_strided(x2d.data_ptr(), w.data_ptr(), float_code(x2d.dtype),
+                                                           out.data_ptr() + col0 * 4, m, n, k, x2d.stride(0), out.shape[1],
+                                                           _stream(x2d)), "linear_float_f32out_strided")
+
+
+def col2im(cols: torch.Tensor, bias, out_dtype: torch.dtype, batch: int, channels: int, in_size, out_size, kernel, stride, padding,
+           dilation) -> torch.Tensor:
+    """sdnq_hip_col2im: the gather half of a transposed convolution.  cols float32 [batch * prod(in_size), >= channels * prod(kernel)];
+    in_size / out_size / kernel / stride / padding / dilation: 1 to 3 entries each -> [batch, channels, *out_size] of out_dtype.
+    Limits of the launch: batch * ceil(prod(out_size) / 16) < 2^31 and channels <= 16 * 65535 (SDNQ_ERR_SHAPE beyond)."""
+    _require_cuda(cols, bias)
+    nd = len(in_size)
+    lead = 3 - nd
+
+    def three(v, fill):
+        return [fill] * lead + [int(e) for e in v]
+    i3, o3, k3, s3, p3, d3 = three(in_size, 1), three(out_size, 1), three(kernel, 1), three(stride, 1), three(padding, 0), three(dilation, 1)
+    if cols.dtype != torch.float32 or cols.ndim != 2 or cols.stride(1) != 1 or cols.shape[0] != batch * i3[0] * i3[1] * i3[2]:
+        raise _lib.SdnqHipError("col2im expects float32 cols [batch * input positions, columns]")
+    if bias is not None:
+        bias = bias.to(out_dtype).contiguous()
+        if bias.numel() != channels:
+            raise _lib.SdnqHipError("col2im: bias must hold one value per output channel")
+    out = torch.empty((batch, channels, *[int(e) for e in out_size]), device=cols.device, dtype=out_dtype)
+    check(_lib.load().sdnq_hip_col2im(cols.data_ptr(), cols.stride(0), _ptr(bias), float_code(out_dtype), out.data_ptr(), batch, channels,
+                                      *i3, *o3, *k3, *s3, *p3, *d3, _stream(cols)), "col2im")
+    return out
+
+
 def dequant_loss_sum(qw: QuantWeight, ref: torch.Tensor, hadamard_group: int = 0) -> torch.Tensor:
     """sum((dequant(qw, float32, hadamard_group) - ref) ** 2) over [N][K] as a device fp64 scalar, in one fused pass that never writes
     the dequantized weight (sdnq_hip_dequant_loss; each term (d * d) in fp32, the sum in fp64, bitwise the same on every call).

@@ -4,7 +4,8 @@ API names are the reference's (quantizer.py: SDNQConfig :846, sdnq_quantize_laye
 sdnq_quantize_layer :423, apply_sdnq_to_module :477, QuantizationMethod :60) so host code switches with an
 import change; the module/tensor layout produced is byte-compatible with reference checkpoints
 (SURVEY App. C), which tests/test_quantizer.py checks against the golden fixtures.  Only what feeds the Linear
-hot path is implemented: no stochastic rounding, no transposed conv.
+hot path is implemented: no stochastic rounding.  Transposed convolutions (quant_conv=True) take the reference's own branch: reduction over C_in,
+or the square grouped layout (_quantize_conv_transpose_weight).
 Embedding layers (quant_embedding=True) take the reference's non-Linear branch; use_codebook=True stores Lloyd-Max level tables
 (unsigned integer dtypes up to 8 bits); use_dynamic_quantization=True picks each layer's dtype by its reconstruction loss
 (sdnq_quantize_layer_weight_dynamic, reference quantizer.py:279-417).
@@ -18,7 +19,7 @@ from enum import Enum
 import torch
 
 from . import packed
-from .common import conv_types, dtype_dict, embedding_types, linear_types, sdnq_version, weights_dtype_order
+from .common import conv_transpose_types, conv_types, dtype_dict, embedding_types, linear_types, sdnq_version, weights_dtype_order
 from .dequantizer import SDNQDequantizer
 from .forward import get_forward_func
 from .layers import get_sdnq_wrapper_class
@@ -175,8 +176,12 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
     """
     is_conv = layer_class_name in conv_types
     is_embedding = layer_class_name in embedding_types
+    if layer_class_name in conv_transpose_types:
+        return _quantize_conv_transpose_weight(weight.detach(), layer_class_name, weights_dtype, quantized_matmul_dtype, group_size,
+                                               hadamard_group_size, svd_rank, svd_steps, codebook_steps, use_svd, use_hadamard, use_codebook,
+                                               dequantize_fp32, weight.dtype if torch_dtype is None else torch_dtype)
     if layer_class_name not in linear_types and not is_conv and not is_embedding:
-        raise NotImplementedError(f"{layer_class_name}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X")
+        raise NotImplementedError(f"{layer_class_name}: only Linear, conv, transposed conv and Embedding layers are built for MI355X")
     weight = weight.detach()
     original_shape, original_stride = weight.shape, weight.stride()
     torch_dtype = weight.dtype if torch_dtype is None else torch_dtype
@@ -279,6 +284,86 @@ def sdnq_quantize_layer_weight(weight: torch.Tensor, layer_class_name: str = "Li
                          use_hadamard=bool(use_hadamard or using_pre_rotated_hadamard), use_codebook=bool(use_codebook),
                          layer_class_name=layer_class_name)
     return dq, {"weight": q, "scale": scale, "zero_point": zero_point, "svd_up": svd_up, "svd_down": svd_down}
+
+
+def _quantize_conv_transpose_weight(weight: torch.Tensor, layer_class_name: str, weights_dtype: str, quantized_matmul_dtype, group_size: int,
+                                    hadamard_group_size: int, svd_rank: int, svd_steps: int, codebook_steps: int, use_svd: bool,
+                                    use_hadamard: bool, use_codebook: bool, dequantize_fp32: bool, torch_dtype: torch.dtype):
+    """The transposed-conv branch of the reference's quantizer (quantizer.py:129-133, 210-214): weight [C_in, C_out / groups, *kernel],
+    never a quantized matmul, the scale reduces over C_in -- scale / zero_point [1, C_out / groups, *kernel], the stored weight keeps its
+    shape, result_shape None.  Group quantization runs `weight.unflatten(1, (group_size, num_of_groups))` with group_size *
+    num_of_groups = C_in, which only multiplies up when C_out / groups == C_in: layout [C_in, group_size, num_of_groups, *kernel], reduction
+    over axis 1, scale [C_in, 1, num_of_groups, *kernel], result_shape = the original shape.  Any other shape fails in the reference's own
+    quantizer and raises here.  GPU tensors in an integer format of up to 8 bits or an unpacked 8-bit float format: the HIP row quantizer with
+    the reduction axis moved last (the same float32 arithmetic), moved back -- column and square grouped layouts alike, packed integer codes
+    unpacked, moved and packed again.  Everything else runs the torch restatement on the host (a GPU weight is copied there and the results
+    back): a torch division on the device is not correctly rounded, so only the host run reproduces the reference's tensors."""
+    if use_svd or use_hadamard or use_codebook:
+        raise NotImplementedError(f"{layer_class_name}: SVD factors, Hadamard rotation and codebooks on transposed convolutions are not built")
+    original_shape, original_stride = weight.shape, weight.stride()
+    c_in = int(weight.shape[0])
+    mm_dtype = get_quantized_matmul_dtype(weights_dtype, quantized_matmul_dtype)
+    requant = _needs_requant(weights_dtype, mm_dtype)
+    ent = dtype_dict[weights_dtype]
+    group_size, groups = _pick_group_size(group_size, c_in, weights_dtype, False, False, direct_matmul=False)
+    result_shape = None
+    dim = 0
+    if groups > 1:
+        if int(weight.shape[1]) != c_in:
+            raise NotImplementedError(
+                f"{layer_class_name} weight {tuple(original_shape)} with group quantization (group_size={group_size}): the reference's "
+                f"unflatten(1, (group_size, num_of_groups)) needs C_out / groups == C_in ({int(weight.shape[1])} != {c_in}) and raises too; "
+                "quantize this layer with group_size=-1")
+        result_shape = weight.shape
+        weight = weight.unflatten(1, (group_size, groups))
+        dim = 1
+    scale_dtype = None
+    if not dequantize_fp32 and ent["max"] <= 16384 and torch_dtype in (torch.bfloat16, torch.float16):
+        scale_dtype = torch_dtype
+    kprod = 1
+    for d in original_shape[2:]:
+        kprod *= int(d)
+    p_cols = int(original_shape[1]) * kprod
+    reduce_len = int(weight.shape[dim])
+    hip_format = (ent["is_integer"] and ent["num_bits"] <= 8) or (not ent["is_packed"] and ent["num_bits"] == 8)
+    if (weight.is_cuda and USE_HIP_QUANTIZER and weight.dtype in (torch.float32, torch.bfloat16, torch.float16) and reduce_len % 16 == 0
+            and hip_format and weights_dtype not in _HIP_QUANTIZER_SKIP and scale_dtype is None):
+        # the reduction axis moved last: rows (column of the flat matrix | (ci, group, kernel position)) x reduce_len, one row-wise launch
+        # pair of the HIP quantizer; packed integer codes are unpacked, moved back to the reference's element order and packed again
+        # (integer ops: exact) -- a torch division on the device is not correctly rounded, so the restatement below runs on the host
+        from . import ops
+        rows = weight.movedim(dim, -1)
+        moved_shape = rows.shape
+        q, scale, zero_point = ops.quantize_weight(rows.reshape(-1, reduce_len).contiguous(), weights_dtype, reduce_len)
+        if ent["is_packed"]:
+            q = packed.unpack_int(q, weights_dtype, (rows.numel() // reduce_len, reduce_len))
+        q = q.view(moved_shape).movedim(-1, dim).contiguous()
+        scale = scale.view(*moved_shape[:-1], 1).movedim(-1, dim).contiguous()
+        zero_point = None if zero_point is None else zero_point.view(*moved_shape[:-1], 1).movedim(-1, dim).contiguous()
+        quantized_weight_shape = q.shape
+        if ent["is_packed"]:
+            q = packed.pack_int(q, weights_dtype)
+    else:
+        # host tensors, and on the GPU what the HIP quantizer does not take (16-bit scales of dequantize_fp32=False, packed float formats,
+        # formats wider than 8 bits, a reduction length that is no multiple of 16): the torch restatement ON THE HOST, as the reference's
+        # CPU run computes it, and the results moved back -- load-time work
+        dev = weight.device
+        src = weight.cpu() if weight.is_cuda else weight
+        q, scale, zero_point = quantize_weight(src, dim, weights_dtype, dtype=scale_dtype)
+        quantized_weight_shape = q.shape
+        if ent["is_packed"]:
+            q = packed.pack_int(q, weights_dtype) if ent["is_integer"] else packed.pack_float(q, weights_dtype)
+        else:
+            q = q.to(ent["torch_dtype"])
+        if src is not weight:
+            q, scale, zero_point = q.to(dev), scale.to(dev), None if zero_point is None else zero_point.to(dev)
+    dq = SDNQDequantizer(result_dtype=torch_dtype, result_shape=result_shape, original_shape=original_shape,
+                         original_stride=original_stride, quantized_weight_shape=quantized_weight_shape,
+                         weights_dtype=weights_dtype, quantized_matmul_dtype=mm_dtype, hadamard_group_size=hadamard_group_size,
+                         group_size=group_size, svd_rank=svd_rank, svd_steps=svd_steps, codebook_steps=codebook_steps,
+                         use_quantized_matmul=False, re_quantize_for_matmul=bool(requant or groups > 1), use_stochastic_rounding=False,
+                         use_hadamard=False, use_codebook=False, layer_class_name=layer_class_name)
+    return dq, {"weight": q, "scale": scale, "zero_point": zero_point, "svd_up": None, "svd_down": None}
 
 
 def _quantize_codebook_layer(weight: torch.Tensor, dim: int, weights_dtype: str, steps: int, scale_dtype, n: int, k: int, groups: int,
@@ -469,7 +554,7 @@ def _quant_kwargs(cfg: SDNQConfig, torch_dtype, param_name: str, layer_class_nam
 
 def _quantizable_class(name: str, quantization_config: SDNQConfig) -> bool:
     """Layer classes the config quantizes: Linear always, convs with quant_conv, embeddings with quant_embedding."""
-    return (name == "Linear" or (name in ("Conv1d", "Conv2d", "Conv3d") and quantization_config.quant_conv)
+    return (name == "Linear" or (name in ("Conv1d", "Conv2d", "Conv3d", "ConvTranspose1d", "ConvTranspose2d", "ConvTranspose3d") and quantization_config.quant_conv)
             or (name in ("Embedding", "Gemma4TextScaledWordEmbedding") and quantization_config.quant_embedding))
 
 
@@ -523,7 +608,8 @@ def apply_sdnq_to_module(model: torch.nn.Module, quantization_config: SDNQConfig
         if _quantizable_class(cname, quantization_config) and getattr(child, "weight", None) is not None:
             wname = pname + ".weight"
             skip = check_param_name_in(wname, quantization_config.modules_to_not_convert) is not None
-            big = pre_quantized or (child.weight.shape[1 if cname in conv_types else -1] >= quantization_config.minimum_allowed_channel_size
+            # the quantization axis: C_in of a conv weight, shape[0] of a transposed conv's (utils.py:82-87)
+            big = pre_quantized or (child.weight.shape[1 if cname in conv_types else (0 if cname in conv_transpose_types else -1)] >= quantization_config.minimum_allowed_channel_size
                                     and child.weight.numel() >= quantization_config.minimum_allowed_numel)
             if not skip and big and child.weight.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.float64):
                 child, quantization_config = sdnq_quantize_layer(child, quantization_config, torch_dtype=torch_dtype, param_name=wname)

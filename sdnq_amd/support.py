@@ -28,7 +28,7 @@ def unsupported_reason(module) -> str | None:
         return "not an SDNQ layer (no sdnq_dequantizer)"
     cls = getattr(dq, "layer_class_name", None)
     if cls in conv_transpose_types:
-        return f"{cls}: only Linear, Conv1d / Conv2d / Conv3d and Embedding layers are built for MI355X (transposed convolutions are outside SURVEY 8)"
+        return _conv_transpose_reason(module, dq, cls)
     if cls not in linear_types and cls not in conv_types and cls not in embedding_types:
         return f"{cls}: unknown layer class"
     if dq.weights_dtype not in dtype_dict or dq.quantized_matmul_dtype not in dtype_dict:
@@ -95,6 +95,46 @@ def unsupported_reason(module) -> str | None:
                        or (getattr(module, "zero_point", None) is not None and not dq.re_quantize_for_matmul)):
                 return ("grouped conv matmul with 16-bit scales is built for bfloat16 scales on the int8 / fp8 matmul without a weight zero point (float16: the reference "
                         "casts acc * input_scale to float16 before the weight scale, dequantizer.py:27, 63 -- an epilogue of its own)")
+    return None
+
+
+def _conv_transpose_reason(module, dq, cls) -> str | None:
+    """Transposed convolutions (conv_transpose.py): dequantize into the GEMM operand (sdnq_hip_dequant_convt), a float GEMM per conv group
+    with a float32 store, one col2im launch.  Plain quantized weights in every storage format, column scales or the square grouped layout,
+    float32 scales or the 16-bit ones of apply_sdnq_options_to_model(dequantize_fp32=False)."""
+    if dq.weights_dtype not in dtype_dict:
+        return f"unknown dtype {dq.weights_dtype}"
+    if getattr(dq, "use_codebook", False):
+        return f"codebooks on transposed convolutions ({cls}) are not built"
+    if getattr(module, "svd_up", None) is not None or getattr(module, "svd_down", None) is not None:
+        return f"SVD factors on transposed convolutions ({cls}) are not built"
+    if getattr(dq, "use_hadamard", False):
+        return f"Hadamard rotation on transposed convolutions ({cls}) is not built"
+    if isinstance(getattr(module, "padding", 0), str) or getattr(module, "padding_mode", "zeros") != "zeros":
+        return f"string or non-zero padding modes on transposed convolutions ({cls}) are not built (torch's own ConvTransposeNd takes 'zeros' only)"
+    if dq.result_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return f"transposed-conv result dtype {dq.result_dtype} is not built (float32, bfloat16, float16 are)"
+    sdt = _scale_dtype(module)
+    lp = sdt is not None and sdt not in (torch.float32, torch.float64)
+    if lp and sdt != dq.result_dtype:
+        return (f"scale dtype {sdt} differs from the layer's result dtype {dq.result_dtype}: 16-bit scales are built for the layout "
+                "apply_sdnq_options_to_model(dequantize_fp32=False) produces")
+    if sdt == torch.float64:
+        return "float64 scales on transposed convolutions are not built"
+    if lp and dtype_dict[dq.weights_dtype]["num_bits"] > 8:
+        return "16-bit scales with formats wider than 8 bits are not built (the codes are not exact in the scale dtype)"
+    shape = tuple(int(d) for d in dq.original_shape)
+    if len(shape) not in (3, 4, 5):
+        return f"transposed-conv weight of shape {shape}: [C_in, C_out / groups, *kernel] with 1 to 3 kernel axes is expected"
+    groups = int(getattr(module, "groups", 1))
+    p_cols = 1
+    for d in shape[1:]:
+        p_cols *= d
+    if groups < 1 or shape[0] % groups or (shape[0] // groups) % 16:
+        return f"transposed conv needs 16 | C_in / groups (got C_in = {shape[0]}, groups = {groups}): the float GEMM's K"
+    if p_cols % 16:
+        return (f"transposed conv needs 16 | C_out / groups * prod(kernel) (got {p_cols}): the weight kernel decodes 16-element runs of a "
+                "stored row")
     return None
 
 

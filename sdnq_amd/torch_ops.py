@@ -27,6 +27,7 @@ import torch
 from torch.library import custom_op
 
 from . import _lib, ops
+from .common import conv_transpose_types
 
 _MM = {"int8": ops.MM_I8, "fp8": ops.MM_FP8, "float8_e4m3fn": ops.MM_FP8}
 _MM_TORCH = {"int8": torch.int8, "fp8": torch.float8_e4m3fn, "float8_e4m3fn": torch.float8_e4m3fn}
@@ -406,4 +407,15 @@ def _(input, handle):
         ks, st, pd, dl = tuple(int(k) for k in dq.original_shape[2:]), t(mod.stride), t(mod.padding), t(mod.dilation)
         spatial = [(int(input.shape[2 + i]) + 2 * pd[i] - dl[i] * (ks[i] - 1) - 1) // st[i] + 1 for i in range(nd)]
         return input.new_empty((input.shape[0], dq.out_features, *spatial))
+    if dq.layer_class_name in conv_transpose_types:
+        # ConvTranspose1d / 2d / 3d called with one argument (no output_size=): the module's own output_padding, the arithmetic of
+        # torch.nn.functional.conv_transposeNd; weight [C_in, C_out / groups, *kernel]; batched or unbatched input
+        ks = tuple(int(k) for k in dq.original_shape[2:])
+        nd = len(ks)
+        t = lambda v: (int(v),) * nd if isinstance(v, int) else tuple(int(e) for e in v)  # noqa: E731
+        st, pd, dl, op = t(mod.stride), t(mod.padding), t(mod.dilation), t(mod.output_padding)
+        lead = input.ndim - nd  # 2: [B, C_in, *in]; 1: [C_in, *in]
+        spatial = [(int(input.shape[lead + i]) - 1) * st[i] - 2 * pd[i] + dl[i] * (ks[i] - 1) + op[i] + 1 for i in range(nd)]
+        c_out = int(dq.original_shape[1]) * int(mod.groups)
+        return input.new_empty((*input.shape[:lead - 1], c_out, *spatial))
     return input.new_empty((*input.shape[:-1], dq.out_features))
