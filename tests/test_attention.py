@@ -184,11 +184,11 @@ def test_hip_attention_vs_oracle_random(dtype, shape, gpu_device):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["bool", "bf16", "f32"])
 def test_hip_attention_masks_vs_oracle(kind, gpu_device):
-    """Attention masks on the split-key path (2 waves per query tile) and with broadcast dimensions, bf16, against the oracle;
+    """Attention masks on the split-key path (4 key parts per query tile at this shape) and with broadcast dimensions, bf16, against the oracle;
     queries with no visible key return 0 like the reference."""
     import torch
     from sdnq_amd import attention as A
-    z, h, qn, kn, d = 1, 18, 2048, 2100, 64  # 1152 query tiles and kv_len >= 2048: the launcher picks the split-key variant
+    z, h, qn, kn, d = 1, 18, 2048, 2100, 64  # 1152 query tiles (x 2 < 4096) and 66 key blocks: the launcher splits the keys four ways
     g = torch.Generator().manual_seed(11)
     q = torch.randn(z, h, qn, d, generator=g).bfloat16()
     k = torch.randn(z, h, kn, d, generator=g).bfloat16()
