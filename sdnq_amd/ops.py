@@ -390,9 +390,7 @@ class GemmGroup:
                 rows.append((w.data_ptr() + loc * self.k, ws.data_ptr() + 4 * loc,
                              0 if bias is None else bias.data_ptr() + loc * bias.element_size(), n_start, n, loc))
             n_start += n
-        dt = np.dtype([("b", "<u8"), ("sb", "<u8"), ("bias", "<u8"), ("n_start", "<i8"), ("n_seg", "<i4"), ("n_loc", "<i4")])
-        assert dt.itemsize == ctypes.sizeof(_lib.SdnqGemmUnit)
-        table = np.array(rows, dtype=dt)
+        table = np.array(rows, dtype=np.dtype(_lib.SdnqGemmUnit))  # b, sb, bias, n_start, n_seg, n_loc: the struct's own layout
         self.device = members[0][0].device
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
         self.n_units, self.unit_n, self.n_total = len(rows), unit, n_start

@@ -1,17 +1,11 @@
 """The C-ABI shared library loads (no GPU needed) and exports every symbol include/sdnq_hip.h declares."""
 import ctypes
-import os
-import re
+import subprocess
 
-from sdnq_amd import _lib
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    hdr = open(os.path.join(ROOT, "include", "sdnq_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdnq_hip_[a-z0-9_]+)\s*\(", hdr)))
+from sdnq_amd import _abi, _lib
+from tests.header_util import INCLUDE, declared_arity, declared_symbols, struct_field_names
 
 
 def test_library_exports_every_declared_symbol():
@@ -279,23 +273,8 @@ def test_bf16_uint8_matmul_argument_validation_without_gpu():
 
 
 def test_linear_args_struct_matches_the_header():
-    """The ctypes mirror of SdnqLinearArgs has the header's field order and the size the library checks (struct_size)."""
-    import ctypes
-    import re
-    from sdnq_amd import _lib
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sdnq_hip.h")).read()
-    body = hdr[hdr.index("typedef struct SdnqLinearArgs {"):hdr.index("} SdnqLinearArgs;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        parts = decl.replace("*", " ").split()
-        for nm in decl.split(",") if "," in decl else [decl]:
-            names.append(nm.replace("*", " ").split()[-1])
-        del parts
-    assert names == [f[0] for f in _lib.SdnqLinearArgs._fields_], names
+    """The ctypes class of SdnqLinearArgs has the header's field order and the size the library checks (struct_size)."""
+    assert struct_field_names("SdnqLinearArgs") == [f[0] for f in _lib.SdnqLinearArgs._fields_]
     assert ctypes.sizeof(_lib.SdnqLinearArgs) == 10 * 4 + 4 * 8 + 16 * 8
 
 
@@ -349,8 +328,89 @@ def test_scaled_mm_tile_is_a_dry_run_of_the_shape_rules():
 
 def test_every_export_has_declared_argument_types():
     """ctypes converts an undeclared Python int to a 32-bit C int: a device pointer or an int64 size would be truncated silently (round 6:
-    a new entry point without argtypes sent truncated pointers to the GPU).  Every export must carry argtypes."""
+    a new entry point without argtypes sent truncated pointers to the GPU).  Every export must carry argtypes, as many as its prototype
+    has parameters."""
     lib = _lib.load()
     raw = getattr(lib, "_ctypes", lib)
-    missing = [name for name in _lib.EXPORTS if name not in ("sdnq_hip_version",) and getattr(raw, name).argtypes is None]
-    assert missing == [], missing
+    arity = declared_arity()
+    assert sorted(arity) == sorted(_lib.EXPORTS)
+    wrong = [name for name in _lib.EXPORTS if getattr(raw, name).argtypes is None or len(getattr(raw, name).argtypes) != arity[name]]
+    assert wrong == [], wrong
+
+
+def test_the_c_compiler_accepts_everything_read_from_the_header():
+    """What sdnq_amd/_abi.py read goes back to the compiler that builds csrc/binding.c, beside the header itself: every prototype in the
+    reader's own spellings must be the declared type, every spelling must have the size of its ctypes type, every struct field the offset
+    and size the ctypes class gives it, every enum constant its value.  A prototype, parameter or field that the reader dropped,
+    reordered or misread does not compile."""
+    hdr = _lib._ABI
+    lines = ["#include <stddef.h>", '#include "sdnq_hip.h"']
+    for ret, name, params in hdr.prototypes:
+        lines.append(f'_Static_assert(__builtin_types_compatible_p(__typeof__(&{name}), {ret} (*)({", ".join(params) or "void"})), "{name}");')
+        restype, argtypes = hdr.signatures[name]
+        for spelling, ctype in zip([ret] + params, [restype] + argtypes):
+            if ctype is not None:
+                lines.append(f'_Static_assert(sizeof({spelling}) == {ctypes.sizeof(ctype)}, "{spelling} in {name}");')
+    for struct, cls in hdr.classes.items():
+        assert [f[0] for f in cls._fields_] == [f[0] for f in hdr.structs[struct]]
+        lines.append(f'_Static_assert(sizeof({struct}) == {ctypes.sizeof(cls)}, "{struct}");')
+        for field, _ in hdr.structs[struct]:
+            at = getattr(cls, field)
+            lines.append(f'_Static_assert(offsetof({struct}, {field}) == {at.offset} && sizeof((({struct}*)0)->{field}) == {at.size}, "{struct}.{field}");')
+    lines += [f'_Static_assert({name} == {value}, "{name}");' for name, value in hdr.enums.items()]
+    assert len(hdr.prototypes) == len(declared_symbols()) and len(hdr.classes) == 3 and len(hdr.enums) >= 25
+    cc = subprocess.run(["gcc", "-fsyntax-only", "-Werror", "-I" + INCLUDE, "-x", "c", "-"], input="\n".join(lines) + "\n", text=True,
+                        capture_output=True)
+    assert cc.returncode == 0, cc.stderr
+
+
+@pytest.mark.parametrize("text, line, what", [
+    ("int sdnq_hip_a(int x);\nint sdnq_hip_b(long n);\n", 2, "'long'"),                        # a parameter type outside the table
+    ("int sdnq_hip_a(int x);\n\nsize_t sdnq_hip_b(int x);\n", 3, "'size_t'"),                   # ... a return type
+    ("int sdnq_hip_a(int x);\nint sdnq_hip_b(void (*cb)(int), int x);\n", 2, "sdnq_hip_b"),     # a declaration the prototype pattern misses
+    ("int sdnq_hip_a(int x);\nint sdnq_hip_b(int x)\n{ return x; }\n", 2, "sdnq_hip_b"),
+    ("int sdnq_hip_a(int);\n", 1, "not `type name`"),
+    ("typedef struct S {\n    int32_t n;\n    float v[4];\n} S;\n", 3, "v[4]"),                  # an array field
+    ("typedef struct S {\n    int32_t n : 3;\n} S;\n", 2, "n : 3"),                            # a bit-field
+    ("typedef struct S {\n    /* c */ short n;\n} S;\n", 2, "'short'"),                        # a field type outside the table
+    ("int sdnq_hip_a(const SdnqWeight* w);\n", 1, "SdnqWeight"),                               # a typed pointer whose struct was not read
+    ("typedef enum E { SDNQ_A = 0, SDNQ_B } E;\n", 1, "SDNQ_B"),                               # a constant the reader would have to count
+])
+def test_the_header_reader_fails_closed(text, line, what):
+    with pytest.raises(_abi.SdnqHipError) as e:
+        _abi.Header(text)
+    assert f"line {line}:" in str(e.value) and what in str(e.value), str(e.value)
+
+
+def test_the_header_reader_on_a_small_header():
+    hdr = _abi.Header("/* int sdnq_hip_no(int x); */\n#define N 4\ntypedef enum E { SDNQ_A = 0, SDNQ_B = -2 } E; // c\n"
+                      "typedef struct SdnqWeight {\n  const void * weight;\n  int64_t m, n;\n} SdnqWeight;\n"
+                      "int64_t sdnq_hip_a(const SdnqWeight *w,\n  void * const *outs, unsigned long long* id);\nvoid sdnq_hip_b(void);\n")
+    assert hdr.enums == {"SDNQ_A": 0, "SDNQ_B": -2}
+    assert hdr.structs == {"SdnqWeight": [("weight", "const void*"), ("m", "int64_t"), ("n", "int64_t")]}
+    assert hdr.prototypes == [("int64_t", "sdnq_hip_a", ["const SdnqWeight*", "void* const*", "unsigned long long*"]), ("void", "sdnq_hip_b", [])]
+    W = hdr.classes["SdnqWeight"]
+    assert W._fields_ == [("weight", ctypes.c_void_p), ("m", ctypes.c_int64), ("n", ctypes.c_int64)]
+    assert hdr.signatures == {"sdnq_hip_a": (ctypes.c_int64, [ctypes.POINTER(W), ctypes.c_void_p, ctypes.c_void_p]), "sdnq_hip_b": (None, [])}
+
+
+def test_spot_table_of_declared_types():
+    """Eight prototypes against expectations written by hand from the header; between them and the struct every row of the type table."""
+    c = ctypes
+    vp, i, i64, u64, f32 = c.c_void_p, c.c_int, c.c_int64, c.c_uint64, c.c_float
+    want = {
+        "sdnq_hip_strerror": (c.c_char_p, [i]),
+        "sdnq_hip_set_tile_override": (None, [i]),
+        "sdnq_hip_dequant_loss_workspace_bytes": (i64, [i64, i64]),
+        "sdnq_hip_embedding": (i, [vp, i, vp, i, i64, i, c.c_double, vp, i, vp]),  # argument 0 by address, not POINTER(SdnqWeight)
+        "sdnq_hip_push_post": (i, [vp, i, i, u64, u64, vp]),
+        "sdnq_hip_scaled_mm_tile": (i, [i, i, i, i64, i64, i64, vp, vp, vp, vp]),
+        "sdnq_hip_adamw_step": (i, [vp, vp, vp, vp, i, i64] + [f32] * 7 + [vp, i, i, u64, u64, vp]),
+        "sdnq_hip_linear": (i, [c.POINTER(_lib.SdnqLinearArgs), vp]),
+    }
+    raw = getattr(_lib.load(), "_ctypes", _lib.load())
+    for name, (restype, argtypes) in want.items():
+        fn = getattr(raw, name)
+        assert fn.restype == restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
+    assert _lib._ABI.signatures["sdnq_hip_embedding"][1][0] == c.POINTER(_lib.SdnqWeight) == raw.sdnq_hip_dequant.argtypes[0]
+    assert _lib.SdnqWeight._fields_[4:6] == [("svd_down", vp), ("n", c.c_int32)] and list(raw.sdnq_hip_version.argtypes) == []

@@ -3,14 +3,12 @@ predicate, the wrapper classes, the loader on a reference-written checkpoint, an
 import ctypes
 import json
 import os
-import re
 
 import pytest
 import torch
 
 from tests import convt_util as U
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.header_util import declared_arity
 
 
 @pytest.mark.parametrize("name", U.NAMES)
@@ -206,12 +204,6 @@ def test_hf_quantizer_converts_transposed_convs():
     assert tuple(skel.up.weight.shape) == (64, 32, 4, 4) and skel.up.weight.dtype == torch.int8 and tuple(skel.up.scale.shape) == (1, 32, 4, 4)
 
 
-def _declared():
-    hdr = open(os.path.join(ROOT, "include", "sdnq_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(sdnq_hip_[a-z0-9_]+)\s*\(([^;]*)\)\s*;", hdr)}
-
-
 NEW = ("sdnq_hip_dequant_convt", "sdnq_hip_linear_float_f32out", "sdnq_hip_linear_float_f32out_strided", "sdnq_hip_col2im")
 
 
@@ -219,13 +211,13 @@ def test_header_prototypes_equal_the_exports():
     """Every new entry point is declared in include/sdnq_hip.h, listed in _lib.EXPORTS, exported by the library, and bound with as many
     ctypes arguments as the prototype has parameters."""
     from sdnq_amd import _lib
-    decl = _declared()
+    decl = declared_arity()
     lib = _lib.load()
     raw = getattr(lib, "_ctypes", lib)
     for name in NEW:
         assert name in decl and name in _lib.EXPORTS, name
         fn = getattr(raw, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == len([a for a in decl[name].split(",") if a.strip()]), name
+        assert fn.argtypes is not None and len(fn.argtypes) == decl[name], name
     units = [u[0] for u in __import__("sdnq_amd._build", fromlist=["UNITS"]).UNITS]
     assert "convt" in units
 
