@@ -798,6 +798,23 @@ int sdnq_hip_col2im(const float* cols, int64_t ldcols, const void* bias, int dty
                     int in_h, int in_w, int out_d, int out_h, int out_w, int kd, int kh, int kw, int stride_d, int stride_h,
                     int stride_w, int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w, sdnq_stream_t stream);
 
+/* ---- input gradients through frozen quantized Linear layers: the transposed weight operand ----------------------------------------------
+ * replaces the weight side of QuantizedLinearBackward (training/layers/linear/forward.py): grad_input = grad_output @ weight.dequantize().
+ * The product reduces over N and sdnq_hip_linear_float wants both operands contiguous along the reduction, so the weight is needed as
+ * [K][N]; it is decoded into a scratch buffer of the caller's per call, no float copy per layer.
+ *
+ * sdnq_hip_dequant_t: out[k][n] = the value sdnq_hip_dequant(w, 0, ..) writes to out[n][k], bit for bit (the same per-element code:
+ *   every storage format, group scales, zero points, codebooks, scale_dtype), for a weight WITHOUT SVD factors and without a Hadamard
+ *   rotation.  out: [K][N] contiguous of out_dtype, 16-byte aligned.  Built for K % 16 == 0 and N % 8 == 0; any other shape and a
+ *   descriptor with SVD factors: SDNQ_ERR_UNSUPPORTED.  One launch, no atomics, no workspace.
+ *
+ * sdnq_hip_transpose2d: out[c][r] = x[r][c] for a matrix of `dtype` (SdnqFloat), row stride ldx elements, out [c][r] contiguous.  The route
+ *   of layers with SVD factors or a Hadamard rotation: sdnq_hip_dequant writes their full weight (SVD product added, rotation undone) and
+ *   this transposes it -- one more pass over the weight, the same bits.  r % 8 == 0, c % 8 == 0, ldx >= c; x, out and the rows of x
+ *   16-byte aligned. */
+int sdnq_hip_dequant_t(const SdnqWeight* w, void* out, int out_dtype, sdnq_stream_t stream);
+int sdnq_hip_transpose2d(const void* x, int dtype, int64_t r, int64_t c, int64_t ldx, void* out, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

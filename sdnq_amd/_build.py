@@ -52,6 +52,7 @@ UNITS = (
     ("quantize", "", None),
     ("conv", _PRELOAD, None),
     ("convt", "", None),
+    ("dequant_t", "", None),
     # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them
     # with VALU every block; in AGPR form the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),

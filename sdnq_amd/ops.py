@@ -622,6 +622,48 @@ def dequant(qw: QuantWeight, out_dtype: torch.dtype, hadamard_group: int = 0, us
     return out
 
 
+def dequant_t(qw: QuantWeight, out_dtype: torch.dtype, out: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_dequant_t: the dequantized weight transposed, [K, N] contiguous -- ``dequant(qw, out_dtype, 0, use_svd=False).t()`` bit
+    for bit, decoded from the stored codes in one launch.  No SVD factors, K % 16 == 0 and N % 8 == 0 (anything else raises)."""
+    dev = qw.keep[0].device
+    if out is None:
+        out = torch.empty((qw.k, qw.n), device=dev, dtype=out_dtype)
+    elif out.dtype != out_dtype or out.numel() != qw.n * qw.k or not out.is_contiguous():
+        raise _lib.SdnqHipError(f"dequant_t: out must be {qw.k * qw.n} contiguous elements of {out_dtype}")
+    check(_lib.load().sdnq_hip_dequant_t(ctypes.byref(qw.desc), out.data_ptr(), float_code(out_dtype), _stream(out)), "dequant_t")
+    return out.view(qw.k, qw.n)
+
+
+def transpose2d(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_transpose2d: x [R, C] (unit column stride, any row stride) -> [C, R] contiguous, the same bits."""
+    _require_cuda(x, out)
+    if x.ndim != 2 or x.stride(1) != 1:
+        raise _lib.SdnqHipError(f"transpose2d takes a 2-D tensor with contiguous rows (got shape {tuple(x.shape)}, strides {x.stride()})")
+    r, c = x.shape
+    if out is None:
+        out = torch.empty((c, r), device=x.device, dtype=x.dtype)
+    elif out.dtype != x.dtype or out.numel() != r * c or not out.is_contiguous():
+        raise _lib.SdnqHipError(f"transpose2d: out must be {r * c} contiguous elements of {x.dtype}")
+    check(_lib.load().sdnq_hip_transpose2d(x.data_ptr(), float_code(x.dtype), r, c, x.stride(0), out.data_ptr(), _stream(x)), "transpose2d")
+    return out.view(c, r)
+
+
+def weight_t(qw: QuantWeight, out_dtype: torch.dtype, hadamard_group: int, scratch) -> torch.Tensor:
+    """The weight a layer's forward multiplies by -- SVD product added, Hadamard rotation undone: the reference's weight.dequantize() --
+    as the [K, N] operand of grad_input = linear_float(dY, weight_t), written into `scratch` and returned as a view of it.
+    scratch: (first, second), 1-D tensors of `out_dtype` with at least N * K elements each; `second` may be None for a plain layer.
+    A plain layer is decoded transposed in one launch (dequant_t); a layer with SVD factors or a rotation is dequantized into `second` by
+    the kernels of its forward (dequant) and transposed into `first` (transpose2d): one more pass, the same bits."""
+    first, second = scratch
+    nk = qw.n * qw.k
+    if not qw.desc.svd_up and not hadamard_group:
+        return dequant_t(qw, out_dtype, out=first[:nk])
+    if second is None:
+        raise _lib.SdnqHipError("weight_t: a layer with SVD factors or a Hadamard rotation needs the second scratch buffer")
+    wd = dequant(qw, out_dtype, hadamard_group, out=second[:nk].view(qw.n, qw.k))
+    return transpose2d(wd, out=first[:nk])
+
+
 def make_convt_weight(weights_dtype: str, weight: torch.Tensor, scale: torch.Tensor, zero_point, c_in: int, p_cols: int, kprod: int) -> QuantWeight:
     """The stored tensors of a transposed-conv layer ([C_in, C_out / groups, *kernel] codes or their packed form, element order
     [C_in][P]) as the descriptor sdnq_hip_dequant_convt reads: n = C_in, k = P = C_out / groups * prod(kernel), positions = prod(kernel).

@@ -14,6 +14,9 @@ the forward and saves only those int8 codes and float32 scales; its results are 
 Built: plain float weights (float32 / bfloat16 / float16), N % 16 == 0 and K % 16 == 0.  Everything else the reference's training
 package offers raises NotImplementedError naming the configuration; there is no float fallback except the reference's own rule for fewer
 than 32 rows (linear_int8_dynamic.py:209-215).  Nothing here synchronises with the host: a forward + backward can be stream-captured.
+
+The second half of the module is the other way of training on this package: adapters on a FROZEN quantized model --
+``enable_input_grad(model)`` / ``QuantizedLinearInputGrad``, the input gradient through an accelerated quantized Linear layer.
 """
 from __future__ import annotations
 
@@ -201,3 +204,174 @@ NOT_BUILT = {
     "fp16_matmul_dynamic_with_backward_ckpt": "the dynamic fp16 training matmul (linear_fp16_dynamic_ckpt.py)",
 }
 globals().update({name: _not_built(name, what) for name, what in NOT_BUILT.items()})
+
+
+# ---- input gradients through FROZEN quantized Linear layers (adapters on a quantized model) ---------------------------------------------
+# The reference's QuantizedLinearBackward (training/layers/linear/forward.py): the forward is the layer, grad_input = grad_output @
+# weight.dequantize().  Here the forward is the layer's own accelerated forward_func -- whatever it is: w8a8, fp8, uint8, float16 matmul,
+# dequantize mode, the few-row branch, plans, linked projections -- so its output bits are the inference call's, and the backward decodes
+# the stored codes transposed into ONE scratch buffer per device (ops.weight_t) and runs the float GEMM on it.  No float copy per layer:
+# peak extra memory is one float copy of the LARGEST layer seen (two when a layer has SVD factors or a Hadamard rotation).
+_SCRATCH = {}  # device index -> [first, second | None]: uint8 buffers, grown to the largest layer seen and reused by every layer
+
+
+def _scratch(dev: torch.device, dtype: torch.dtype, numel: int, two: bool):
+    """(first, second | None) as 1-D tensors of `dtype` with at least `numel` elements.  `second` exists once a layer with SVD factors or a
+    Hadamard rotation was seen and then has the size of `first`.  The buffers are used in stream order by the stream the backward runs on
+    (autograd runs a node's backward on its forward's stream); a model whose backwards run on several streams at once is not served."""
+    nbytes = numel * dtype.itemsize
+    bufs = _SCRATCH.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [None, None])
+    have = 0 if bufs[0] is None else bufs[0].numel()
+    want = max(have, nbytes)
+    grow = [i for i in range(2) if (i == 0 or two or bufs[1] is not None) and (bufs[i] is None or bufs[i].numel() < want)]
+    if grow and torch.cuda.is_current_stream_capturing():
+        raise _lib.SdnqHipError("input-gradient scratch: run one eager backward before capturing a graph (the buffer is not sized yet)")
+    for i in grow:
+        bufs[i] = None  # (the old block goes back to the allocator before the new one is taken)
+        bufs[i] = torch.empty(want, device=dev, dtype=torch.uint8)
+    return bufs[0].view(dtype), (None if bufs[1] is None else bufs[1].view(dtype))
+
+
+def scratch_bytes(device=None) -> int:
+    """Bytes the input-gradient scratch holds on `device` (default: the current one)."""
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    return sum(b.numel() for b in _SCRATCH.get(idx, ()) if b is not None)
+
+
+def release_scratch() -> None:
+    _SCRATCH.clear()
+
+
+class QuantizedLinearInputGrad(torch.autograd.Function):
+    """y = layer(input) with a graph: grad_input = dY . W, where W is the weight the layer's forward multiplies by (SVD product added,
+    Hadamard rotation undone).  grad_bias = dY.sum(0) when the bias requires grad; the weight, scale, zero point and SVD factors are
+    frozen and get none.  Saves the module and the input shape, no tensor.  Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, layer, input, bias=None):
+        if not input.is_cuda:
+            raise _lib.SdnqHipError("input gradients through a quantized Linear need the input on a gfx950 device (got a CPU tensor); "
+                                    "there is no CPU path")
+        ctx.layer, ctx.input_shape = layer, input.shape
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        with torch.no_grad():  # (autograd has switched gradients off here already: the layer takes the very path of an inference call)
+            return layer.forward_func(layer, input)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        from . import linear
+        layer = ctx.layer
+        dq = layer.sdnq_dequantizer
+        if grad_output.dtype != dq.result_dtype:
+            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
+                                      f"{dq.result_dtype}: the backward GEMM runs in the layer's dtype")
+        if not grad_output.is_cuda:
+            raise _lib.SdnqHipError("input gradients through a quantized Linear need grad_output on a gfx950 device (got a CPU tensor)")
+        g2d = _rows(grad_output)
+        grad_input = grad_bias = None
+        if ctx.needs_input_grad[1]:
+            if g2d.shape[0] == 0:
+                grad_input = grad_output.new_zeros(ctx.input_shape)
+            else:
+                qw = linear._state(layer).qw
+                had = dq.hadamard_group_size if dq.use_hadamard else 0
+                scratch = _scratch(g2d.device, g2d.dtype, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)
+                grad_input = ops.linear_float(g2d, ops.weight_t(qw, g2d.dtype, had, scratch), None).view(ctx.input_shape)
+        if ctx.needs_input_grad[2]:
+            grad_bias = g2d.sum(0).to(ctx.bias_dtype)
+        return None, grad_input, grad_bias
+
+
+def quantized_linear_input_grad(layer, input: torch.Tensor) -> torch.Tensor:
+    """`layer(input)` -- the output bits of the inference call -- with grad_input (and grad_bias) flowing back through the frozen layer."""
+    from .linear import _attr
+    return QuantizedLinearInputGrad.apply(layer, input, _attr(layer, "bias"))
+
+
+def input_grad_unsupported_reason(module) -> str | None:
+    """None when `enable_input_grad` serves `module` (an SDNQ layer); otherwise the sentence that says why not."""
+    from .common import linear_types
+    from .support import unsupported_reason
+    dq = module.sdnq_dequantizer
+    cls = getattr(dq, "layer_class_name", None)
+    if cls not in linear_types:
+        return f"{cls}: input gradients are built for quantized Linear layers (conv, transposed-conv and embedding layers are not)"
+    why = unsupported_reason(module)
+    if why is not None:
+        return why
+    fwd = getattr(module, "forward_func", None)
+    if getattr(fwd, "__module__", None) not in ("sdnq_amd.linear", __name__):
+        return "the layer does not run on the MI355X forwards (call sdnq_amd.accelerate(model) first)"
+    n, k = dq.out_features, dq.in_features
+    if k % 16 or n % 8:
+        return f"input gradients need 16 | K and 8 | N (got K = {k}, N = {n}): the transposed weight leaves in 16-byte runs"
+    if dq.result_dtype not in _FLOATS:
+        return f"layer dtype {dq.result_dtype} is not built for input gradients (float32, bfloat16, float16 are)"
+    return None
+
+
+def _with_input_grad(fwd):
+    grad_on = torch.is_grad_enabled
+
+    def forward(self, input):
+        if grad_on() and input.requires_grad:
+            return quantized_linear_input_grad(self, input)  # (its forward comes back here with gradients off)
+        return fwd(self, input)
+    forward.__name__ = forward.__qualname__ = getattr(fwd, "__name__", "forward") + "_with_input_grad"
+    forward._sdnq_inference_forward = fwd
+    return forward
+
+
+class InputGradResult(int):
+    """What `enable_input_grad()` returns: an int (the number of layers switched) that also carries `.enabled` and `.skipped` --
+    [(qualified module name, reason)] of the SDNQ layers that still cut the graph."""
+
+    def __new__(cls, enabled: int, skipped):
+        r = super().__new__(cls, enabled)
+        r.enabled, r.skipped = int(enabled), list(skipped)
+        return r
+
+    def __iter__(self):  # `n, skipped = enable_input_grad(model)`
+        return iter((self.enabled, self.skipped))
+
+
+def enable_input_grad(model: torch.nn.Module, enabled: bool = True) -> InputGradResult:
+    """Let gradients flow to what is upstream of the frozen quantized Linear layers of an accelerated `model` (adapters, LoRA).
+
+    Wraps the ``forward_func`` of every accelerated quantized Linear: a call made with gradients enabled on an input that requires grad
+    goes through ``QuantizedLinearInputGrad`` (same output bits, grad_input = dY . W on HIP kernels, no float weight kept); every other
+    call takes the forward the layer had, plans included, for the price of one Python check.  Conv, transposed-conv and embedding layers,
+    layers with K % 16 != 0 or N % 8 != 0 and layers outside float32 / bfloat16 / float16 are left alone and listed in ``.skipped`` and in
+    ONE ``warnings.warn``: the graph is still cut there.  ``enabled=False`` puts the forwards back.  Re-pointing a layer's forward
+    afterwards (``apply_sdnq_options_to_model``, ``accelerate``) drops the switch for that layer.  Out of scope: ``torch.compile`` of the
+    wrapped forward and double backward."""
+    count, skipped = 0, []
+    for name, module in model.named_modules():
+        if getattr(module, "sdnq_dequantizer", None) is None:
+            continue
+        fwd = getattr(module, "forward_func", None)
+        inner = getattr(fwd, "_sdnq_inference_forward", None)
+        if not enabled:
+            if inner is not None:
+                module.forward_func = inner
+                count += 1
+            continue
+        if inner is not None:  # switched already
+            count += 1
+            continue
+        try:
+            why = input_grad_unsupported_reason(module)
+        except Exception as e:  # noqa: BLE001  a foreign record the predicate cannot read: leave the layer alone
+            why = f"{type(e).__name__} while reading the layer's record: {e}"
+        if why is not None:
+            skipped.append((name or type(module).__name__, why))
+            continue
+        module.forward_func = _with_input_grad(fwd)
+        count += 1
+    if skipped:
+        import warnings
+        warnings.warn(f"sdnq_amd.enable_input_grad: {len(skipped)} SDNQ layer(s) still cut the autograd graph (nothing upstream of them "
+                      "receives a gradient): " + "; ".join(f"{n} ({w})" for n, w in skipped[:8]) + (" ..." if len(skipped) > 8 else ""),
+                      stacklevel=2)
+    return InputGradResult(count, skipped)
