@@ -763,6 +763,35 @@ int sdnq_hip_adamw_step_q8(void* param, const void* grad, int dtype, int64_t num
                            float w2, float bc1, float bc2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
                            uint64_t seed, uint64_t offset, sdnq_stream_t stream);
 
+/* ---- optimizer: the fused AdamW step on many tensors ---------------------------------------------------------------------------------
+ * replaces `count` calls of sdnq_hip_adamw_step / sdnq_hip_adamw_step_q8 -- the loop over a parameter group in SDNQOptimizer.step
+ * (optim/optimizer.py:97-139) -- by one launch per sdnq_hip_adamw_multi_capacity(quantized) tensors: a few workgroups per launch is
+ * all that a set of small tensors (adapters, biases, norms) gives the single-tensor call.  Tensor i is updated as
+ *     sdnq_hip_adamw_step(params[i], grads[i], exp_avgs[i], exp_avg_sqs[i], dtype, numels[i], lr, w1, w2, bc1[i], bc2[i], clip, decay,
+ *                         grad_scale, sr_param, sr_state, seed, offsets[i], stream)
+ * would update it, BIT FOR BIT, random bits included: a workgroup works on 2048 consecutive elements of one tensor with indices
+ * relative to that tensor's start, and the random bits of an element depend on (seed, offsets[i], its index in its tensor) alone.
+ * dtype, lr, w1, w2, clip, decay, grad_scale, sr_param, sr_state and seed are shared; bc1, bc2 (tensors of one call may be at different
+ * steps) and the Philox offset are per tensor.  The tensors must not overlap.
+ * The arrays are HOST arrays of `count` entries, owned by the caller and read during the call only: the table of a launch travels by
+ * value in its kernel arguments.  No workspace, no atomics, no host-to-device copy; capturable in a graph as the single-tensor call is;
+ * the same bits on every call.  The library cuts `count` into launches of at most the capacity; count == 0 is SDNQ_OK without a launch.
+ * Everything is validated for ALL tensors before the first launch, by the single-tensor rules: a NULL array or element SDNQ_ERR_NULL;
+ * dtype SDNQ_ERR_DTYPE; count < 0, numels[i] <= 0 (or % 32 != 0 with uint8 state), or a launch of more than 2^31 - 1 workgroups
+ * SDNQ_ERR_SHAPE; param / grad / state of a tensor with numels[i] >= 8 (any tensor with uint8 state) not 16-byte aligned, scale / zero
+ * point / grad_scale not 4-byte aligned SDNQ_ERR_ALIGN; a scalar, bc1[i] or bc2[i] that is not finite SDNQ_ERR_UNSUPPORTED.
+ * sdnq_hip_adamw_multi_capacity: tensors per launch with dense (0) / uint8 (non-zero) state; needs no device. */
+int sdnq_hip_adamw_multi_capacity(int quantized);
+int sdnq_hip_adamw_step_multi(int64_t count, void* const* params, const void* const* grads, void* const* exp_avgs,
+                              void* const* exp_avg_sqs, const int64_t* numels, const float* bc1, const float* bc2,
+                              const uint64_t* offsets, int dtype, float lr, float w1, float w2, float clip, float decay,
+                              const float* grad_scale, int sr_param, int sr_state, uint64_t seed, sdnq_stream_t stream);
+int sdnq_hip_adamw_step_multi_q8(int64_t count, void* const* params, const void* const* grads, void* const* exp_avg_qs,
+                                 void* const* exp_avg_scales, void* const* exp_avg_zps, void* const* exp_avg_sq_qs,
+                                 void* const* exp_avg_sq_scales, void* const* exp_avg_sq_zps, const int64_t* numels, const float* bc1,
+                                 const float* bc2, const uint64_t* offsets, int dtype, float lr, float w1, float w2, float clip,
+                                 float decay, const float* grad_scale, int sr_param, int sr_state, uint64_t seed, sdnq_stream_t stream);
+
 /* ---- transposed convolutions: GEMM + col2im -------------------------------------------------------------------------------------------
  * replaces quantized_conv_transpose_{1,2,3}d_forward (layers/conv/forward.py:85-99): F.conv_transposeNd(x, dequantize(W), bias, stride,
  * padding, output_padding, groups, dilation) on a weight [C_in][C_out / groups][k...].  Per conv group the product

@@ -1,4 +1,5 @@
-// Fused AdamW step for gfx950: one launch per parameter tensor, one pass over the parameter, everything in float32 registers.
+// Fused AdamW step for gfx950: one launch per parameter tensor, or per table of small ones, one pass over the parameter, everything in
+// float32 registers.
 //
 // Reference chain replaced (about 25 elementwise torch passes per parameter there, plus a dequantize and a re-quantize of two buffers
 // when the state is quantized; ONE launch here):
@@ -35,6 +36,19 @@
 // NaN: fminf / fmaxf drop a NaN operand, so the clamps here turn a NaN into a bound where torch's clamp keeps it; every clamp of the
 // chain follows a nan_to_num, so none sees one.  A group whose min equals its max gets scale 0 and codes 0 (0 / 0 cast to uint8 in the
 // reference, see quant_pack_kernel in quantize.hip).
+//
+// Many tensors in one launch (adamw_dense_multi_kernel, adamw_q8_multi_kernel): a block is still 2048 consecutive elements of ONE
+// tensor, the grid is the tensors' block ranges one after the other.  The table of tensors -- per tensor its pointers, numel, bc1, bc2
+// and Philox offset, and in a column of its own the tensor's first block -- travels BY VALUE in the kernel arguments beside the shared
+// scalars: no device-side table, no workspace, no copy, so the call is captured like the single-tensor one.  blockIdx.x is uniform, so
+// the binary search over the first-block column and the reads of the record are scalar loads from the argument segment.  A block then
+// fills an AdamWScalars and runs the single-tensor chain with indices relative to its tensor's start: the bits of
+// sdnq_hip_adamw_step(_q8) on that tensor alone, random bits included (they depend on seed, offset and the element index only).
+// Capacity: HIP documents 4096 bytes of kernel arguments.  hipcc enforces nothing (a 64 KB by-value argument compiles without a
+// diagnostic), so the bound is a static_assert here, and it leaves room for the whole argument segment: 4096 less the 256 bytes of implicit
+// arguments the compiler appends to a kernel that uses them (these do not) = 3840.  The shared scalars take 48, a tensor 56 + 4 (dense: four pointers) or 88 + 4 (uint8 state:
+// eight), which gives (3840 - 48) / 60 = 63 and (3840 - 48) / 92 = 41 tensors per launch.  The entry points cut a longer list into
+// launches.
 #include "sdnq_dev.h"
 
 namespace {
@@ -282,6 +296,134 @@ __global__ __launch_bounds__(AW_BLOCK) void adamw_q8_kernel(void* __restrict__ p
     }
 }
 
+// ---- many tensors in one launch ------------------------------------------------------------------------------------------------------
+struct AwShared {
+    float neg_lr, w1, w2, clip, decay;
+    int count;                // tensors in this launch, 1 .. capacity
+    const float* grad_scale;  // device, one float32, or NULL
+    u32 seed_lo, seed_hi;
+    int sr_param, sr_state;
+};
+struct AwDenseRec {
+    void* param; const void* grad; void* exp_avg; void* exp_avg_sq;
+    int64_t numel;
+    uint64_t offset;
+    float bc1, bc2;
+};
+struct AwQ8Rec {
+    void* param; const void* grad;
+    uint8_t* m_q; float* m_scale; float* m_zp;
+    uint8_t* v_q; float* v_scale; float* v_zp;
+    int64_t numel;
+    uint64_t offset;
+    float bc1, bc2;
+};
+constexpr int AW_KERNARG_BYTES = 4096 - 256;  // the documented 4 KB less 256 bytes of implicit arguments
+template <class Rec>
+struct AwTable {
+    static constexpr int CAP = (AW_KERNARG_BYTES - (int)sizeof(AwShared)) / (int)(sizeof(Rec) + sizeof(u32));
+    AwShared s;
+    Rec rec[CAP];
+    u32 first[CAP];  // the tensor's first block: ascending, first[0] == 0
+};
+static_assert(sizeof(AwTable<AwDenseRec>) <= AW_KERNARG_BYTES && AwTable<AwDenseRec>::CAP == 63, "dense table: 63 tensors");
+static_assert(sizeof(AwTable<AwQ8Rec>) <= AW_KERNARG_BYTES && AwTable<AwQ8Rec>::CAP == 41, "uint8-state table: 41 tensors");
+
+// the tensor that block `b` belongs to: the last i with first[i] <= b.  Uniform over the block: scalar loads, at most 6 rounds
+template <class Rec>
+__device__ __forceinline__ int aw_find(const AwTable<Rec>& t, u32 b) {
+    int lo = 0, hi = t.s.count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t.first[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+template <class Rec>
+__device__ __forceinline__ AdamWScalars aw_scalars_of(const AwShared& s, const Rec& r) {
+    AdamWScalars a;
+    a.neg_lr = s.neg_lr; a.w1 = s.w1; a.w2 = s.w2; a.bc1 = r.bc1; a.bc2 = r.bc2; a.clip = s.clip; a.decay = s.decay;
+    a.grad_scale = s.grad_scale;
+    a.seed_lo = s.seed_lo; a.seed_hi = s.seed_hi; a.off_lo = (u32)r.offset; a.off_hi = (u32)(r.offset >> 32);
+    a.sr_param = s.sr_param; a.sr_state = s.sr_state;
+    return a;
+}
+
+// adamw_dense_kernel's chain on the block's own tensor; e8 counts from the tensor's first block
+template <int T_ID>
+__global__ __launch_bounds__(AW_BLOCK) void adamw_dense_multi_kernel(const AwTable<AwDenseRec> t) {
+    const int i = aw_find(t, blockIdx.x);
+    const AwDenseRec& r = t.rec[i];
+    const AdamWScalars a = aw_scalars_of(t.s, r);
+    void* const param = r.param; const void* const grad = r.grad; void* const exp_avg = r.exp_avg; void* const exp_avg_sq = r.exp_avg_sq;
+    const int64_t numel = r.numel;
+    const int64_t e8 = (int64_t)(blockIdx.x - t.first[i]) * AW_BLOCK + threadIdx.x;
+    const int64_t left = numel - e8 * AW_EPL;
+    const int nv = left >= AW_EPL ? AW_EPL : (left > 0 ? (int)left : 0);
+    const int nl = nv ? nv : (numel >= AW_EPL ? AW_EPL : (int)numel);
+    const int64_t idx = nv ? e8 * AW_EPL : 0;
+    float p[8], g[8], m[8], v[8];
+    aw_load8<T_ID>(param, idx, nl, p);
+    aw_load8<T_ID>(grad, idx, nl, g);
+    aw_load8<T_ID>(exp_avg, idx, nl, m);
+    aw_load8<T_ID>(exp_avg_sq, idx, nl, v);
+    const bool has_gs = a.grad_scale != nullptr;
+    const float gs = has_gs ? *a.grad_scale : 1.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) aw_update<T_ID>(p[e], g[e], m[e], v[e], a, gs, has_gs);
+    if constexpr (T_ID != SDNQ_F32) {
+        if (a.sr_param) aw_sr8<T_ID>(p, a, e8, 0u);
+        if (a.sr_state) {
+            aw_sr8<T_ID>(m, a, e8, 1u);
+            aw_sr8<T_ID>(v, a, e8, 2u);
+        }
+    }
+    if (nv == 0) return;
+    aw_store8<T_ID>(param, idx, nv, p);
+    aw_store8<T_ID>(exp_avg, idx, nv, m);
+    aw_store8<T_ID>(exp_avg_sq, idx, nv, v);
+}
+
+// adamw_q8_kernel's chain on the block's own tensor: numel % 32 == 0 per tensor and a block never spans two, so a group of four lanes
+// is whole here as well
+template <int T_ID>
+__global__ __launch_bounds__(AW_BLOCK) void adamw_q8_multi_kernel(const AwTable<AwQ8Rec> t) {
+    const int i = aw_find(t, blockIdx.x);
+    const AwQ8Rec& r = t.rec[i];
+    const AdamWScalars a = aw_scalars_of(t.s, r);
+    void* const param = r.param; const void* const grad = r.grad;
+    uint8_t* const m_q = r.m_q; float* const m_scale = r.m_scale; float* const m_zp = r.m_zp;
+    uint8_t* const v_q = r.v_q; float* const v_scale = r.v_scale; float* const v_zp = r.v_zp;
+    const int64_t e8 = (int64_t)(blockIdx.x - t.first[i]) * AW_BLOCK + threadIdx.x;
+    const bool ok = e8 * AW_EPL < r.numel;
+    const int64_t idx = ok ? e8 * AW_EPL : 0;
+    const int64_t grp = idx >> 5;
+    float p[8], g[8], m[8], v[8];
+    aw_load8<T_ID>(param, idx, AW_EPL, p);
+    aw_load8<T_ID>(grad, idx, AW_EPL, g);
+    const uint2 mc = *(const uint2*)(m_q + idx), vc = *(const uint2*)(v_q + idx);
+    aw_dequant8(mc, m_scale[grp], m_zp[grp], m);
+    aw_dequant8(vc, v_scale[grp], v_zp[grp], v);
+    const bool has_gs = a.grad_scale != nullptr;
+    const float gs = has_gs ? *a.grad_scale : 1.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) aw_update<T_ID>(p[e], g[e], m[e], v[e], a, gs, has_gs);
+    if constexpr (T_ID != SDNQ_F32) {
+        if (a.sr_param) aw_sr8<T_ID>(p, a, e8, 0u);
+    }
+    float ms, mz, vs, vz;
+    const uint2 mn = aw_quant8(m, a.sr_state != 0, a, e8, 1u, 3u, ms, mz);
+    const uint2 vn = aw_quant8(v, a.sr_state != 0, a, e8, 2u, 4u, vs, vz);
+    if (!ok) return;
+    aw_store8<T_ID>(param, idx, AW_EPL, p);
+    *(uint2*)(m_q + idx) = mn;
+    *(uint2*)(v_q + idx) = vn;
+    if ((threadIdx.x & 3) == 0) {
+        m_scale[grp] = ms; m_zp[grp] = mz;
+        v_scale[grp] = vs; v_zp[grp] = vz;
+    }
+}
+
 int aw_scalars(AdamWScalars& a, float lr, float w1, float w2, float bc1, float bc2, float clip, float decay, const float* grad_scale,
                int sr_param, int sr_state, uint64_t seed, uint64_t offset) {
     // finite scalars only: a NaN here would reach every element
@@ -351,4 +493,133 @@ extern "C" int sdnq_hip_adamw_step_q8(void* param, const void* grad, int dtype, 
 #undef AW_Q8_LAUNCH
     SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
+}
+
+// ---- many tensors in one launch: entry points ----------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t AW_PER_BLOCK = AW_BLOCK * AW_EPL;
+constexpr int64_t AW_GRID_MAX = 0x7fffffff;
+
+int aw_shared(AwShared& s, float lr, float w1, float w2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
+              uint64_t seed) {
+    AdamWScalars a;
+    const int st = aw_scalars(a, lr, w1, w2, 1.0f, 1.0f, clip, decay, grad_scale, sr_param, sr_state, seed, 0);
+    if (st != SDNQ_OK) return st;
+    s.neg_lr = a.neg_lr; s.w1 = a.w1; s.w2 = a.w2; s.clip = a.clip; s.decay = a.decay; s.count = 0;
+    s.grad_scale = grad_scale; s.seed_lo = a.seed_lo; s.seed_hi = a.seed_hi; s.sr_param = a.sr_param; s.sr_state = a.sr_state;
+    return SDNQ_OK;
+}
+bool aw_finite(float x) { return x == x && x != __builtin_inff() && x != -__builtin_inff(); }
+
+// the checks that do not depend on the state's form, for all `count` tensors, and the grid of every launch of `cap` tensors
+int aw_multi_check(int64_t count, int cap, const void* const* const* arrays, int n_arrays, const int64_t* numels, const float* bc1,
+                   const float* bc2, const uint64_t* offsets, int dtype, const float* grad_scale, bool q8) {
+    if (count < 0) return SDNQ_ERR_SHAPE;
+    if (count == 0) return SDNQ_OK;
+    for (int k = 0; k < n_arrays; ++k) {
+        if (!arrays[k]) return SDNQ_ERR_NULL;
+    }
+    if (!numels || !bc1 || !bc2 || !offsets) return SDNQ_ERR_NULL;
+    if (dtype < 0 || dtype > 2) return SDNQ_ERR_DTYPE;
+    if (grad_scale && ((uintptr_t)grad_scale % 4)) return SDNQ_ERR_ALIGN;
+    int64_t blocks = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        uintptr_t wide = 0, narrow = 0;  // addresses that need 16 bytes / 4 bytes
+        for (int k = 0; k < n_arrays; ++k) {
+            const void* ptr = arrays[k][i];
+            if (!ptr) return SDNQ_ERR_NULL;
+            // uint8 state: param, grad and the two code arrays (0, 1, 2, 5) are read as vectors, scale and zero point as floats
+            ((q8 && k != 0 && k != 1 && k != 2 && k != 5) ? narrow : wide) |= (uintptr_t)ptr;
+        }
+        const int64_t n = numels[i];
+        if (n <= 0 || (q8 && (n % 32) != 0)) return SDNQ_ERR_SHAPE;
+        if ((q8 || n >= AW_EPL) && (wide % 16)) return SDNQ_ERR_ALIGN;
+        if (narrow % 4) return SDNQ_ERR_ALIGN;
+        if (!aw_finite(bc1[i]) || !aw_finite(bc2[i])) return SDNQ_ERR_UNSUPPORTED;
+        if (i % cap == 0) blocks = 0;
+        blocks += (n - 1) / AW_PER_BLOCK + 1;
+        if (blocks > AW_GRID_MAX) return SDNQ_ERR_SHAPE;
+    }
+    return SDNQ_OK;
+}
+
+template <class Rec, class Fill, class Launch>
+int aw_multi_launch(int64_t count, const int64_t* numels, const float* bc1, const float* bc2, const uint64_t* offsets, AwTable<Rec>& t,
+                    Fill fill, Launch launch) {
+    constexpr int cap = AwTable<Rec>::CAP;
+    for (int64_t base = 0; base < count; base += cap) {
+        const int n = (int)(count - base < cap ? count - base : cap);
+        u32 blocks = 0;
+        for (int j = 0; j < n; ++j) {
+            const int64_t i = base + j;
+            fill(t.rec[j], i);
+            t.rec[j].numel = numels[i]; t.rec[j].offset = offsets[i]; t.rec[j].bc1 = bc1[i]; t.rec[j].bc2 = bc2[i];
+            t.first[j] = blocks;
+            blocks += (u32)((numels[i] - 1) / AW_PER_BLOCK + 1);
+        }
+        t.s.count = n;
+        launch(dim3(blocks), t);
+        SDNQ_CHECK_LAUNCH();
+    }
+    return SDNQ_OK;
+}
+
+}  // namespace
+
+extern "C" int sdnq_hip_adamw_multi_capacity(int quantized) { return quantized ? AwTable<AwQ8Rec>::CAP : AwTable<AwDenseRec>::CAP; }
+
+extern "C" int sdnq_hip_adamw_step_multi(int64_t count, void* const* params, const void* const* grads, void* const* exp_avgs,
+                                         void* const* exp_avg_sqs, const int64_t* numels, const float* bc1, const float* bc2,
+                                         const uint64_t* offsets, int dtype, float lr, float w1, float w2, float clip, float decay,
+                                         const float* grad_scale, int sr_param, int sr_state, uint64_t seed, sdnq_stream_t stream) {
+    using Table = AwTable<AwDenseRec>;
+    const void* const* const arrays[4] = {(const void* const*)params, grads, (const void* const*)exp_avgs, (const void* const*)exp_avg_sqs};
+    int st = aw_multi_check(count, Table::CAP, arrays, 4, numels, bc1, bc2, offsets, dtype, grad_scale, false);
+    if (st != SDNQ_OK || count == 0) return st;
+    Table t{};
+    st = aw_shared(t.s, lr, w1, w2, clip, decay, grad_scale, sr_param, sr_state, seed);
+    if (st != SDNQ_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    return aw_multi_launch(count, numels, bc1, bc2, offsets, t,
+        [&](AwDenseRec& r, int64_t i) { r.param = params[i]; r.grad = grads[i]; r.exp_avg = exp_avgs[i]; r.exp_avg_sq = exp_avg_sqs[i]; },
+        [&](dim3 grid, const Table& tab) {
+            switch (dtype) {
+                case SDNQ_F32: hipLaunchKernelGGL((adamw_dense_multi_kernel<SDNQ_F32>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+                case SDNQ_BF16: hipLaunchKernelGGL((adamw_dense_multi_kernel<SDNQ_BF16>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+                default: hipLaunchKernelGGL((adamw_dense_multi_kernel<SDNQ_F16>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+            }
+        });
+}
+
+extern "C" int sdnq_hip_adamw_step_multi_q8(int64_t count, void* const* params, const void* const* grads, void* const* exp_avg_qs,
+                                            void* const* exp_avg_scales, void* const* exp_avg_zps, void* const* exp_avg_sq_qs,
+                                            void* const* exp_avg_sq_scales, void* const* exp_avg_sq_zps, const int64_t* numels,
+                                            const float* bc1, const float* bc2, const uint64_t* offsets, int dtype, float lr, float w1,
+                                            float w2, float clip, float decay, const float* grad_scale, int sr_param, int sr_state,
+                                            uint64_t seed, sdnq_stream_t stream) {
+    using Table = AwTable<AwQ8Rec>;
+    const void* const* const arrays[8] = {(const void* const*)params, grads, (const void* const*)exp_avg_qs,
+                                          (const void* const*)exp_avg_scales, (const void* const*)exp_avg_zps,
+                                          (const void* const*)exp_avg_sq_qs, (const void* const*)exp_avg_sq_scales,
+                                          (const void* const*)exp_avg_sq_zps};
+    int st = aw_multi_check(count, Table::CAP, arrays, 8, numels, bc1, bc2, offsets, dtype, grad_scale, true);
+    if (st != SDNQ_OK || count == 0) return st;
+    Table t{};
+    st = aw_shared(t.s, lr, w1, w2, clip, decay, grad_scale, sr_param, sr_state, seed);
+    if (st != SDNQ_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    return aw_multi_launch(count, numels, bc1, bc2, offsets, t,
+        [&](AwQ8Rec& r, int64_t i) {
+            r.param = params[i]; r.grad = grads[i];
+            r.m_q = (uint8_t*)exp_avg_qs[i]; r.m_scale = (float*)exp_avg_scales[i]; r.m_zp = (float*)exp_avg_zps[i];
+            r.v_q = (uint8_t*)exp_avg_sq_qs[i]; r.v_scale = (float*)exp_avg_sq_scales[i]; r.v_zp = (float*)exp_avg_sq_zps[i];
+        },
+        [&](dim3 grid, const Table& tab) {
+            switch (dtype) {
+                case SDNQ_F32: hipLaunchKernelGGL((adamw_q8_multi_kernel<SDNQ_F32>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+                case SDNQ_BF16: hipLaunchKernelGGL((adamw_q8_multi_kernel<SDNQ_BF16>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+                default: hipLaunchKernelGGL((adamw_q8_multi_kernel<SDNQ_F16>), grid, dim3(AW_BLOCK), 0, s, tab); break;
+            }
+        });
 }

@@ -1266,16 +1266,34 @@ def _adamw_check(p: torch.Tensor, g: torch.Tensor, grad_scale) -> None:
         raise _lib.SdnqHipError("adamw_step: grad_scale must be one float32 element on the device")
 
 
+def _adamw_dense_state(p: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor) -> list:
+    """The addresses of dense state, checked against its parameter."""
+    for t in (exp_avg, exp_avg_sq):
+        _require_cuda(t)
+        if t.dtype != p.dtype or t.numel() != p.numel() or not t.is_contiguous():
+            raise _lib.SdnqHipError("adamw_step: dense state must be contiguous, of the parameter's dtype and size")
+    return [exp_avg.data_ptr(), exp_avg_sq.data_ptr()]
+
+
+def _adamw_q8_state(p: torch.Tensor, exp_avg, exp_avg_sq) -> list:
+    """The six addresses of uint8 state (codes, scale, zero point of either moment), checked against its parameter."""
+    ptrs = []
+    for q, s, z in (exp_avg, exp_avg_sq):
+        _require_cuda(q, s, z)
+        if (q.dtype != torch.uint8 or q.numel() != p.numel() or s.dtype != torch.float32 or z.dtype != torch.float32
+                or s.numel() * 32 != p.numel() or z.numel() != s.numel() or not (q.is_contiguous() and s.is_contiguous() and z.is_contiguous())):
+            raise _lib.SdnqHipError("adamw_step_q8: state must be contiguous uint8 codes [numel] with float32 scale and zero point [numel / 32]")
+        ptrs += [q.data_ptr(), s.data_ptr(), z.data_ptr()]
+    return ptrs
+
+
 def adamw_step(p: torch.Tensor, g: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, *, step: int, lr: float,
                betas=(0.9, 0.999), weight_decay: float = 0.01, clip: float = 1.0, grad_scale: torch.Tensor | None = None,
                sr_param: bool = False, sr_state: bool = False, seed: int = 0, offset: int = 0) -> None:
     """sdnq_hip_adamw_step: one fused AdamW update of `p` in place, with dense state in p's dtype.  `step` counts from 1."""
     _adamw_check(p, g, grad_scale)
-    for t in (exp_avg, exp_avg_sq):
-        _require_cuda(t)
-        if t.dtype != p.dtype or t.numel() != p.numel() or not t.is_contiguous():
-            raise _lib.SdnqHipError("adamw_step: dense state must be contiguous, of the parameter's dtype and size")
-    check(_lib.load().sdnq_hip_adamw_step(p.data_ptr(), g.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), float_code(p.dtype),
+    state = _adamw_dense_state(p, exp_avg, exp_avg_sq)
+    check(_lib.load().sdnq_hip_adamw_step(p.data_ptr(), g.data_ptr(), *state, float_code(p.dtype),
                                           p.numel(), *_adamw_tail(p, lr, betas, step, weight_decay, clip, grad_scale, sr_param,
                                                                   sr_state, seed, offset)), "adamw_step")
 
@@ -1286,13 +1304,49 @@ def adamw_step_q8(p: torch.Tensor, g: torch.Tensor, exp_avg, exp_avg_sq, *, step
     """sdnq_hip_adamw_step_q8: the same with uint8 state; exp_avg / exp_avg_sq are (codes uint8 [numel], scale f32 [numel / 32],
     zero_point f32 [numel / 32]) triples, updated in place."""
     _adamw_check(p, g, grad_scale)
-    ptrs = []
-    for q, s, z in (exp_avg, exp_avg_sq):
-        _require_cuda(q, s, z)
-        if (q.dtype != torch.uint8 or q.numel() != p.numel() or s.dtype != torch.float32 or z.dtype != torch.float32
-                or s.numel() * 32 != p.numel() or z.numel() != s.numel() or not (q.is_contiguous() and s.is_contiguous() and z.is_contiguous())):
-            raise _lib.SdnqHipError("adamw_step_q8: state must be contiguous uint8 codes [numel] with float32 scale and zero point [numel / 32]")
-        ptrs += [q.data_ptr(), s.data_ptr(), z.data_ptr()]
+    ptrs = _adamw_q8_state(p, exp_avg, exp_avg_sq)
     check(_lib.load().sdnq_hip_adamw_step_q8(p.data_ptr(), g.data_ptr(), float_code(p.dtype), p.numel(), *ptrs,
                                              *_adamw_tail(p, lr, betas, step, weight_decay, clip, grad_scale, sr_param, sr_state,
                                                           seed, offset)), "adamw_step_q8")
+
+
+def _adamw_multi(entry: str, state_of, params, grads, exp_avgs, exp_avg_sqs, steps, offsets, lr, betas, weight_decay, clip, grad_scale,
+                 sr_param, sr_state, seed) -> None:
+    """One call of a multi-tensor entry point: the single-tensor checks per tensor, the addresses column by column as host arrays, and
+    _adamw_tail's scalars -- bc1 and bc2 once per distinct step, everything else shared."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == len(offsets) == n):
+        raise _lib.SdnqHipError(f"{entry}: params, grads, exp_avgs, exp_avg_sqs, steps and offsets must have one entry per tensor")
+    if n == 0:
+        return
+    rows = []
+    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+        if p.dtype != params[0].dtype or p.device != params[0].device:
+            raise _lib.SdnqHipError(f"{entry}: the tensors of one call must share a dtype and a device (got {p.dtype} on {p.device} "
+                                    f"beside {params[0].dtype} on {params[0].device})")
+        _adamw_check(p, g, grad_scale)
+        rows.append([p.data_ptr(), g.data_ptr(), *state_of(p, m, v)])
+    tails = {s: _adamw_tail(params[0], lr, betas, s, weight_decay, clip, grad_scale, sr_param, sr_state, seed, 0) for s in set(steps)}
+    lr_, w1, w2, _bc1, _bc2, clip_, decay, gs, srp, srs, seed_, _offset, stream = tails[steps[0]]
+    columns = [(ctypes.c_void_p * n)(*column) for column in zip(*rows)]
+    check(getattr(_lib.load(), entry)(
+        n, *columns, (ctypes.c_int64 * n)(*(p.numel() for p in params)), (ctypes.c_float * n)(*(tails[s][3] for s in steps)),
+        (ctypes.c_float * n)(*(tails[s][4] for s in steps)), (ctypes.c_uint64 * n)(*(int(o) & 0xFFFFFFFFFFFFFFFF for o in offsets)),
+        float_code(params[0].dtype), lr_, w1, w2, clip_, decay, gs, srp, srs, seed_, stream), entry[len("sdnq_hip_"):])
+
+
+def adamw_step_multi(params, grads, exp_avgs, exp_avg_sqs, *, steps, offsets, lr: float, betas=(0.9, 0.999), weight_decay: float = 0.01,
+                     clip: float = 1.0, grad_scale: torch.Tensor | None = None, sr_param: bool = False, sr_state: bool = False,
+                     seed: int = 0) -> None:
+    """sdnq_hip_adamw_step_multi: adamw_step on every (params[i], grads[i], exp_avgs[i], exp_avg_sqs[i]) with step steps[i] and random
+    offset offsets[i], bit for bit, in one launch per sdnq_hip_adamw_multi_capacity(0) tensors.  One dtype and one device per call."""
+    _adamw_multi("sdnq_hip_adamw_step_multi", _adamw_dense_state, params, grads, exp_avgs, exp_avg_sqs, steps, offsets, lr, betas,
+                 weight_decay, clip, grad_scale, sr_param, sr_state, seed)
+
+
+def adamw_step_multi_q8(params, grads, exp_avgs, exp_avg_sqs, *, steps, offsets, lr: float, betas=(0.9, 0.999),
+                        weight_decay: float = 0.01, clip: float = 1.0, grad_scale: torch.Tensor | None = None, sr_param: bool = False,
+                        sr_state: bool = False, seed: int = 0) -> None:
+    """sdnq_hip_adamw_step_multi_q8: the same on adamw_step_q8; exp_avgs[i] / exp_avg_sqs[i] are its (codes, scale, zero_point) triples."""
+    _adamw_multi("sdnq_hip_adamw_step_multi_q8", _adamw_q8_state, params, grads, exp_avgs, exp_avg_sqs, steps, offsets, lr, betas,
+                 weight_decay, clip, grad_scale, sr_param, sr_state, seed)

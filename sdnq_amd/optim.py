@@ -1,6 +1,6 @@
-"""The reference's optimizer package (optim/optimizer.py, optim/adamw.py, optim/utils.py) on one HIP launch per parameter tensor:
+"""The reference's optimizer package (optim/optimizer.py, optim/adamw.py, optim/utils.py) on fused HIP launches (csrc/optim.hip):
 ``SDNQOptimizer`` with the reference's group keys, defaults and ``step(closure)`` contract, and ``AdamW`` on ``ops.adamw_step`` /
-``ops.adamw_step_q8`` (csrc/optim.hip).
+``ops.adamw_step_q8`` (one tensor per launch) and ``ops.adamw_step_multi`` / ``ops.adamw_step_multi_q8`` (a table of tensors per launch).
 
 Built: parameters and gradients of float32 / bfloat16 / float16 on the device, any shape; ``lr``, ``betas``, ``weight_decay``,
 ``clip_threshold``, ``grad_scale``, ``final_norm_mode`` "clip" and "none"; dense state in the parameter's dtype, or -- with
@@ -15,15 +15,25 @@ once, advancing the generator's offset; parameter i of the step uses offset + i,
 ``torch.cuda.manual_seed`` therefore reproduces a run.  Nothing here synchronises with the host.  ``state["step"]`` is a Python int,
 as in the reference: a ``step()`` captured in a graph replays with the bias correction (and the random offset) of the step that was
 captured, so only the deterministic configuration is captured -- a stochastic one raises while the stream is capturing.
+
+Launches: ``step()`` collects the parameters that have a gradient into buckets keyed by (group, device, dtype, dense | quantized state)
+and hands each bucket of more than one tensor to ``update_params_``, which ``AdamW`` serves with one multi-tensor call (the library
+cuts it into launches of ``sdnq_hip_adamw_multi_capacity`` tensors); a bucket of one goes through ``update_param_`` and the
+single-tensor entry point.  The bits of every tensor are those of its single-tensor launch either way.  Large tensors go through the
+table like small ones: a set of 1482 adapter tensors and four tensors of up to 16384 x 5120 together takes the time of the two sets
+apart (profiles/optim_multi_bench.jsonl, set "mixed"), and the four alone what four single-tensor launches take.  ``MULTI`` (environment
+``SDNQ_HIP_OPTIM_MULTI``, default on; read at every ``step()``) set false sends every parameter through ``update_param_``: an A/B aid.
 """
 from __future__ import annotations
 
+import os
 from collections.abc import Iterator
 
 import torch
 
 from . import _lib, ops
 
+MULTI = os.environ.get("SDNQ_HIP_OPTIM_MULTI", "1").lower() not in {"0", "false", "no"}
 _FLOATS = (torch.float32, torch.bfloat16, torch.float16)
 GROUP = 32  # elements per scale / zero point of quantized state: the reference's default quantized_buffers_group_size, the only one built
 _WHOLE_TENSOR_NORMS = ("rms", "rms_clip", "relative", "rms_scaled", "rms_clip_scaled", "muon")
@@ -86,7 +96,8 @@ torch.serialization.add_safe_globals([QuantizedBuffer])
 
 class SDNQOptimizer(torch.optim.Optimizer):
     """SDNQOptimizer (optim/optimizer.py:13-144): group keys and defaults, ``step(closure)`` with ``state["step"]``, lazy
-    ``init_state`` and ``self.grad_scale``.  A subclass gives ``init_state`` and ``update_param_``, the one fused launch."""
+    ``init_state`` and ``self.grad_scale``.  A subclass gives ``init_state`` and ``update_param_``, the one fused launch of one tensor,
+    and may give ``update_params_``, the launch of a whole bucket."""
 
     _base_group_keys = frozenset({
         "params", "lr", "betas", "weight_decay", "clip_threshold", "final_norm_mode", "use_kahan", "use_cautious", "use_torch_compile",
@@ -183,6 +194,11 @@ class SDNQOptimizer(torch.optim.Optimizer):
     def update_param_(self, param: torch.Tensor, grad: torch.Tensor, group: dict, state: dict, grad_scale, seed: int, offset: int) -> None:
         raise NotImplementedError
 
+    def update_params_(self, group: dict, batch: list, grad_scale, seed: int) -> None:
+        """Update every (param, grad, state, offset) of `batch`: tensors of one group, device, dtype and state form.  Here: one by one."""
+        for param, grad, state, offset in batch:
+            self.update_param_(param, grad, group, state, grad_scale, seed, offset)
+
     @staticmethod
     def needs_random(param: torch.Tensor, group: dict) -> bool:
         if param.dtype != torch.float32 and (group["use_stochastic_rounding"] or group["use_stochastic_buffers"]):
@@ -199,7 +215,8 @@ class SDNQOptimizer(torch.optim.Optimizer):
                 loss = closure()
         scales = {}   # device -> grad_scale as one float32 there
         drawn = {}    # device -> [generator, seed, first offset, tensors served]
-        for group in self.param_groups:
+        buckets = {}  # (group index, device, dtype, quantized state, seed) -> (group, [(param, grad, state, offset)], grad_scale, seed)
+        for index, group in enumerate(self.param_groups):
             self.check_group(group)
             for param in group["params"]:
                 if param.grad is None:
@@ -240,7 +257,16 @@ class SDNQOptimizer(torch.optim.Optimizer):
                     d = drawn[dev]
                     seed, offset = d[1], d[2] + d[3]
                     d[3] += 1
-                self.update_param_(param, grad, group, state, gs, seed, offset)
+                quantized = any(isinstance(value, QuantizedBuffer) for value in state.values())
+                bucket = buckets.setdefault((index, dev, param.dtype, quantized, seed), (group, [], gs, seed))
+                bucket[1].append((param, grad, state, offset))
+        multi = MULTI
+        for group, batch, gs, seed in buckets.values():
+            if multi and len(batch) > 1:
+                self.update_params_(group, batch, gs, seed)
+            else:
+                for param, grad, state, offset in batch:
+                    self.update_param_(param, grad, group, state, gs, seed, offset)
         for gen, _seed, first, used in drawn.values():
             gen.set_offset(first + (used + 3) // 4 * 4)  # torch keeps the offset a multiple of 4
         return loss
@@ -259,7 +285,8 @@ class SDNQOptimizer(torch.optim.Optimizer):
 
 
 class AdamW(SDNQOptimizer):
-    """AdamW (optim/adamw.py:12-50): state keys ``step``, ``exp_avg``, ``exp_avg_sq``; the whole update of a parameter is one launch."""
+    """AdamW (optim/adamw.py:12-50): state keys ``step``, ``exp_avg``, ``exp_avg_sq``; the whole update of a parameter, or of a bucket
+    of them, is one launch."""
 
     def init_state(self, param: torch.Tensor, group: dict, state: dict) -> dict:
         if self.quantizes(param, group):
@@ -270,18 +297,35 @@ class AdamW(SDNQOptimizer):
             state["exp_avg_sq"] = torch.zeros_like(param, memory_format=torch.contiguous_format)
         return state
 
-    def update_param_(self, param, grad, group, state, grad_scale, seed, offset) -> None:
+    @staticmethod
+    def _options(group: dict, grad_scale, seed: int) -> dict:
         clips = group["clip_threshold"]
-        kw = dict(step=state["step"], lr=group["lr"], betas=group["betas"], weight_decay=group["weight_decay"],
-                  clip=clips if isinstance(clips, (int, float)) else clips[0], grad_scale=grad_scale,
-                  sr_param=group["use_stochastic_rounding"], sr_state=group["use_stochastic_buffers"], seed=seed, offset=offset)
+        return dict(lr=group["lr"], betas=group["betas"], weight_decay=group["weight_decay"],
+                    clip=clips if isinstance(clips, (int, float)) else clips[0], grad_scale=grad_scale,
+                    sr_param=group["use_stochastic_rounding"], sr_state=group["use_stochastic_buffers"], seed=seed)
+
+    @staticmethod
+    def _moments(state: dict):
+        """(exp_avg, exp_avg_sq, quantized) with quantized state as its (codes, scale, zero point) triples."""
         m, v = state["exp_avg"], state["exp_avg_sq"]
         if isinstance(m, QuantizedBuffer) != isinstance(v, QuantizedBuffer):
             raise ValueError("AdamW: exp_avg and exp_avg_sq must both be dense or both be quantized")
-        if isinstance(m, QuantizedBuffer):
-            ops.adamw_step_q8(param, grad, m.parts(), v.parts(), **kw)
-        else:
-            ops.adamw_step(param, grad, m, v, **kw)
+        return (m.parts(), v.parts(), True) if isinstance(m, QuantizedBuffer) else (m, v, False)
+
+    def update_param_(self, param, grad, group, state, grad_scale, seed, offset) -> None:
+        m, v, quantized = self._moments(state)
+        (ops.adamw_step_q8 if quantized else ops.adamw_step)(param, grad, m, v, step=state["step"], offset=offset,
+                                                             **self._options(group, grad_scale, seed))
+
+    def update_params_(self, group, batch, grad_scale, seed) -> None:
+        if type(self).update_param_ is not AdamW.update_param_:  # a subclass that changed the single-tensor hook keeps it
+            return super().update_params_(group, batch, grad_scale, seed)
+        moments = [self._moments(state) for _, _, state, _ in batch]
+        if any(m[2] != moments[0][2] for m in moments):
+            raise ValueError("AdamW: the tensors of one bucket must all have dense or all have quantized state")
+        (ops.adamw_step_multi_q8 if moments[0][2] else ops.adamw_step_multi)(
+            [b[0] for b in batch], [b[1] for b in batch], [m[0] for m in moments], [m[1] for m in moments],
+            steps=[b[2]["step"] for b in batch], offsets=[b[3] for b in batch], **self._options(group, grad_scale, seed))
 
 
 def _not_built(name: str, what: str):
