@@ -844,6 +844,30 @@ int sdnq_hip_col2im(const float* cols, int64_t ldcols, const void* bias, int dty
 int sdnq_hip_dequant_t(const SdnqWeight* w, void* out, int out_dtype, sdnq_stream_t stream);
 int sdnq_hip_transpose2d(const void* x, int dtype, int64_t r, int64_t c, int64_t ldx, void* out, sdnq_stream_t stream);
 
+/* ---- input gradients through frozen quantized Conv1d / Conv2d layers: the activation operand ---------------------------------------------
+ * replaces the activation side of F.grad.conv{1,2}d_input(input_size, weight.dequantize(), grad_output, stride, padding, dilation, groups)
+ * (what autograd runs behind the reference's quantized_conv_forward, layers/conv/forward.py:80-81): for a weight W[C_out][C_in / groups][kh][kw]
+ *   grad_x[b][ci][ih][iw] = sum over (co, i, j) of dY[b][co][oh][ow] * W[co][ci][i][j]   with ih + pad_h - i * dil_h = oh * stride_h,
+ *   0 <= oh < out_h (likewise w); a tap with no such (oh, ow) contributes 0.
+ * It runs as this gather followed by sdnq_hip_linear_float on the transposed weight operand of sdnq_hip_dequant_t / sdnq_hip_transpose2d.
+ *
+ * sdnq_hip_im2col_bwd: rows row0 .. row0 + rows of U [batch * in_h * in_w][kh * kw * channels] of `dtype`, written to out [rows][kh * kw *
+ *   channels] (16-byte aligned).  Row r = (b, ih, iw); column ((g * kh * kw) + i * kw + j) * (channels / groups) + co_local holds
+ *   dY[b][g * (channels / groups) + co_local][oh][ow], or 0 where the tap does not exist -- for groups == 1 that is column
+ *   (i * kw + j) * channels + co: (kernel position, channel), NOT the forward im2col's (channel, kernel position), so that the [K][N]
+ *   weight operand viewed as [C_in][kh * kw * C_out] is the GEMM's other side as it stands; for groups > 1 every conv group's columns are
+ *   one contiguous range.  dy: [batch][channels][out_h][out_w] contiguous (channels = C_out), float32 / bfloat16 / float16 (SdnqFloat).
+ *   Pure data movement, bit-exact; every element of the rows asked for, zeros included, is written exactly once and nothing is written
+ *   behind out.  One launch, no atomics, no workspace, capturable.  Conv1d passes out_h = in_h = kh = 1 (stride 1, padding 0, dilation 1).
+ *   The input extent is given, not derived (a strided conv does not determine it; trailing input rows / columns that no window reaches
+ *   get zeros), but out_h must equal (in_h + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1, likewise w (SDNQ_ERR_SHAPE).
+ *   SDNQ_ERR_SHAPE also: a non-positive extent, groups that do not divide channels, a row window outside [0, batch * in_h * in_w] or an
+ *   empty one, kh * kw * channels * sizeof(dtype) not a multiple of 16.  SDNQ_ERR_ALIGN: out not 16-byte aligned.  SDNQ_ERR_UNSUPPORTED:
+ *   kh * kw * channels > 64 * 65535 (the launch grid).  row0 / rows let the caller bound U: a slab of rows per launch and GEMM. */
+int sdnq_hip_im2col_bwd(const void* dy, int dtype, int batch, int channels, int out_h, int out_w, int in_h, int in_w, int kh, int kw,
+                        int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int groups, int64_t row0, int64_t rows,
+                        void* out, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

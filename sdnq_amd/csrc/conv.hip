@@ -7,6 +7,9 @@
 // One workgroup copies a 64 (m) x 64 (k) tile: global reads are coalesced along w_out (consecutive m of one (c, i, j)),
 // the tile is transposed through LDS and leaves as 16-byte row segments of the [M][K] matrix.  HBM-bound:
 // reads ~ input * (kernel positions hit in L2), writes M*K*e bytes.
+//
+// sdnq_hip_im2col_bwd: the same unfold turned round for the input gradient of a frozen quantized conv -- dY gathered per INPUT pixel into
+// the activation operand of grad_x = U . W^T (geometry, LDS image and bank arithmetic: at im2col_bwd_kernel below).
 #include <hip/hip_runtime.h>
 
 #include "../../include/sdnq_hip.h"
@@ -259,6 +262,99 @@ __global__ __launch_bounds__(256) void im2col_kernel(const Im2colParams p) {
     }
 }
 
+// ---- the activation side of the backward-data convolution (sdnq_hip_im2col_bwd) -----------------------------------------------------
+// U[r][col] = dY[b][co][oh][ow] or 0: rows r = (b, ih, iw) of the INPUT image, columns (g, kernel position, channel inside the group),
+// with ih + pad - i * dil = oh * stride (likewise w).  grad_x = U . W^T is then the float GEMM of the forward (sdnq_amd/training.py).
+//
+// Tile geometry: a workgroup of 256 threads moves 64 rows x 64 columns of U.  Lane = row, so a wave's global load of one column is a
+// run along ow (contiguous in NCHW for stride 1, every stride-th lane active otherwise); wave w owns columns 16 w .. 16 w + 15 of the
+// tile and walks them in SEGMENTS that stay inside one (group, kernel position): the tap geometry -- two integer divisions by the
+// strides per lane -- is worked out once per segment, the loads inside a segment differ by the channel stride only and are
+// unconditional (clamped address, value zeroed afterwards), and (g, i, j, channel) advance by scalar increments, no division per column.
+// The tile crosses LDS as one 32-bit cell per element (16-bit elements are widened; 16 KB per workgroup) and leaves as 16-byte runs
+// along the columns: 8 (16-bit) or 4 (float32) cells gathered into one global store per lane, 8 / 16 lanes covering a tile row.
+// LDS image: u32 tile[64 columns][64 rows], the row index XOR-ed with swz(column) = (column / EPC) * (32 / CPR), EPC = elements per
+// 16 bytes, CPR = 64 / EPC (16-bit: 4 * (column / 8); float32: 2 * (column / 4)).
+//   stores (ds_write_b32, bank = dword % 32, conflicts inside a 32-lane half): the column is wave-uniform, the lanes of a half are 32
+//     consecutive rows XOR-ed with one constant -- 32 distinct banks: conflict-free.
+//   loads (ds_read_b32, bank = dword % 32, 32-lane halves): a half holds the CPR chunks of 32 / CPR consecutive rows (the first a multiple
+//     of 32 / CPR); in one load instruction the element inside the chunk is the same for every lane, so the bank is (row ^ swz) % 32 =
+//     ((row0 / (32 / CPR)) ^ chunk) % CPR * (32 / CPR) + (row - row0): 32 distinct banks: conflict-free.
+// Both claims are worked out by hand from the guide's bank tables; no counter run has confirmed them.  The element-wide LDS reads (eight
+// ds_read_b32 per 16-byte store for 16-bit data) are the price of a conflict-free image on both sides; the kernel is bound by the HBM write
+// of U (measured figures: profiles/conv_input_grad_bench.jsonl).
+struct Im2colBwdParams {
+    const void* dy;
+    void* out;
+    int B, C, HO, WO, H, W, KH, KW, SH, SW, PH, PW, DH, DW, G;
+    int64_t row0, rows, KC;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void im2col_bwd_kernel(const Im2colBwdParams p) {
+    SDNQ_KERNARGS_NOW("s"(p.dy), "s"(p.out), "s"(p.B), "s"(p.C), "s"(p.HO), "s"(p.WO), "s"(p.H), "s"(p.W), "s"(p.KH), "s"(p.KW), "s"(p.SH), "s"(p.SW), "s"(p.PH),
+                      "s"(p.PW), "s"(p.DH), "s"(p.DW), "s"(p.G), "s"(p.row0), "s"(p.rows), "s"(p.KC));
+    constexpr int EPC = 16 / (int)sizeof(T), CPR = 64 / EPC, SWZ = 32 / CPR;
+    __shared__ uint32_t tile[64][64];  // [column][row ^ swz(column)]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t rl0 = (int64_t)blockIdx.x * 64, col0 = (int64_t)blockIdx.y * 64;
+    const bool rok = rl0 + lane < p.rows;
+    int64_t t64, iw64, b64, ih64;
+    divmod(p.row0 + (rok ? rl0 + lane : 0), p.W, t64, iw64);  // (a lane behind the window works on the window's first row and stores zeros)
+    divmod(t64, p.H, b64, ih64);
+    const int iw = (int)iw64, ih = (int)ih64;
+    const int Cg = p.C / p.G, P = p.KH * p.KW;
+    const int64_t plane = (int64_t)p.HO * p.WO;
+    const T* dy = (const T*)p.dy;
+    int kk = w * 16;
+    const int end = (p.KC - col0 < kk + 16) ? (int)(p.KC - col0) : kk + 16;  // columns [kk, end) of the tile are this wave's
+    if (kk < end) {
+        // the first column, decomposed once; from there on (g, i, j, cl) advance by increments
+        const int64_t q = (col0 + kk) / Cg;
+        int cl = (int)(col0 + kk - q * Cg);
+        int g = (int)(q / P);
+        const int kpos = (int)(q - (int64_t)g * P);
+        int i = kpos / p.KW, j = kpos - i * p.KW;
+        while (kk < end) {
+            const int seg = (end - kk < Cg - cl) ? end - kk : Cg - cl;
+            const int th = ih + p.PH - i * p.DH, tw = iw + p.PW - j * p.DW;
+            const int oh = (th > 0 ? th : 0) / p.SH, ow = (tw > 0 ? tw : 0) / p.SW;
+            const bool ok = rok && th >= 0 && tw >= 0 && oh * p.SH == th && ow * p.SW == tw && oh < p.HO && ow < p.WO;
+            const T* src = ok ? dy + ((b64 * p.C + (int64_t)g * Cg + cl) * p.HO + oh) * p.WO + ow : dy;  // (dy[0] exists: a safe address)
+            const int64_t step = ok ? plane : 0;
+#pragma unroll 4
+            for (int u = 0; u < seg; ++u) {
+                const T v = src[u * step];
+                const int c = kk + u;
+                tile[c][lane ^ ((c / EPC) * SWZ)] = ok ? (uint32_t)v : 0u;
+            }
+            kk += seg;
+            cl += seg;
+            if (cl == Cg) {
+                cl = 0;
+                if (++j == p.KW) {
+                    j = 0;
+                    if (++i == p.KH) { i = 0; ++g; }
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ch = tid; ch < 64 * CPR; ch += 256) {
+        const int r = ch / CPR, c16 = ch % CPR;
+        const int64_t grow = rl0 + r, gcol = col0 + c16 * EPC;
+        if (grow >= p.rows || gcol >= p.KC) continue;  // KC % EPC == 0: a chunk never straddles the row end
+        uint32_t e[EPC];
+#pragma unroll
+        for (int x = 0; x < EPC; ++x) e[x] = tile[c16 * EPC + x][r ^ (c16 * SWZ)];
+        uint4 o;
+        if constexpr (EPC == 4) o = make_uint4(e[0], e[1], e[2], e[3]);
+        else o = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+        *(uint4*)((T*)p.out + grow * p.KC + gcol) = o;
+    }
+}
+
 int fill_geometry(Im2colParams& p, const void* x, void* out, int batch, int channels, int height, int width, int kh, int kw,
                   int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w) {
     if (!x || !out) return SDNQ_ERR_NULL;
@@ -365,6 +461,38 @@ extern "C" int sdnq_hip_im2col(const void* x, int dtype, int batch, int channels
     hipStream_t s = (hipStream_t)stream;
     if (eb == 4) hipLaunchKernelGGL((im2col_kernel<uint32_t>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((im2col_kernel<uint16_t>), grid, block, 0, s, p);
+    SDNQ_CHECK_LAUNCH();
+    return SDNQ_OK;
+}
+
+extern "C" int sdnq_hip_im2col_bwd(const void* dy, int dtype, int batch, int channels, int out_h, int out_w, int in_h, int in_w, int kh,
+                                   int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int groups,
+                                   int64_t row0, int64_t rows, void* out, sdnq_stream_t stream) {
+    if (!dy || !out) return SDNQ_ERR_NULL;
+    if (dtype < 0 || dtype > 2) return SDNQ_ERR_DTYPE;
+    if (batch <= 0 || channels <= 0 || out_h <= 0 || out_w <= 0 || in_h <= 0 || in_w <= 0 || kh <= 0 || kw <= 0 || stride_h <= 0 ||
+        stride_w <= 0 || pad_h < 0 || pad_w < 0 || dil_h <= 0 || dil_w <= 0 || groups <= 0 || (channels % groups) != 0)
+        return SDNQ_ERR_SHAPE;
+    // the input extent is given, not derived (a strided conv does not determine it), but it must be one that produces this output
+    const int64_t span_h = (int64_t)in_h + 2 * (int64_t)pad_h - (int64_t)dil_h * (kh - 1) - 1;
+    const int64_t span_w = (int64_t)in_w + 2 * (int64_t)pad_w - (int64_t)dil_w * (kw - 1) - 1;
+    if (span_h < 0 || span_w < 0 || span_h / stride_h + 1 != out_h || span_w / stride_w + 1 != out_w) return SDNQ_ERR_SHAPE;
+    const int64_t total = (int64_t)batch * in_h * in_w;
+    if (row0 < 0 || rows <= 0 || row0 > total - rows) return SDNQ_ERR_SHAPE;
+    const int eb = (dtype == SDNQ_F32) ? 4 : 2;
+    const int64_t kc = (int64_t)kh * kw * channels;
+    if ((kc * eb) % 16) return SDNQ_ERR_SHAPE;
+    if ((uintptr_t)out % 16 || (uintptr_t)dy % eb) return SDNQ_ERR_ALIGN;
+    const int64_t gx = (rows + 63) / 64, gy = (kc + 63) / 64;
+    if (gx > 0x7fffffff || gy > 65535) return SDNQ_ERR_UNSUPPORTED;  // the launch grid: kh * kw * channels <= 64 * 65535
+    Im2colBwdParams p{};
+    p.dy = dy; p.out = out; p.B = batch; p.C = channels; p.HO = out_h; p.WO = out_w; p.H = in_h; p.W = in_w; p.KH = kh; p.KW = kw;
+    p.SH = stride_h; p.SW = stride_w; p.PH = pad_h; p.PW = pad_w; p.DH = dil_h; p.DW = dil_w; p.G = groups;
+    p.row0 = row0; p.rows = rows; p.KC = kc;
+    dim3 grid((unsigned)gx, (unsigned)gy), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (eb == 4) hipLaunchKernelGGL((im2col_bwd_kernel<uint32_t>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((im2col_bwd_kernel<uint16_t>), grid, block, 0, s, p);
     SDNQ_CHECK_LAUNCH();
     return SDNQ_OK;
 }

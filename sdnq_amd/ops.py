@@ -1106,6 +1106,32 @@ def im2col(x: torch.Tensor, kernel, stride, padding, dilation) -> tuple[torch.Te
     return out, (b, ho, wo)
 
 
+def im2col_bwd(dy: torch.Tensor, in_hw, kernel, stride, padding, dilation, row0: int = 0, rows: int | None = None,
+               out: torch.Tensor | None = None, groups: int = 1) -> torch.Tensor:
+    """sdnq_hip_im2col_bwd: dy [B, C_out, H_out, W_out] gathered per INPUT pixel into rows row0 .. row0 + rows of
+    U [B * H * W, kh * kw * C_out] -- the activation operand of grad_x = U . W^T for a conv of this geometry on an input of in_hw = (H, W).
+    Columns are (kernel position, channel) -- (group, kernel position, channel inside the group) for groups > 1 -- and a tap that no output
+    position matches is 0.  rows=None: everything from row0 on.  out: a 1-D or 2-D tensor of dy's dtype with at least rows * kh * kw * C_out
+    elements (its first rows * kh * kw * C_out are written); returned as the [rows, kh * kw * C_out] view."""
+    _require_cuda(dy, out)
+    if dy.ndim != 4:
+        raise _lib.SdnqHipError("im2col_bwd expects grad_output as [B, C_out, H_out, W_out]")
+    dy = dy if dy.is_contiguous() else dy.contiguous()
+    b, c, ho, wo = dy.shape
+    (h, w), (kh, kw), (sh, sw), (ph, pw), (dh, dw) = in_hw, kernel, stride, padding, dilation
+    total = b * int(h) * int(w)
+    if rows is None:
+        rows = total - row0
+    kc = kh * kw * c
+    if out is None:
+        out = torch.empty((rows, kc), device=dy.device, dtype=dy.dtype)
+    elif out.dtype != dy.dtype or out.numel() < rows * kc or not out.is_contiguous():
+        raise _lib.SdnqHipError(f"im2col_bwd: out must hold {rows * kc} contiguous elements of {dy.dtype}")
+    check(_lib.load().sdnq_hip_im2col_bwd(dy.data_ptr(), float_code(dy.dtype), b, c, ho, wo, int(h), int(w), kh, kw, sh, sw, ph, pw, dh, dw,
+                                          int(groups), int(row0), int(rows), out.data_ptr(), _stream(dy)), "im2col_bwd")
+    return out.view(-1)[:rows * kc].view(rows, kc)
+
+
 # per (device, stream): [zeroed int32 buffer (ticket + amax map) of sdnq_hip_im2col_rowquant_z, call-in-flight flag]
 _amax_maps: dict = {}
 _capture_amax_maps: dict = {}  # per (device, stream): (capture id, the map the convs of that capture address)
