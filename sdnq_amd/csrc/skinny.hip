@@ -504,7 +504,15 @@ __global__ __launch_bounds__(256) void skinny_svd32_kernel(const DeqParams p, co
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float q0 = (float)((cw >> (16 * h)) & 0xffu) - qsub, q1 = (float)((cw >> (16 * h + 8)) & 0xffu) - qsub;
-                const u32 pw = pack2<T_ID>(fmaf(q0, sc, zc), fmaf(q1, sc, zc));  // dequantize -> .to(svd dtype)
+                float b0 = fmaf(q0, sc, zc), b1 = fmaf(q1, sc, zc);
+                if constexpr (!IS_BF16) {
+                    // float16: the reference rounds the fma to float32 and THAT to float16 (addcmul in float32, then .to(), dequantizer.py:27).
+                    // Left visible to the compiler, fma + conversion fold into one v_fma_mixlo_f16, which rounds the exact q s + z ONCE:
+                    // another float16 whenever the float32 rounding lands on a float16 tie (profiles/skinny_census.md)
+                    asm("" : "+v"(b0));
+                    asm("" : "+v"(b1));
+                }
+                const u32 pw = pack2<T_ID>(b0, b1);  // dequantize -> .to(svd dtype)
                 float r0, r1;
                 if constexpr (IS_BF16) { r0 = __uint_as_float(pw << 16); r1 = __uint_as_float(pw & 0xffff0000u); }
                 else { r0 = f16_bits_to_f32((uint16_t)pw); r1 = f16_bits_to_f32((uint16_t)(pw >> 16)); }
