@@ -376,7 +376,9 @@ int sdnq_hip_lowrank_down(const void* x, int x_dtype, int64_t m, int64_t k, int6
 /* scaled matmul whose bias is  cast_svd( f32(bias[n]) + sum_r t[m][r]*svd_up[n][r] )  [+ zero-point terms]:
  *   zp_rowsum/zp (both or neither): adds f32(rowsum[m]) * sa[m] * zp[n]  (linear_int8.py:65-69);
  *   a_zp/w_colsum_scaled (both or neither; the uint8 matmul, linear_uint8.py:61-66): adds
- *       w_colsum_scaled[n] * a_zp[m]  +  K * (a_zp[m] * zp[n])      with w_colsum_scaled[n] = f32(sum_k b[n][k]) * sb[n]. */
+ *       w_colsum_scaled[n] * a_zp[m]  +  K * (a_zp[m] * zp[n])      with w_colsum_scaled[n] = f32(sum_k b[n][k]) * sb[n].
+ * t [M][rank] and svd_up [N][rank] are contiguous rows of svd_dtype elements and, like a / b / out, 16-byte aligned
+ * (SDNQ_ERR_ALIGN otherwise, as in sdnq_hip_scaled_mm_lp and its _zp / _uzp_svd forms): the epilogue reads them in 16-byte pieces. */
 int sdnq_hip_scaled_mm_lowrank(int mm_dtype, const void* a, const void* b, const float* sa, const float* sb,
                                const void* bias, int bias_dtype, const void* t, const void* svd_up, int svd_dtype,
                                int rank, const int32_t* zp_rowsum, const float* zp, const float* a_zp,

@@ -1466,6 +1466,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                                 for (int e = 0; e < 4; ++e) {
                                     const float vv = acc_times_sa<LP>(MT::tof(acc[i][j], 4 * q + e), sa);
                                     r[e] = fmaf(vv, sb4[e], b2[e]);
+                                    // float16 output: the reference rounds the fma to float32 and THAT to float16 (addcmul in float32, then
+                                    // .to(), kernel_wrappers.py:132-136).  Left visible to the compiler, fma + conversion fold into one
+                                    // v_fma_mixlo_f16 / _mixhi_f16, which rounds the exact vv sb + bias2d ONCE: another float16 whenever
+                                    // the float32 rounding lands on a float16 tie (tests/test_lowrank_exact_gpu.py, register layout f16)
+                                    if constexpr (OUT_T == SDNQ_F16) asm("" : "+v"(r[e]));
                                 }
                                 *(v2i*)(ostq + sr * O_ROW + nl0 * OUT_B) = (v2i){(int)pack2<OUT_T>(r[0], r[1]), (int)pack2<OUT_T>(r[2], r[3])};
                             }
@@ -2579,6 +2584,8 @@ extern "C" int sdnq_hip_scaled_mm_lowrank(int mm_dtype, const void* a, const voi
     if ((zp_rowsum == nullptr) != (zp == nullptr)) return SDNQ_ERR_NULL;
     if ((a_zp == nullptr) != (w_colsum_scaled == nullptr)) return SDNQ_ERR_NULL;
     if (t && (rank <= 0 || rank > 1024)) return SDNQ_ERR_SHAPE;
+    // as sdnq_hip_scaled_mm_lp_zp / _lp_uzp_svd: the epilogue reads the factors as 16-byte LDS-DMA pieces and v4i fragments
+    if (t && (((uintptr_t)t % 16) || ((uintptr_t)svd_up % 16))) return SDNQ_ERR_ALIGN;
     // the [M][N] bias of the reference lives in the svd dtype (addmm in svd_down.dtype, linear_int8.py:60);
     // a 1-D bias is cast to it first, so bias/t/up share one element type here.
     int bt = t ? svd_dtype : (bias ? bias_dtype : out_dtype);

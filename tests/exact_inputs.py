@@ -8,7 +8,7 @@ the same guarantee the int8 GEMM has on any input.
 
 The span the matrix cores keep was measured, not assumed: tools/micro/mfma_sum_probe.hip, output in profiles/mfma_sum_probe.txt
 (C = 2^s plus products equal to 1 is exact up to s = 23 for v_mfma_scale_f32_32x32x64_f8f6f4, v_mfma_f32_32x32x16_bf16 and
-v_mfma_f32_32x32x16_f16: the full float32 significand).
+v_mfma_f32_32x32x16_f16, and for v_mfma_f32_16x16x32_bf16 / _f16 of sdnq_hip_lowrank_down: the full float32 significand).
 """
 import math
 from dataclasses import dataclass
@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 # profiles/mfma_sum_probe.txt: "measured span, accumulator against products (a, b)", one per instruction
-MEASURED_SPAN_BITS = {"fp8": 23, "bf16": 23, "f16": 23}
+# ("bf16" / "f16": v_mfma_f32_32x32x16 of the GEMMs; "*_16x16x32": v_mfma_f32_16x16x32 of sdnq_hip_lowrank_down, the same 23 bits)
+MEASURED_SPAN_BITS = {"fp8": 23, "bf16": 23, "f16": 23, "bf16_16x16x32": 23, "f16_16x16x32": 23}
 # the budget of the dense cases: the measured span minus 2 bits (alignment cases the probe's few patterns may miss), at most 20
 B = {fmt: min(span - 2, 20) for fmt, span in MEASURED_SPAN_BITS.items()}
 

@@ -61,6 +61,16 @@ def test_argument_validation_without_gpu():
     assert lib.sdnq_hip_lowrank_down(p, 1, 4, 64, 64, p, 2, 32, p, None) == -2                         # activation / factor dtype mismatch
     assert lib.sdnq_hip_scaled_mm_lp_zp(0, p, p, p, p, None, 0, 0, None, None, 0, p, None, p, 32, 32, 32, None) == -1   # rowsum without zero point
     assert lib.sdnq_hip_scaled_mm_lp_zp(0, p, p, p, p, p, 2, 32, None, None, 0, p, p, p, 32, 32, 32, None) == -3        # zero point with a 2-D bias
+    # the low-rank factors are read as 16-byte pieces: one element off (2 bytes for bf16 / f16 factors, 4 for float32) is refused, by
+    # this entry as by its bf16-scale siblings
+    lrk = lib.sdnq_hip_scaled_mm_lowrank
+    assert lrk(0, p, p, p, p, None, 0, p + 2, p, 1, 32, None, None, None, None, p, 1, 32, 32, 32, None) == -4   # t, bf16
+    assert lrk(0, p, p, p, p, None, 0, p, p + 2, 2, 32, None, None, None, None, p, 2, 32, 32, 32, None) == -4   # svd_up, f16
+    assert lrk(1, p, p, p, p, None, 0, p + 4, p, 0, 32, None, None, None, None, p, 0, 32, 32, 32, None) == -4   # t, float32
+    assert lrk(0, p, p, p, p, None, 0, p, p + 4, 0, 32, None, None, None, None, p, 0, 32, 32, 32, None) == -4   # svd_up, float32
+    assert lrk(0, p, p, p, p, None, 0, p, None, 1, 32, None, None, None, None, p, 1, 32, 32, 32, None) == -1    # t without svd_up
+    assert lib.sdnq_hip_scaled_mm_lp(0, p, p, p, p, None, 0, 0, p + 2, p, 32, p, 32, 32, 32, None) == -4
+    assert lib.sdnq_hip_scaled_mm_lp_uzp_svd(p, p, p, p, None, None, None, p, p, 0, p, p + 2, 32, p, 32, 32, 32, None) == -4
     # matmuls on views (grouped convs)
     smm = lib.sdnq_hip_scaled_mm_strided
     assert smm(0, p, 16, p, p, p, None, 0, p, 32, 1, 32, 32, 32, 0, None) == -3                    # lda < K

@@ -21,8 +21,9 @@ def test_budget_comes_from_the_recorded_probe():
     import re
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "mfma_sum_probe.txt")
     spans = [int(v) for v in re.findall(r"measured span, accumulator against products \(a, b\): (\d+) bits", open(path).read())]
-    assert spans == [X.MEASURED_SPAN_BITS[f] for f in FMTS]
-    assert X.B == {f: min(X.MEASURED_SPAN_BITS[f] - 2, 20) for f in FMTS}
+    probed = FMTS + ("bf16_16x16x32", "f16_16x16x32")  # the file's order: the GEMMs' three instructions, then lowrank_down's two
+    assert spans == [X.MEASURED_SPAN_BITS[f] for f in probed]
+    assert X.B == {f: min(X.MEASURED_SPAN_BITS[f] - 2, 20) for f in probed}
     assert min(spans) >= 10  # below that the dense cases would have to fall back to {0, +-1} values and K <= 512
 
 
