@@ -870,6 +870,40 @@ int sdnq_hip_im2col_bwd(const void* dy, int dtype, int batch, int channels, int 
                         int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int groups, int64_t row0, int64_t rows,
                         void* out, sdnq_stream_t stream);
 
+/* ---- trainable low-rank adapters (LoRA) on frozen quantized Linear layers ------------------------------------------------------------------
+ * The reference has no adapters; these replace what a user assembles from torch ops around a quantized layer -- for a layer y = W x with
+ * the adapter branch scale * up . (down . x): `y + scale * (t @ up.t())` (an [M][N] product with an inner dimension of `rank`, a multiply
+ * and an add: five passes over [M][N]), the same on grad_input, and the two transposed products `dY.t() @ t` and `g_t.t() @ x` of the
+ * factor gradients.  t = down . x and g_t = up^T . dY are sdnq_hip_lowrank_down.
+ *
+ * sdnq_hip_lowrank_add: in place,
+ *     y[i][j] = round_dtype( fmaf(scale, sum_r f32(t[i][r]) * f32(up[j][r]), f32(y[i][j])) )
+ *   t [m][rank] and up [n][rank] contiguous, y [m] rows of ldy elements (ldy >= n: a column slice of a wider buffer is served; nothing
+ *   outside the m x n window is read or written), all of `dtype` = SDNQ_BF16 / SDNQ_F16 (SDNQ_F32: SDNQ_ERR_DTYPE).  The sum runs on the
+ *   matrix cores (v_mfma_f32_16x16x32, float32 accumulation, rank steps of 32; a step's chunks past `rank` are zero fragments in
+ *   registers, nothing is read past a row); every element is rounded once -- except that an element whose float32 sum is exactly zero is
+ *   stored back as it was read (fmaf(scale, +0, -0.0) would turn a -0.0 into +0.0: with up == 0 every bit of y is kept).  One read and one
+ *   write of y in 16-byte pieces, one launch, no workspace, no atomics.  Rows go to the launch grid's second axis in blocks of 64 (128 once the
+ *   launch has 512 blocks of 128 x 128): m up to 65535 * 64 = 4194240 rows (8388480 in the second form), more: SDNQ_ERR_SHAPE.  rank % 8 == 0, 8 <= rank <= 256, n % 8 == 0, m > 0 (else SDNQ_ERR_SHAPE); t, up, y and ldy * 2 bytes
+ *   16-byte aligned (else SDNQ_ERR_ALIGN).
+ *
+ * sdnq_hip_lowrank_grad: a product that reduces over the rows,
+ *     acc[j][r] = sum_i f32(a[i][j]) * f32(b[i][r])  (float32) ;  out = round_out_dtype(scale * acc)
+ *   a [m] rows of lda elements (lda >= p), b [m][rank] contiguous, both of `dtype` = SDNQ_BF16 / SDNQ_F16.  out: [p][rank] (out_t == 0) or
+ *   [rank][p] (out_t == 1) contiguous of out_dtype (SdnqFloat).  Deterministic: m is cut into slabs of 256 rows -- a constant of the
+ *   source, whatever the device or the grid -- a workgroup sums one (64-column tile, slab) on the matrix cores in float32, and with more
+ *   than one slab a second launch adds the slabs' partial sums in ascending order, ((s0 + s1) + s2) + ..., scales and rounds.  No atomics;
+ *   the same bits on every call; capturable in a graph.  workspace: sdnq_hip_lowrank_grad_workspace_bytes(m, p, rank) bytes (< 0:
+ *   SdnqStatus; 0 when m fits one slab, and NULL is then allowed), 16-byte aligned, owned by the caller until the stream has run the call;
+ *   a smaller one: SDNQ_ERR_SHAPE.  The slabs are the launch grid's second axis: m up to 65535 * 256 = 16776960 rows (SDNQ_ERR_SHAPE beyond).
+ *   p % 8 == 0, rank % 8 == 0, 8 <= rank <= 256, out_t 0 / 1 (SDNQ_ERR_SHAPE); a, b and lda * 2 bytes
+ *   16-byte aligned (SDNQ_ERR_ALIGN); everything is validated before the first launch. */
+int sdnq_hip_lowrank_add(const void* t, const void* up, int dtype, int rank, float scale, void* y, int64_t m, int64_t n, int64_t ldy,
+                         sdnq_stream_t stream);
+int64_t sdnq_hip_lowrank_grad_workspace_bytes(int64_t m, int64_t p, int rank);
+int sdnq_hip_lowrank_grad(const void* a, int64_t lda, const void* b, int dtype, int64_t m, int64_t p, int rank, float scale, int out_t,
+                          void* out, int out_dtype, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

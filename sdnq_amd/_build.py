@@ -42,7 +42,8 @@ UNITS = (
     # gemm.hip: the same for the GEMM kernel's 14 leading scalar arguments (tile mapping, operand descriptors, prologue DMAs)
     ("gemm", "-DSDNQ_PRELOAD_GEMM " + _PRELOAD, "SDNQ_PRELOAD_GEMM"),
     # the other kernels with scalar arguments get theirs preloaded as well: the GEMM variants, the weight-side units (dequant.hip's
-    # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax, ...
+    # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax,
+    # the adapter kernels of lowrank_train.hip, ...
     ("gemm_aq", _PRELOAD, None),
     ("gemm_ks", _PRELOAD, None),
     ("gemm_w4", _PRELOAD, None),
@@ -53,6 +54,7 @@ UNITS = (
     ("conv", _PRELOAD, None),
     ("convt", "", None),
     ("dequant_t", "", None),
+    ("lowrank_train", _PRELOAD, None),
     # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them
     # with VALU every block; in AGPR form the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),

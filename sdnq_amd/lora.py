@@ -1,0 +1,332 @@
+"""Trainable low-rank adapters (LoRA) on the frozen quantized Linear layers of an accelerated model, fused on HIP kernels.
+
+    y = layer(x) + scale * (x . down^T) . up^T          down [rank][K], up [N][rank], scale = alpha / rank
+
+``add_lora(model)`` registers ``lora_down`` / ``lora_up`` on every accelerated quantized Linear it serves and replaces the layer's
+``forward_func`` by a wrapper of this module.  The wrapper's base is the layer's own inference forward -- w8a8, fp8, uint8, the float16
+matmul, dequantize mode, the few-row branch, plans, linked projections -- so with ``up == 0`` the output bits are the inference call's.
+Per call:
+
+    forward      y   = base(layer, x)                          the layer's own route
+                 t   = ops.lowrank_down(x, down)               [M][rank], rounded to the layer dtype
+                 y  += scale * t . up^T                         ops.lowrank_add, in place, one rounding of y
+    backward     g_t = ops.lowrank_down(dY, up^T)              [M][rank]; its matrix-core kernel needs 16 | N: a layer with N % 16 == 8 (which
+                                                               add_lora serves) takes sdnq_hip_linear_float's few-row kernel there --
+                                                               the same values, much slower; not measured
+                 grad_input = ops.linear_float(dY, W^T)        as QuantizedLinearInputGrad computes it (ops.weight_t into the scratch)
+                 grad_input += scale * g_t . down              ops.lowrank_add, in place: one more rounding of grad_input
+                 grad_up    = scale * dY^T . t                 ops.lowrank_grad, [N][rank]
+                 grad_down  = scale * g_t^T . x                ops.lowrank_grad(out_t=True), [rank][K]
+                 grad_bias  = dY.sum(0)                        when the bias requires grad
+
+The wrapper handles input gradients itself; ``enable_input_grad`` called afterwards leaves these layers alone (it lists them as running
+a forward that is not its own).  The parameters go to ``sdnq_amd.optim.AdamW`` (``add_lora(...).parameters``).
+
+Not built, each raising or listed with its sentence: adapters on conv and embedding layers and on float32 layers; dropout, per-layer
+ranks, DoRA / rsLoRA; merging the adapter into the stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque
+whole-layer operator: the values of adapter inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper
+calls the base forward, which keeps its plan).
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib, ops, training
+from .linear import _attr
+
+_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def _workspace(dev: torch.device, nbytes: int):
+    """The float32 partial sums of ops.lowrank_grad: a fourth buffer of the per-device input-gradient scratch (training._SCRATCH), under
+    the rules of the other three -- grown to the largest seen, counted by training.scratch_bytes(), freed by training.release_scratch()."""
+    if nbytes == 0:
+        return None
+    bufs = training._SCRATCH.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [None, None, None])
+    while len(bufs) < 4:
+        bufs.append(None)
+    if bufs[3] is None or bufs[3].numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.SdnqHipError("adapter scratch: run one eager backward before capturing a graph (the buffer is not sized yet)")
+        bufs[3] = None
+        bufs[3] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    return bufs[3]
+
+
+def _factor_grad(a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype: torch.dtype) -> torch.Tensor:
+    ws = _workspace(a.device, ops.lowrank_grad_workspace_bytes(a.shape[0], a.shape[1], b.shape[1])) if a.shape[0] else None
+    return ops.lowrank_grad(a, b, scale, out_t=out_t, out_dtype=out_dtype, workspace=ws)
+
+
+def _check_call(layer, input: torch.Tensor) -> torch.dtype:
+    dt = layer.sdnq_dequantizer.result_dtype
+    if not input.is_cuda:
+        raise _lib.SdnqHipError("a quantized Linear with an adapter needs its input on a gfx950 device (got a CPU tensor); there is no CPU path")
+    if input.dtype != dt:
+        raise NotImplementedError(f"input of dtype {input.dtype} through an adapter on a layer whose compute dtype is {dt}: the adapter "
+                                  "products run in the layer's dtype")
+    return dt
+
+
+def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor):
+    """(y, x2d, t): the three steps of the forward with gradients off.  down / up: the factors in the layer dtype."""
+    y = base(layer, input)
+    x2d = training._rows(input)
+    n = up.shape[0]
+    if x2d.shape[0] == 0:
+        return y, x2d, x2d.new_empty((0, down.shape[0]))
+    t = ops.lowrank_down(x2d, down)
+    try:
+        y2d = y.view(-1, n)
+    except RuntimeError:
+        y = y.contiguous()
+        y2d = y.view(-1, n)
+    # in place unless the rows cannot be moved in 16-byte pieces or several of them are one piece of memory (an expanded view)
+    ld = ops._ld(y2d)  # (a single row: its length, whatever stride torch reports for the size-1 axis)
+    if y2d.stride(1) != 1 or ld < n or y2d.data_ptr() % 16 or (ld * y2d.element_size()) % 16:
+        y = y.clone(memory_format=torch.contiguous_format)
+        y2d = y.view(-1, n)
+    ops.lowrank_add(t, up, y2d, layer.lora_scale)
+    return y, x2d, t
+
+
+class QuantizedLinearLoRA(torch.autograd.Function):
+    """y = layer(input) + scale * (input . down^T) . up^T with a graph: gradients for the input, the two factors and the bias; the
+    weight, scale, zero point and SVD factors of the layer are frozen and get none.  Saves the module, the flattened input and t.  Not
+    differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, layer, base, input, down, up, bias=None):
+        dt = _check_call(layer, input)
+        with torch.no_grad():
+            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt))
+        ctx.layer, ctx.input_shape = layer, input.shape
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.save_for_backward(x2d, t, down, up)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        from . import linear
+        layer = ctx.layer
+        dq = layer.sdnq_dequantizer
+        x2d, t, down, up = ctx.saved_tensors
+        if grad_output.dtype != dq.result_dtype:
+            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
+                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
+        if not grad_output.is_cuda:
+            raise _lib.SdnqHipError("gradients through a quantized Linear with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
+        g2d = training._rows(grad_output)
+        dt, scale = g2d.dtype, layer.lora_scale
+        _, _, need_x, need_down, need_up, need_bias = ctx.needs_input_grad
+        grad_input = grad_down = grad_up = grad_bias = None
+        if g2d.shape[0] == 0:
+            if need_x:
+                grad_input = grad_output.new_zeros(ctx.input_shape)
+            grad_down = torch.zeros_like(down) if need_down else None
+            grad_up = torch.zeros_like(up) if need_up else None
+        else:
+            g_t = None
+            if need_x or need_down:
+                g_t = ops.lowrank_down(g2d, up.to(dt).t().contiguous())
+            if need_x:
+                qw = linear._state(layer).qw
+                had = dq.hadamard_group_size if dq.use_hadamard else 0
+                scratch = training._scratch(g2d.device, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)
+                gi2d = ops.linear_float(g2d, ops.weight_t(qw, dt, had, scratch), None)
+                ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
+                grad_input = gi2d.view(ctx.input_shape)
+            if need_up:
+                grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
+            if need_down:
+                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype)
+        if need_bias:
+            grad_bias = g2d.sum(0).to(ctx.bias_dtype)
+        return None, None, grad_input, grad_down, grad_up, grad_bias
+
+
+def _with_lora(base, previous):
+    grad_on = torch.is_grad_enabled
+
+    def forward(self, input):
+        down, up = _attr(self, "lora_down"), _attr(self, "lora_up")
+        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad):
+            return QuantizedLinearLoRA.apply(self, base, input, down, up, _attr(self, "bias"))
+        dt = _check_call(self, input)
+        with torch.no_grad():
+            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt))[0]
+    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_lora"
+    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
+    return forward
+
+
+def _refresh_compile_plan(module) -> None:
+    """Under torch.compile SDNQLayer.forward traces a planned layer as rowquant + matmul operators, which never reach forward_func;
+    torch_ops.layer_plan gives a layer that carries an adapter no such plan (whoever derives it: here, accelerate, a deepcopy), so it
+    traces as the ONE opaque whole-layer operator, which calls the wrapper: the values of adapter inference, no gradients there."""
+    if "_sdnq_hip_plan" in module.__dict__:
+        from . import torch_ops
+        try:
+            module.__dict__["_sdnq_hip_plan"] = torch_ops.layer_plan(module)
+        except Exception:  # noqa: BLE001  (as torch_ops.layer_handle: the whole-layer operator handles a module the rule cannot read)
+            module.__dict__["_sdnq_hip_plan"] = None
+
+
+def lora_unsupported_reason(module) -> str | None:
+    """None when `add_lora` serves `module` (an SDNQ layer); otherwise the sentence that says why not."""
+    from .common import linear_types
+    cls = getattr(module.sdnq_dequantizer, "layer_class_name", None)
+    if cls not in linear_types:
+        return f"{cls}: adapters are built for quantized Linear layers (conv, transposed-conv and embedding layers are not)"
+    if getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None:
+        return "the layer carries an adapter already (remove_lora(model) takes it off)"
+    why = training.input_grad_unsupported_reason(module)
+    if why is not None:
+        return why
+    dt = module.sdnq_dequantizer.result_dtype
+    if dt not in _DTYPES:
+        return f"layer dtype {dt}: adapters are built for bfloat16 and float16 layers (float32 layers are not)"
+    return None
+
+
+class LoRAResult(int):
+    """What `add_lora()` returns: an int (the number of layers that got an adapter) that also carries `.added`, `.skipped` --
+    [(qualified module name, reason)] of the SDNQ layers left without one -- and `.parameters`, the new nn.Parameters in module order
+    (down, up per layer): the list to hand to ``sdnq_amd.optim.AdamW``."""
+
+    def __new__(cls, added: int, skipped, parameters):
+        r = super().__new__(cls, added)
+        r.added, r.skipped, r.parameters = int(added), list(skipped), list(parameters)
+        return r
+
+
+def _selected(targets):
+    if targets is None:
+        return lambda name: True
+    if callable(targets):
+        return targets
+    subs = [targets] if isinstance(targets, str) else list(targets)
+    return lambda name: any(s in name for s in subs)
+
+
+def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None, targets=None, dtype: torch.dtype | None = None,
+             seed: int | None = None) -> LoRAResult:
+    """Put a trainable rank-`rank` adapter on every accelerated quantized Linear of `model` whose qualified name `targets` selects
+    (None: all; a list of substrings; or a predicate on the name).
+
+    Registers ``module.lora_down`` [rank, K] (kaiming-uniform as nn.Linear initialises its weight, drawn from `seed` in module order)
+    and ``module.lora_up`` [N, rank] (zeros) as nn.Parameters of `dtype` (default: the layer's dtype; torch.float32 for master weights,
+    cast to the layer dtype per call), stores ``module.lora_scale = (alpha or rank) / rank`` and replaces ``forward_func`` (see the module
+    docstring; a layer switched by ``enable_input_grad`` before is unwrapped to its inference forward -- the adapter's own backward
+    computes the input gradient).  Served: what ``training.input_grad_unsupported_reason`` accepts (16 | K, 8 | N, running on the MI355X
+    forwards) in bfloat16 or float16.  float32 layers, conv and embedding layers are left alone and listed in ``.skipped`` and in ONE
+    ``warnings.warn``.  8 <= rank <= 256, rank % 8 == 0.  Re-pointing a layer's forward afterwards (``accelerate``,
+    ``apply_sdnq_options_to_model``) takes the adapter off that layer's forward, eager and compiled alike, as it drops the switch of
+    ``enable_input_grad``: the parameters stay registered until ``remove_lora``; call ``add_lora`` after those, not before."""
+    if rank % 8 or not 8 <= rank <= 256:
+        raise ValueError(f"add_lora: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank}): the adapter kernels move 16-byte rank chunks")
+    if dtype is not None and dtype not in (torch.float32, *_DTYPES):
+        raise ValueError(f"add_lora: dtype must be None (the layer's), torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
+    pick = _selected(targets)
+    gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+    scale = float(alpha if alpha else rank) / rank
+    added, skipped, params = 0, [], []
+    for name, module in model.named_modules():
+        if getattr(module, "sdnq_dequantizer", None) is None or not pick(name):
+            continue
+        try:
+            why = lora_unsupported_reason(module)
+        except Exception as e:  # noqa: BLE001  a foreign record the predicate cannot read: leave the layer alone
+            why = f"{type(e).__name__} while reading the layer's record: {e}"
+        if why is not None:
+            skipped.append((name or type(module).__name__, why))
+            continue
+        dq = module.sdnq_dequantizer
+        n, k = int(dq.out_features), int(dq.in_features)
+        pdt = dq.result_dtype if dtype is None else dtype
+        dev = module.weight.device
+        bound = 1.0 / math.sqrt(k)  # kaiming_uniform_(a = sqrt(5)) on fan_in = K: sqrt(6 / ((1 + 5) K))
+        down = torch.empty((rank, k), dtype=torch.float32).uniform_(-bound, bound, generator=gen)
+        module.lora_down = torch.nn.Parameter(down.to(device=dev, dtype=pdt))
+        module.lora_up = torch.nn.Parameter(torch.zeros((n, rank), device=dev, dtype=pdt))
+        module.lora_scale = scale
+        fwd = module.forward_func
+        module.forward_func = _with_lora(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
+        _refresh_compile_plan(module)
+        params += [module.lora_down, module.lora_up]
+        added += 1
+    if skipped:
+        import warnings
+        warnings.warn(f"sdnq_amd.add_lora: {len(skipped)} SDNQ layer(s) got no adapter: "
+                      + "; ".join(f"{n} ({w})" for n, w in skipped[:8]) + (" ..." if len(skipped) > 8 else ""), stacklevel=2)
+    return LoRAResult(added, skipped, params)
+
+
+def _lora_modules(model: torch.nn.Module):
+    for name, module in model.named_modules():
+        if getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None:
+            yield name, module
+
+
+def remove_lora(model: torch.nn.Module) -> int:
+    """Take the adapters off: every layer gets back the very forward it had before `add_lora` and loses lora_down, lora_up and
+    lora_scale.  A layer whose forward was re-pointed after `add_lora` (see there) keeps the forward it has now and loses the three
+    attributes.  Returns the number of layers changed."""
+    count = 0
+    for module in list(model.modules()):
+        wrapped = getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None
+        if not wrapped and "lora_down" not in module.__dict__.get("_parameters", {}):
+            continue
+        if wrapped:
+            module.forward_func = module.forward_func._sdnq_lora_previous
+            _refresh_compile_plan(module)
+        for attr in ("lora_down", "lora_up", "lora_scale"):
+            if hasattr(module, attr):
+                delattr(module, attr)
+        count += 1
+    return count
+
+
+_PEFT_PREFIX = "base_model.model."
+
+
+def lora_state_dict(model: torch.nn.Module) -> dict:
+    """The adapters under PEFT's key names: ``<module>.lora_A.weight`` [rank, K] (lora_down) and ``<module>.lora_B.weight`` [N, rank]
+    (lora_up), detached.  alpha is not a tensor: PEFT keeps it in its config, here it is the `alpha` of `add_lora`."""
+    sd = {}
+    for name, module in _lora_modules(model):
+        sd[f"{name}.lora_A.weight"] = module.lora_down.detach()
+        sd[f"{name}.lora_B.weight"] = module.lora_up.detach()
+    return sd
+
+
+def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
+    """Copy `sd` (the keys of `lora_state_dict`; a leading ``base_model.model.`` and an adapter name as in ``lora_A.default.weight`` are
+    accepted) into the adapters `add_lora` put on `model`.  Every layer with an adapter must find both its keys and every key its layer,
+    with the shapes of the registered parameters: KeyError / ValueError otherwise.  Returns the number of layers loaded."""
+    import re
+    found = {}
+    for key, value in sd.items():
+        m = re.fullmatch(r"(.*)\.lora_([AB])(?:\.[^.]+)?\.weight", key[len(_PEFT_PREFIX):] if key.startswith(_PEFT_PREFIX) else key)
+        if m is None:
+            raise KeyError(f"load_lora_state_dict: {key!r} is not a <module>.lora_A.weight / <module>.lora_B.weight key")
+        found.setdefault(m.group(1), {})[m.group(2)] = value
+    mods = dict(_lora_modules(model))
+    missing = [n for n in found if n not in mods]
+    if missing:
+        raise KeyError(f"load_lora_state_dict: no adapter on {missing[:4]} (add_lora(model) registers them first)")
+    count = 0
+    for name, module in mods.items():
+        got = found.get(name, {})
+        if set(got) != {"A", "B"}:
+            raise KeyError(f"load_lora_state_dict: {name} needs both lora_A.weight and lora_B.weight (got {sorted(got)})")
+        for p, v, what in ((module.lora_down, got["A"], "lora_A"), (module.lora_up, got["B"], "lora_B")):
+            if tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f"load_lora_state_dict: {name}.{what}.weight has shape {tuple(v.shape)}, the adapter {tuple(p.shape)}")
+            with torch.no_grad():
+                p.copy_(v)
+        count += 1
+    return count

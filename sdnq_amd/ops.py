@@ -1007,6 +1007,104 @@ def lowrank_down(x2d: torch.Tensor, svd_down_phys: torch.Tensor) -> torch.Tensor
     return t
 
 
+def _ld(t: torch.Tensor) -> int:
+    """The row stride the library is given: the tensor's, or the row length for a single row (torch leaves the stride of a size-1 axis
+    arbitrary, and nothing steps over it)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _lowrank_check(what: str, rank: int, **tensors) -> None:
+    """The checks the two adapter entry points share: device tensors of ONE 16-bit dtype, 8 <= rank <= 256 a multiple of 8, 2-D operands
+    with contiguous, 16-byte aligned rows -- each failure names what is wrong.  (The device check comes last, in the callers: what a call
+    gets wrong about shapes and dtypes does not depend on where its tensors live.)"""
+    dt = next(iter(tensors.values())).dtype
+    if dt not in (torch.bfloat16, torch.float16):
+        raise _lib.SdnqHipError(f"{what}: built for bfloat16 / float16 operands (got {dt})")
+    if rank % 8 or not 8 <= rank <= 256:
+        raise _lib.SdnqHipError(f"{what}: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank})")
+    for name, t in tensors.items():
+        if t.dtype != dt:
+            raise _lib.SdnqHipError(f"{what}: {name} must have the dtype of the other operands (got {t.dtype}, {dt})")
+        if t.ndim != 2 or t.stride(1) != 1 or _ld(t) < t.shape[1]:
+            raise _lib.SdnqHipError(f"{what}: {name} must be 2-D with contiguous rows (got shape {tuple(t.shape)}, strides {t.stride()})")
+        if t.data_ptr() % 16 or (_ld(t) * 2) % 16:
+            raise _lib.SdnqHipError(f"{what}: {name} is misaligned: its rows must start on 16 bytes (storage offset "
+                                    f"{t.storage_offset()}, row stride {t.stride(0)} elements)")
+
+
+def lowrank_add(t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """sdnq_hip_lowrank_add: y [M, N] += scale * t [M, R] @ up [N, R]^T IN PLACE on the matrix cores, every element rounded once:
+    y = round(fma(scale, sum_r t up, y)).  bfloat16 / float16; y may be a column slice of a wider buffer (unit column stride, 16-byte
+    aligned rows); t and up contiguous.  Returns y."""
+    if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
+        raise _lib.SdnqHipError(f"lowrank_add: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    (m, r), (n, r2) = t.shape, up.shape
+    _lowrank_check("lowrank_add", r, t=t, up=up, y=y)
+    if r2 != r or tuple(y.shape) != (m, n):
+        raise _lib.SdnqHipError(f"lowrank_add: t [M, R], up [N, R], y [M, N] (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    if n % 8:
+        raise _lib.SdnqHipError(f"lowrank_add: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
+    if not t.is_contiguous() or not up.is_contiguous():
+        raise _lib.SdnqHipError("lowrank_add: t and up must be contiguous")
+    _require_cuda(t, up, y)
+    if m == 0:
+        return y
+    check(_lib.load().sdnq_hip_lowrank_add(t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y),
+                                           _stream(y)), "lowrank_add")
+    return y
+
+
+def lowrank_grad_workspace_bytes(m: int, p: int, rank: int) -> int:
+    """sdnq_hip_lowrank_grad_workspace_bytes: 0 while the m rows fit one slab of the deterministic reduction."""
+    nbytes = _lib.load().sdnq_hip_lowrank_grad_workspace_bytes(m, p, rank)
+    if nbytes < 0:
+        check(int(nbytes), "lowrank_grad_workspace_bytes")
+    return int(nbytes)
+
+
+def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bool = False, out_dtype: torch.dtype | None = None,
+                 workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_lowrank_grad: round(scale * a [M, P]^T @ b [M, R]) -> [P, R] (out_t: [R, P]) of `out_dtype` (default: the operands'),
+    float32 sums on the matrix cores over slabs of rows added in a fixed order: the same bits on every call, no atomics.  a may be a
+    column slice (unit column stride, 16-byte aligned rows), b contiguous; bfloat16 / float16.  workspace: a uint8 tensor of at least
+    lowrank_grad_workspace_bytes(M, P, R) bytes, or None -- then the per-(device, stream) buffer of this module (_workspace: at least 1 MB,
+    kept for the life of the process, NOT counted by training.scratch_bytes() nor freed by training.release_scratch(); sdnq_amd.lora passes
+    its own, which is) is used, and a call that would have to grow it while its stream is being captured raises before any launch."""
+    if a.ndim != 2 or b.ndim != 2:
+        raise _lib.SdnqHipError(f"lowrank_grad: a and b must be 2-D (got {tuple(a.shape)}, {tuple(b.shape)})")
+    (m, p), (m2, r) = a.shape, b.shape
+    _lowrank_check("lowrank_grad", r, a=a, b=b)
+    if m2 != m:
+        raise _lib.SdnqHipError(f"lowrank_grad: a [M, P] and b [M, R] must have the same rows (got {tuple(a.shape)}, {tuple(b.shape)})")
+    if p % 8:
+        raise _lib.SdnqHipError(f"lowrank_grad: p % 8 == 0 (got p = {p}): a is read in 16-byte pieces")
+    if not b.is_contiguous():
+        raise _lib.SdnqHipError("lowrank_grad: b must be contiguous")
+    _require_cuda(a, b, workspace)
+    out_dtype = a.dtype if out_dtype is None else out_dtype
+    out = torch.empty((r, p) if out_t else (p, r), device=a.device, dtype=out_dtype)
+    code = float_code(out_dtype)
+    if m == 0:
+        return out.zero_()
+    need = lowrank_grad_workspace_bytes(m, p, r)
+    if need and workspace is None:
+        have = _workspaces.get((a.device.index, _stream(a)))
+        if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
+            raise _lib.SdnqHipError("lowrank_grad: the module's workspace would have to grow inside a graph capture; pass workspace= or run "
+                                    "one eager call on this stream first")
+        workspace = _workspace(a.device, _stream(a), need + 16)
+    if need and (not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need):
+        raise _lib.SdnqHipError(f"lowrank_grad: workspace must be a uint8 device tensor of at least {need} bytes")
+    wp = 0
+    if need:
+        wp = (workspace.data_ptr() + 15) & ~15
+        if wp + need > workspace.data_ptr() + workspace.numel():
+            raise _lib.SdnqHipError(f"lowrank_grad: workspace must hold {need} bytes behind its first 16-byte boundary")
+    check(_lib.load().sdnq_hip_lowrank_grad(a.data_ptr(), _ld(a), b.data_ptr(), float_code(a.dtype), m, p, r, float(scale), int(bool(out_t)),
+                                            out.data_ptr(), code, wp or None, need, _stream(a)), "lowrank_grad")
+    return out
+
+
 _workspaces: dict = {}
 
 

@@ -372,9 +372,12 @@ except Exception:  # noqa: BLE001  (a torch build without Inductor)
 
 def layer_plan(module: torch.nn.Module):
     """("q", matmul dtype name, hadamard group) when the layer's forward at M >= 32 is exactly rowquant + scaled_mm (row-wise or
-    re-quantized weights, no zero-point term, no SVD, fp32 scales), else None: decided from the module's static configuration."""
+    re-quantized weights, no zero-point term, no SVD, fp32 scales, no adapter on the layer), else None: decided from the module's static
+    configuration and the forward it carries."""
     from .common import dtype_dict
     dq = module.__dict__.get("sdnq_dequantizer")
+    if getattr(module.__dict__.get("forward_func"), "_sdnq_lora_base", None) is not None:
+        return None  # a low-rank adapter (sdnq_amd.lora) lives in forward_func: only the whole-layer operator, which calls it, computes the layer
     if dq is None or not dq.use_quantized_matmul or dq.is_conv or getattr(module, "svd_up", None) is not None:
         return None
     mmd = str(dq.quantized_matmul_dtype).replace("torch.", "")
