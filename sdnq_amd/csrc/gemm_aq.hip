@@ -18,6 +18,15 @@
 // Bit-identical to the two-launch route by construction (the same quant8, the same MFMA, the same epilogue expression) and by
 // tests/test_gemm_aq.py; tests/test_gemm_aq_geometry.py runs the same cases on each tile geometry below.
 //
+// The 32 x 256 tile runs WAVE-PRIVATE weight slabs (SLAB in the kernel): its waves are laid out 1 x 8, so every wave multiplies the same
+// 32 activation rows by its own 32 weight rows and no weight byte is read by two waves -- the ring is a landing place only.  There a
+// wave moves its own rows (four pieces of every stage), all three ring slots are in flight behind the rows, and a stage is drained by
+// its wave alone: counted vmcnt for its own pieces, fragments into registers, the slot refilled with stage j + 3 at once.  Two stages
+// are drained under the quantization, the others in a K loop without a barrier, in the ring form's order of stages and sub-steps: the
+// same bits (tests/test_gemm_aq_regslab.py: a placement census of every weight byte, every stage count and edge).  Draining ALL stages
+// into registers under the quantization (160 registers per lane; built and measured) lost: the MFMAs then start only when the last
+// weight byte has landed.
+//
 // Quantization layout (64 x 128 tile; the 32 x 256 tile: rows 4w .. 4w+3, one pass): wave w owns tile rows 8w .. 8w+7 in two passes of 4 rows; a row is read by a QUARTER wave (16 lanes x 16 bytes
 // = 128 elements per load instruction = one K stage), so the row amax is a reduction inside one 16-lane DPP row (four DPP exchanges,
 // no LDS) and lane l's j-th chunk (8 elements) IS bytes 8 (l & 15) .. +8 of stage j's row: one ds_write_b64.
@@ -29,7 +38,8 @@ namespace {
 // Tile geometries (template parameters BM x BN of the kernel and its ring depth; BK, the wave count and the 32x32 MFMA are common):
 //   0: 64 x 128, 4 ring slots : waves 2 x 4; a wave quantizes 8 rows in two passes; 16-KB weight stages; tiles_n workgroups repeat a row block
 //   1: 32 x 256, 3 ring slots : waves 1 x 8; a wave quantizes 4 rows in one pass (half the ingest and the arithmetic in front of the K loop,
-//                               half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280
+//                               half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280; every wave
+//                               moves and drains its own weight rows, no barrier in the K loop (the slab form: BN / 32 == NW)
 // and two "tall" forms for K <= 640 (five stages held) where the 64 x 128 tiles of a problem outnumber the CUs:
 //   2: 64 x 128, 2 ring slots : the tile of geometry 0 on a thin ring: 40 KB image + 32 KB ring, so TWO workgroups share a CU (the second
 //                               one hides the first one's stage waits, as in the two-launch GEMM's 3 slots x 2 workgroups) and
@@ -49,6 +59,7 @@ struct AqParams {
     unsigned long long* trace;  // lab: per-workgroup phase stamps (8 per workgroup), or null
 #ifdef SDNQ_AQ_LAB
     int lab;  // lab build (timing only, results invalid): 1 no loop DMAs, 2 no fragment reads, 4 no MFMAs, 8 no barrier, 16 no quantization arithmetic
+              // (the slab form of the 32 x 256 tile has no loop barrier and counts on every DMA: bits 1 and 8 do nothing there)
 #endif
 };
 
@@ -94,6 +105,12 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     constexpr int PS = BM / (4 * NW);   // quantization passes of a wave: 4 rows (one per quarter wave) each
     constexpr int PPW = BN / (8 * NW);  // 1-KB ring pieces (8 weight rows) of a stage that one wave moves
     static_assert(PS >= 1 && PS <= 4 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
+    // SLAB: every wave owns a private 32-column block (waves 1 x NW: geometry 1).  No weight byte is read by two waves, so a wave moves its
+    // OWN 32 weight rows (pieces PPW w .. PPW w + PPW - 1 of every stage), takes each landed stage from its ring slot into registers,
+    // refills the slot with stage j + NSB at once, and needs no barrier between the one that publishes the codes and the epilogue.
+    constexpr bool SLAB = BN / 32 == NW;
+    constexpr int KS = BK / MT::KB;
+    static_assert(!SLAB || (NSB <= NJ && PPW == 4), "register slab: the ring is no deeper than the stages held; a wave's 32 rows are four pieces");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t* const ldsA = lds;                       // [NJ][BM rows][128 B] quantized activation rows, resident
     uint8_t* const ldsB = lds + NJ * A_STAGE;        // [NSB][BN rows][128 B] weight ring
@@ -129,21 +146,23 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         for (int j = 0; j < NJ; ++j) xr[ps][j] = SDNQ_BUF_LOAD16(rsX, vo, j < nk ? j * 256 : 0x40000000);  // stages past K: out of range = zeros
     }
     // ---- weight ring prologue: piece = 8 rows x 128 B, lane l -> row l / 8, physical chunk l % 8 (source chunk = swizzle-inverse);
-    // wave w owns pieces w, w + 8, ... (PPW of them) of every stage; constant per-lane offsets, the K advance in the scalar operand
+    // wave w owns pieces w, w + 8, ... (PPW of them) of every stage -- in the register-slab form pieces PPW w ..: its own 32 weight rows;
+    // constant per-lane offsets, the K advance in the scalar operand
     const auto rsB = SDNQ_MAKE_RSRC_N(w + (int64_t)n0 * ldb, (int64_t)(n_lim - 1) * ldb + K);
     int voB[PPW];
+    auto pieceB = [&](int u) { return SLAB ? wave * PPW + u : wave + u * NW; };
 #pragma unroll
     for (int u = 0; u < PPW; ++u) {
-        const int r = (wave + u * NW) * 8 + (lane >> 3);
+        const int r = pieceB(u) * 8 + (lane >> 3);
         const int rc = r < n_lim ? r : n_lim - 1;
         voB[u] = rc * ldb + (((lane & 7) ^ ((r >> 1) & 7)) << 4);
     }
     auto issueB = [&](int st, int slot) {  // stages past the end re-fetch stage 0 (never consumed; keeps the counted vmcnt a constant)
         const int s = st < nk ? st : 0;
 #pragma unroll
-        for (int u = 0; u < PPW; ++u) SDNQ_DMA16(rsB, ldsB + slot * B_STAGE + (wave + u * NW) * 1024, voB[u], s * BK);
+        for (int u = 0; u < PPW; ++u) SDNQ_DMA16(rsB, ldsB + slot * B_STAGE + pieceB(u) * 1024, voB[u], s * BK);
     };
-    constexpr int AHEAD = NSB - 1;
+    constexpr int AHEAD = SLAB ? NSB : NSB - 1;  // ring stages in flight behind the rows (the slab form has no slot to hold back: it refills as it drains)
 #pragma unroll
     for (int s = 0; s < AHEAD; ++s) issueB(s, s);
     __builtin_amdgcn_sched_barrier(0);
@@ -164,6 +183,29 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 
     // ---- row quantization: amax inside the 16-lane row group, IEEE scale, lean codes -> the resident LDS image -------------------------
     constexpr float QMAX = (MM == SDNQ_MM_I8) ? 127.0f : 448.0f;
+    // slab form, draining weight stage j: the wave waits for its own four pieces of the stage -- loads return in order, so a count of the
+    // pieces issued after them --, reads its KS fragments out of the ring slot into `dst` and, those reads retired, refills the slot with
+    // stage j + NSB.  Stages past K are issued all the same (issueB's filler: the counts stay constants) and never read.
+    // The first DF stages are drained under the quantization, behind the codes of its last DF stages, into registers of their own (16 per
+    // stage, statically indexed); every later stage in the K loop, in front of its MFMAs.  DF = 2 measured best in the step: 0 leaves the
+    // fill path idle behind the three prologue stages, 3 / 4 / all ten hold up the quantization -- and with it the barrier every wave's
+    // MFMAs wait for -- on weights that have not landed yet (profiles/linear_aq_32x256_regslab.txt).
+    constexpr int DF = !SLAB ? 0 : (NJ < 2 ? NJ : 2);
+    typename MT::frag_t fbr[DF > 0 ? DF : 1][KS], fbs[KS];
+    auto drainB = [&](int j, typename MT::frag_t* dst) {
+        if (j < nk) {
+            static_for_up<NJ>([&](auto jc) {
+                constexpr int later = NJ - 1 - decltype(jc)::value;  // stages issued behind stage j so far
+                if (decltype(jc)::value == j) wait_vmcnt<PPW * (later < NSB - 1 ? later : NSB - 1)>();
+            });
+#ifdef SDNQ_AQ_LAB
+            if (!(p.lab & 2))
+#endif
+            static_for_up<KS>([&](auto ksc) { dst[decltype(ksc)::value] = MT::load(ldsB + (j % NSB) * B_STAGE, wave * 32 + (lane & 31), decltype(ksc)::value, lane >> 5); });
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+        if (j + NSB < NJ) issueB(j + NSB, j % NSB);
+    };
 #pragma unroll
     for (int ps = 0; ps < PS; ++ps) {
         // loads return in order: a pass has landed when at most the NJ loads of each later pass and this wave's PPW AHEAD ring pieces are outstanding
@@ -215,7 +257,15 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         // / inf / nan row), else the general path for all four rows (same codes: quant8 takes the same lean branch lane by lane)
         const bool all_fast = __builtin_amdgcn_ballot_w64(!rd.fast) == 0;
 #ifdef SDNQ_AQ_LAB
-        if (p.lab & 16) continue;
+        if (p.lab & 16) {
+            if constexpr (SLAB) {
+                if (ps == PS - 1) {
+#pragma unroll
+                    for (int j = 0; j < DF; ++j) drainB(j, fbr[j]);
+                }
+            }
+            continue;
+        }
 #endif
         if (all_fast) {
 #pragma unroll
@@ -225,6 +275,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
                 Vec16<X_T>::unpack(make_uint4((u32)t[0], (u32)t[1], (u32)t[2], (u32)t[3]), v);
                 const uint2 q = quant8_fast<MM>(v, rd);
                 *(v2i*)(dst + j * A_STAGE) = (v2i){(int)q.x, (int)q.y};  // (ext-vector store: a HIP-struct store drains the LDS-DMAs first)
+                if constexpr (DF > 0) { if (ps == PS - 1 && j >= NJ - DF) drainB(j - (NJ - DF), fbr[j - (NJ - DF)]); }
             }
         } else {  // (unrolled as well: a run-time index into the row registers would put them in scratch memory)
 #pragma unroll
@@ -235,10 +286,13 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
                 int isum = 0;
                 const uint2 q = quant8<MM>(v, rd, isum);
                 *(v2i*)(dst + j * A_STAGE) = (v2i){(int)q.x, (int)q.y};
+                if constexpr (DF > 0) { if (ps == PS - 1 && j >= NJ - DF) drainB(j - (NJ - DF), fbr[j - (NJ - DF)]); }
             }
         }
     }
-    if (tid < BN) {
+    // the per-channel vectors are parked here -- in the slab form behind the K loop: they were requested behind the ring prologue, and a
+    // wait for them in front of the loop would wait for every prologue stage of the wave as well
+    if (tid < BN && !SLAB) {
         s_sb[tid] = ev_sb;
         if constexpr (HAS_BIAS)
             s_bias[tid] = p.bias_dtype == SDNQ_F32 ? __uint_as_float(ev_bias) : (p.bias_dtype == SDNQ_BF16 ? __uint_as_float(ev_bias << 16) : f16_bits_to_f32((uint16_t)ev_bias));
@@ -253,58 +307,96 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         for (int e = 0; e < 16; ++e) acc[a][e] = 0;
     const int wm = (wave / (BN / 32)) * NACC, wn = wave % (BN / 32);  // first 32-row block, 32-column block of the wave
     const int frow = lane & 31, fgrp = lane >> 5;
-    constexpr int KS = BK / MT::KB;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's codes and scales are in LDS before the first barrier lets anyone read them
-    // Software pipeline one STAGE deep (the LD_OV form of gemm.hip, profiles/r05_overlapped_ring_lab.txt): the fragments of stage kt sit in
-    // registers when its barrier falls, so the MFMAs start at once; dealt out between them are the fragment reads of stage kt + 1 (which that
-    // barrier published) and the DMA pieces of stage kt + NSB into the slot stage kt has just vacated -- NSB - 1 stages in flight behind the
-    // landed one.  Two register sets, so the loop is unrolled by two.
-    typename MT::frag_t fa[2][NACC][KS], fb[2][KS];
-    auto read_stage = [&](auto setc, auto ksc, int st, int slot) {
-        constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
-        fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
-    };
-    wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    issueB(AHEAD, AHEAD);              // the ring's last free slot
-    static_for_up<KS>([&](auto ksc) { read_stage(std::integral_constant<int, 0>{}, ksc, 0, 0); });
-    int slot_c = 0;  // ring slot of the stage whose fragments are in registers
 #ifdef SDNQ_AQ_LAB
     const int lab = __builtin_amdgcn_readfirstlane(p.lab);
 #else
     constexpr int lab = 0;  // (run-time switches inside the K loop cost it 35 %: a lab build only)
 #endif
-    auto half = [&](auto setc, int kt) {
-        constexpr int sx = decltype(setc)::value;
-        wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads of stage kt have retired: the slot may be refilled
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(lab & 8)) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const int slot_free = slot_c;
-        slot_c = (slot_c + 1 == NSB) ? 0 : slot_c + 1;
-        // MFMA ks of stage kt, then read ks of stage kt + 1 (the last sub-step's reads retire under the next barrier's wait; KS <= 4)
-        static_for_up<KS>([&](auto ksc) {
-            constexpr int ks = decltype(ksc)::value;
-            if (!(lab & 4)) {
+    typename MT::frag_t fa[2][NACC][KS];
+    if constexpr (SLAB) {
+        // Slab form: the one barrier below publishes the A image; behind it a wave depends on nobody -- it waits for its OWN pieces of a
+        // stage (counted vmcnt), takes them into registers, refills the slot and multiplies, so the waves drift apart and every wave
+        // keeps NSB stages in flight of its own accord (the ring form refills a slot only once all eight waves have left it).  Stages
+        // 0 .. nk - 1 and their sub-steps in the ring form's order: the accumulation order of every element is the same.  The A
+        // fragments stay software-pipelined one stage deep over two register sets (the stage count is a template constant: unrolled).
+        auto read_a = [&](auto setc, auto ksc, int st) {
+            constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
 #pragma unroll
-                for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fb[sx][ks], fa[sx][a][ks]);
+            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+        };
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        static_for_up<KS>([&](auto ksc) { read_a(std::integral_constant<int, 0>{}, ksc, 0); });
+        static_for_up<NJ>([&](auto ktc) {
+            constexpr int kt = decltype(ktc)::value, sx = kt & 1;
+            if (kt < nk) {
+                if constexpr (kt >= DF) drainB(kt, fbs);
+                __builtin_amdgcn_sched_barrier(0);
+                static_for_up<KS>([&](auto ksc) {
+                    constexpr int ks = decltype(ksc)::value;
+                    if (!(lab & 4)) {
+#pragma unroll
+                        for (int a = 0; a < NACC; ++a) MT::mma(acc[a], kt < DF ? fbr[kt < DF ? kt : 0][ks] : fbs[ks], fa[sx][a][ks]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (kt + 1 < NJ) { if (!(lab & 2)) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1); }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
             }
-            __builtin_amdgcn_sched_barrier(0);
-            if (!(lab & 2)) read_stage(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1, slot_c);
-            if constexpr (ks == 0) { if (!(lab & 1)) issueB(kt + NSB, slot_free); }
-            __builtin_amdgcn_sched_barrier(0);
         });
-    };
+    } else {
+        // Software pipeline one STAGE deep (the LD_OV form of gemm.hip, profiles/r05_overlapped_ring_lab.txt): the fragments of stage kt sit in
+        // registers when its barrier falls, so the MFMAs start at once; dealt out between them are the fragment reads of stage kt + 1 (which that
+        // barrier published) and the DMA pieces of stage kt + NSB into the slot stage kt has just vacated -- NSB - 1 stages in flight behind the
+        // landed one.  Two register sets, so the loop is unrolled by two.
+        typename MT::frag_t fb[2][KS];
+        auto read_stage = [&](auto setc, auto ksc, int st, int slot) {
+            constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
+#pragma unroll
+            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+            fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
+        };
+        wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        issueB(AHEAD, AHEAD);              // the ring's last free slot
+        static_for_up<KS>([&](auto ksc) { read_stage(std::integral_constant<int, 0>{}, ksc, 0, 0); });
+        int slot_c = 0;  // ring slot of the stage whose fragments are in registers
+        auto half = [&](auto setc, int kt) {
+            constexpr int sx = decltype(setc)::value;
+            wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads of stage kt have retired: the slot may be refilled
+            __builtin_amdgcn_sched_barrier(0);
+            if (!(lab & 8)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            const int slot_free = slot_c;
+            slot_c = (slot_c + 1 == NSB) ? 0 : slot_c + 1;
+            // MFMA ks of stage kt, then read ks of stage kt + 1 (the last sub-step's reads retire under the next barrier's wait; KS <= 4)
+            static_for_up<KS>([&](auto ksc) {
+                constexpr int ks = decltype(ksc)::value;
+                if (!(lab & 4)) {
+#pragma unroll
+                    for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fb[sx][ks], fa[sx][a][ks]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (!(lab & 2)) read_stage(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1, slot_c);
+                if constexpr (ks == 0) { if (!(lab & 1)) issueB(kt + NSB, slot_free); }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        };
 #pragma nounroll
-    for (int kt = 0; kt < nk; kt += 2) {
-        half(std::integral_constant<int, 0>{}, kt);
-        if (kt + 1 < nk) half(std::integral_constant<int, 1>{}, kt + 1);
+        for (int kt = 0; kt < nk; kt += 2) {
+            half(std::integral_constant<int, 0>{}, kt);
+            if (kt + 1 < nk) half(std::integral_constant<int, 1>{}, kt + 1);
+        }
     }
     SDNQ_PHASE_STAMP(p.trace, 3);
+    if (tid < BN && SLAB) {  // (the barrier below publishes them to the epilogue)
+        s_sb[tid] = ev_sb;
+        if constexpr (HAS_BIAS)
+            s_bias[tid] = p.bias_dtype == SDNQ_F32 ? __uint_as_float(ev_bias) : (p.bias_dtype == SDNQ_BF16 ? __uint_as_float(ev_bias << 16) : f16_bits_to_f32((uint16_t)ev_bias));
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing filler DMAs target the ring; the staging area below is the A image
     __syncthreads();                                  // every wave is done with the A image before it becomes the output staging area
     SDNQ_PHASE_STAMP(p.trace, 4);

@@ -55,6 +55,7 @@ for (m, n, k) in shapes:
             print("  fused route refused:", e)
         print(f"{m}x{n}x{k} {tag:18s}: two launches {two:7.2f} us | one launch {one:7.2f} us   (supported() = {sup})", flush=True)
     # phase stamps (shader clock, 100 MHz memtime ticks -> reported in ticks): entry, loads+ring issued, quantized, K loop done, synced, staged, stored
+    # (the 32 x 256 tile drains its first two weight stages before "quantized", and its "K loop" has no barrier: thread 0's own loop)
     try:
         buf = torch.zeros(1024 * 8, dtype=torch.int64, device=dev)
         aq_trace = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z22sdnq_internal_aq_tracePy")
