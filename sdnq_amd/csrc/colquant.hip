@@ -22,7 +22,9 @@
 // Traffic for a 16-bit input: 2 reads of x + 1 write of codes = 5 B per element, plus 8 B x C x slabs of partials: written once (at most
 // 256 B per column), re-read by every row tile for its 64 columns (up to 16 KiB per tile; expected in L2, not measured).
 // NaN: fmaxf drops a NaN operand, so a NaN in x does not reach the scale (torch's amax would propagate it).  This is
-// sdnq_hip_rowquant's convention; the reference's result for such a column is a NaN cast to int8, which is undefined.
+// sdnq_hip_rowquant's convention; the reference's result for such a column is a NaN cast to int8, which is undefined.  An inf makes its
+// column's scale inf: every finite element gets code 0 and the inf itself (inf / inf) -128, again as sdnq_hip_rowquant has it
+// (tests/test_colquant_exact_gpu.py holds the two kernels to each other on NaN, +inf, -inf and all-zero columns).
 #include "quant8_dev.h"
 #include "sdnq_dev.h"
 
@@ -170,8 +172,9 @@ __global__ __launch_bounds__(256) void colquant_t_kernel(const void* __restrict_
                 w = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
+                    // the row quantizer's expression as it stands (quant8 in quant8_dev.h), so a NaN quotient -- +-inf under the scale inf
+                    // of its own column -- leaves the clamp as -128 here as it does there, not as a code of this kernel's own
                     float q = (rd.scale == 0.0f) ? 0.0f : __builtin_rintf(v[j][e] / rd.scale);
-                    if (q != q) q = 0.0f;
                     q = fminf(fmaxf(q, -128.0f), 127.0f);
                     w |= ((u32)(int)q & 0xffu) << (8 * j);
                 }

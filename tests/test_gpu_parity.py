@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import rowquant_inputs
 from tests.golden_util import GOLD, Case, case_names
 from tests.modules_util import TORCH_DT, module_from_case, to_f32_numpy
 
@@ -294,17 +295,7 @@ def test_rowquant_bit_exact_vs_oracle(m, k, dt, gpu_device):
 def test_rowquant_rounding_ties_and_near_ties(gpu_device):
     """Rows built so that MANY quotients x / scale are exact rounding ties (k + 0.5 -> half to even) or sit one ulp beside one:
     the codes must be the reference's bit for bit (any shortcut around the IEEE division would show here first)."""
-    rng = np.random.default_rng(7)
-    rows = []
-    for amax in (127.0, 254.0, 63.5, 190.5, 381.0):  # scale = amax / 127 = 1, 2, 0.5, 1.5, 3
-        s = amax / 127.0
-        halves = (rng.integers(-126, 126, size=1280) + 0.5) * s  # exact ties in f32
-        halves[0] = amax
-        rows.append(halves)
-        near = halves.copy().astype(np.float32)
-        near[1:] = np.nextafter(near[1:], np.float32(np.inf) * np.sign(rng.standard_normal(1279)).astype(np.float32))  # one ulp off a tie
-        rows.append(near)
-    x = torch.from_numpy(np.stack(rows).astype(np.float32))
+    x = torch.from_numpy(rowquant_inputs.ties_and_near_ties())
     for asym in (False, True):
         if asym:
             got = ops.rowquant(x.to(gpu_device), ops.MM_I8, asymmetric=True)
@@ -1430,25 +1421,7 @@ def test_rowquant_division_shortcut_over_the_exponent_range(dt, gpu_device):
     number, with the IEEE sequence otherwise.  Rows spanning the whole exponent range -- both sides of the 2^+-60 guard,
     subnormal-scale rows, scales whose significand is all ones (the one case where RN(1 / s) is too coarse), ties and near-ties at
     every magnitude -- must give the reference's codes and scales bit for bit, int8 and fp8."""
-    rng = np.random.default_rng(11)
-    k = 1536
-    rows = []
-    for e in list(range(-120, 121, 4)) + [-126, -61, -60, -59, 59, 60, 61, 120]:
-        base = rng.standard_normal(k).astype(np.float32) * np.float32(0.3)
-        base[0] = 1.0
-        rows.append(np.ldexp(base, e).astype(np.float32))
-        # scale with an all-ones significand: amax = 127 * (2 - 2^-23) * 2^e
-        s = np.ldexp(np.float32(2.0) - np.float32(2.0 ** -23), e)
-        r = (rng.integers(-126, 127, size=k) + rng.choice([0.0, 0.5], size=k)).astype(np.float64) * np.float64(s)
-        r[0] = 127.0 * np.float64(s)
-        rows.append(r.astype(np.float32))
-        # ties / near ties around an ordinary scale at this magnitude
-        s2 = np.ldexp(np.float32(1.25), e)
-        t = ((rng.integers(-126, 126, size=k) + 0.5).astype(np.float64) * np.float64(s2)).astype(np.float32)
-        t[1::2] = np.nextafter(t[1::2], np.float32(np.inf))
-        t[0] = np.float32(127.0) * s2
-        rows.append(t)
-    x = torch.from_numpy(np.stack(rows)).to(dt)
+    x = torch.from_numpy(rowquant_inputs.exponent_range()).to(dt)
     xf = x.float().numpy()
     for mm, name in ((ops.MM_I8, "int8"), (ops.MM_FP8, "fp8")):
         xq, xs, rs, _ = ops.rowquant(x.to(gpu_device), mm, want_rowsum=(mm == ops.MM_I8))

@@ -4,7 +4,9 @@ the standing w8a8 bound, grad_bias, the two variants against each other, what th
 capture and a small training loop.
 
 Shapes: the fixtures' (tests/golden/make_golden_training.py) -- M = 33 / 72 (not multiples of 16), M = 300 (three 128-row statistics
-slabs, two 256-row quantize tiles), C = 48 / 80 / 96 (partial 64-column tiles)."""
+slabs, two 256-row quantize tiles), C = 48 / 80 / 96 (partial 64-column tiles).  At these sizes the statistics loop of colstat_kernel
+runs once per slab and at most three slabs meet; the sizes the kernel was built for -- several passes per slab, 32 slabs, tens of row
+tiles, C = 8, hundreds of column tiles -- and the products against an independent oracle are in tests/test_colquant_exact_gpu.py."""
 import pytest
 import torch
 

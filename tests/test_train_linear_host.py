@@ -87,6 +87,82 @@ def test_colquant_t_argument_validation_without_gpu():
     assert wsb(16384, 3072) < 16384 * 3072 // 8                                                   # partials, not a copy
 
 
+ALL_CQ_SHAPES = {**R.CENSUS_SHAPES, **R.EDGE_SHAPES}
+
+
+@pytest.mark.parametrize("shape", list(ALL_CQ_SHAPES), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_cq_plan_restatement_and_the_regimes_of_the_training_size_shapes(shape):
+    """tests/test_colquant_exact_gpu.py picks its shapes by the regime of csrc/colquant.hip they reach.  The restated plan gives the
+    library's workspace size (2 partials per slab and column), and every shape reaches what the table in train_linear_util says."""
+    from sdnq_amd import _lib
+    r, c = shape
+    ctiles, nslab, slab_rows = R.cq_plan(r, c)
+    assert 2 * nslab * c * 4 == _lib.load().sdnq_hip_colquant_t_workspace_bytes(r, c)
+    assert slab_rows % R.STAT_SLAB_ROWS == 0 and (nslab - 1) * slab_rows < r <= nslab * slab_rows and nslab <= R.MAX_SLABS
+    assert R.regime(r, c) == ALL_CQ_SHAPES[shape]
+
+
+def test_training_size_shapes_cover_what_the_fixtures_leave_out():
+    got = [R.regime(*s) for s in ALL_CQ_SHAPES]
+    assert {1, 2, 3} <= {g["passes"] for g in got}                       # the statistics loop runs once, twice, three times per slab
+    assert max(g["nslab"] for g in got) == R.MAX_SLABS                   # the slab reduction at its maximum ...
+    assert {1, 16} <= {g["want"] for g in got}                           # ... and cut short by many column tiles (want < 32)
+    assert sum(g["last_slab"] == 1 for g in got) >= 2                    # a last slab of one row
+    assert max(g["row_tiles"] for g in got) >= 33 and any(s[0] % 256 == 1 for s in ALL_CQ_SHAPES)   # a last row tile of one row
+    assert any(s[1] == 8 for s in ALL_CQ_SHAPES) and max(g["ctiles"] for g in got) == 512
+    for name in R.train_names():                                         # what the fixtures reach: one pass, three slabs, two row tiles
+        meta = R.load(name)[0]
+        for c in (meta["N"], meta["K"]):
+            g = R.regime(meta["M"], c)
+            assert g["passes"] == 1 and g["nslab"] <= 3 and g["row_tiles"] <= 2 and g["want"] == 32
+
+
+@pytest.mark.parametrize("shape", list(R.CENSUS_SHAPES), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_exact_matrix_is_exact_and_the_oracle_returns_its_codes(shape):
+    """The constructed census input: a value of all three dtypes, every entry non-zero, one +-127 per column at the pinned row -- one in
+    each third of the columns at row 0, at row R - 1 and in a later pass of a slab -- and the C oracle gives back q and 2^e."""
+    r, c = shape
+    pins = R.census_pin_rows(r, c)
+    x, q, e = R.exact_matrix(r, c, torch.Generator().manual_seed(r + c), None, pins)
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(x.to(dt).float(), x)
+    assert q.dtype == torch.int8 and (q != 0).all() and torch.equal(x.double(), q.double() * torch.exp2(e.double()))
+    big = q.abs() == 127
+    assert (big.sum(0) == 1).all() and big[pins, torch.arange(c)].all() and (q.abs()[~big] <= 8).all()
+    assert e.min() >= -3 and e.max() <= 3 and len(set(e.tolist())) > 1
+    _, nslab, slab_rows = R.cq_plan(r, c)
+    cycle = 3 if slab_rows >= 256 else 2
+    assert (pins[0::cycle] == 0).all() and (pins[1::cycle] == r - 1).all() and (r - 1) // slab_rows == nslab - 1
+    if cycle == 3:
+        later = pins[2::3]
+        assert ((later % slab_rows >= 128) & (later < r)).all() and len(set((later // slab_rows).tolist())) >= min(nslab, len(later), 4)
+    assert (x.double().sum(0).abs() < 2.0 ** 24 * torch.exp2(e.double())).all() and torch.equal(x.sum(0).double(), x.double().sum(0))
+    codes, scale = R.oracle_colquant_t(x)
+    assert torch.equal(codes[:, :r], q.t()) and not codes[:, r:].any() and torch.equal(scale.reshape(-1), torch.exp2(e.float()))
+
+
+def test_oracle_column_quantizer_agrees_with_the_restatement_on_the_edge_matrices():
+    """Two independent CPU implementations, bit for bit, on the inputs the GPU tests hold the kernel to the oracle on."""
+    from tests import rowquant_inputs
+    wide = torch.from_numpy(rowquant_inputs.exponent_range()).t()
+    for x in (torch.from_numpy(rowquant_inputs.ties_and_near_ties()).t(), wide, wide.to(torch.bfloat16)):
+        codes, scale = R.oracle_colquant_t(x)
+        q_t, s, _ = R.colquant_t(x.contiguous())
+        assert torch.equal(codes, q_t) and torch.equal(scale.view(torch.int32), s.view(torch.int32))
+
+
+def test_oracle_chain_agrees_with_the_restatement_on_exact_operands():
+    """The chain of the exact-sum GPU test at a small size: the oracle's three products equal the float64 products rounded once."""
+    g = torch.Generator().manual_seed(5)
+    (x, _), (w, _), (dy, _) = R.exact_operand(72, 48, g, -2), R.exact_operand(32, 48, g, -5), R.exact_operand(72, 32, g, -1)
+    bias = torch.randint(-64, 65, (32,), generator=g).float() * 2.0 ** -7
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        y, gi, gw = R.oracle_chain(x.to(dt), w.to(dt), bias.to(dt), dy.to(dt), dt)
+        want = ((x.double() @ w.double().t() + bias.double()), dy.double() @ w.double(), dy.double().t() @ x.double())
+        for got, ref in zip((y, gi, gw), want):
+            assert torch.isfinite(ref.to(dt)).all() and torch.equal(got, ref.to(dt))
+
+
 def test_import_name_drop_in():
     import importlib
 

@@ -58,6 +58,114 @@ def colquant_t(x2d, want_colsum=False):
     return q_t, scale.reshape(c, 1), colsum
 
 
+# ---- the column quantizer at training size (tests/test_colquant_exact_gpu.py) -----------------------------------------------------
+MAX_SLABS = 32
+TAG = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}
+
+
+def cq_plan(r, c):
+    """(ctiles, nslab, slab_rows): cq_plan of csrc/colquant.hip restated -- how the statistics pass cuts R rows into slabs.  It only
+    documents and asserts which regime a test shape reaches; test_train_linear_host.py ties it to the library's workspace size."""
+    ctiles = -(-c // COLUMN_TILE)
+    want = min(-(-512 // ctiles), MAX_SLABS)
+    nslab = min(want, (r + 31) // 32)
+    slab_rows = (-(-r // nslab) + STAT_SLAB_ROWS - 1) // STAT_SLAB_ROWS * STAT_SLAB_ROWS
+    return ctiles, -(-r // slab_rows), slab_rows
+
+
+def row_tiles(r):
+    """Row tiles of colquant_t_kernel at the ld_t ops.colquant_t allocates."""
+    return -(-((r + 15) // 16 * 16) // ROW_TILE)
+
+
+# (R, C) -> the regime it reaches: slabs and 128-row passes per slab of colstat_kernel, rows in the last slab, row tiles of
+# colquant_t_kernel, column tiles, and the slab count the plan asks for before the rows cap it (want < 32: many column tiles)
+CENSUS_SHAPES = {
+    (3969, 8): dict(nslab=32, passes=1, last_slab=1, row_tiles=16, ctiles=1, want=32),        # one column lane of eight works
+    (4097, 72): dict(nslab=17, passes=2, last_slab=1, row_tiles=17, ctiles=2, want=32),       # last row tile holds 1 row; partial column tile
+    (8200, 24): dict(nslab=22, passes=3, last_slab=136, row_tiles=33, ctiles=1, want=32),
+    (4100, 2056): dict(nslab=11, passes=3, last_slab=260, row_tiles=17, ctiles=33, want=16),
+    (260, 32712): dict(nslab=1, passes=3, last_slab=260, row_tiles=2, ctiles=512, want=1),
+}
+EDGE_SHAPES = {
+    (1280, 16): dict(nslab=10, passes=1, last_slab=128, row_tiles=5, ctiles=1, want=32),      # ties and near-ties per column
+    (1536, 208): dict(nslab=12, passes=1, last_slab=128, row_tiles=6, ctiles=4, want=32),     # the exponent range per column
+}
+
+
+def regime(r, c):
+    ctiles, nslab, slab_rows = cq_plan(r, c)
+    return dict(nslab=nslab, passes=slab_rows // STAT_SLAB_ROWS, last_slab=r - (nslab - 1) * slab_rows, row_tiles=row_tiles(r),
+                ctiles=ctiles, want=min(-(-512 // ctiles), MAX_SLABS))
+
+
+def census_pin_rows(r, c):
+    """[C] the row of each column's +-127, cycling over row 0, row R - 1 (alone in the last slab at R = 3969 and 4097) and, where a slab
+    has a second 128-row pass, the first rows of the second or a later pass of some slab (slab_start + 128 p + 0..3)."""
+    _, nslab, slab_rows = cq_plan(r, c)
+    later = [s * slab_rows + STAT_SLAB_ROWS * p for s in range(nslab) for p in range(1, slab_rows // STAT_SLAB_ROWS)
+             if s * slab_rows + STAT_SLAB_ROWS * p + 3 < r]
+    rows = torch.zeros(c, dtype=torch.int64)
+    for col in range(c):
+        kind = col % (3 if later else 2)
+        rows[col] = (0, r - 1, later[col // 3 * 7 % len(later)] + col % 4 if later else 0)[kind]
+    return rows
+
+
+def exact_matrix(r, c, gen, exp, pin_rows):
+    """(x float32 [R][C], q int8 [R][C], e int64 [C]) with x = q * 2^e[c]: 1 <= |q| <= 8 with a random sign -- no zero, so a dropped or
+    doubled row changes every column sum -- except one +-127 per column at pin_rows[c].  e[c] is `exp` (an int, or [C]) or, for None, drawn
+    from -3..3.  127 * 2^e / 127 = 2^e in IEEE arithmetic, so the column quantizer's codes are q and its scales 2^e, and the column sums are
+    integers below 2^24 times 2^e: exact in float32 in every order.  Every x is a bf16 and a float16 value (7 bits, |x| <= 1016)."""
+    q = torch.randint(1, 9, (r, c), generator=gen) * (torch.randint(0, 2, (r, c), generator=gen) * 2 - 1)
+    q[pin_rows, torch.arange(c)] = 127 * (torch.randint(0, 2, (c,), generator=gen) * 2 - 1)
+    e = torch.randint(-3, 4, (c,), generator=gen) if exp is None else torch.as_tensor(exp, dtype=torch.int64).expand(c)
+    return q.float() * torch.exp2(e.float()), q.to(torch.int8), e
+
+
+def exact_operand(r, c, gen, exp):
+    """(x float32 [R][C], q int8) with x = q * 2^exp: |q| <= 8 apart from a +127 in every row (at column i mod C) and a -127 in every
+    column (at row (j + 1) mod R), so that the row scales AND the column scales are exactly 2^exp and the codes are q either way."""
+    q = torch.randint(-8, 9, (r, c), generator=gen)
+    rows, cols = torch.arange(r), torch.arange(c)
+    q[rows, rows % c] = 127
+    assert (((cols + 1) % r) % c != cols).all()  # a -127 never lands on a +127
+    q[(cols + 1) % r, cols] = -127
+    assert (q.abs().amax(0) == 127).all() and (q.abs().amax(1) == 127).all()
+    return q.float() * 2.0 ** exp, q.to(torch.int8)
+
+
+def _oracle():
+    from oracle import oracle
+    return oracle
+
+
+def oracle_colquant_t(x2d):
+    """(codes int8 [C][ld_t], scale float32 [C][1]) of the column quantizer from the C oracle's ROW quantizer on the transposed matrix:
+    an implementation that shares nothing with `quantize` above."""
+    r, c = x2d.shape
+    q, s, _ = _oracle().rowquant(x2d.float().t().contiguous().numpy(), "int8")
+    q_t = torch.zeros(c, (r + 15) // 16 * 16, dtype=torch.int8)
+    q_t[:, :r] = torch.from_numpy(q)
+    return q_t, torch.from_numpy(s).reshape(c, 1)
+
+
+def oracle_chain(x, w, bias, dy, dtype):
+    """(y, grad_input, grad_weight) in `dtype` from the C oracle alone: oracle.rowquant on each operand or its transpose, then
+    oracle.scaled_mm("int8", ...).  x [M][K], w [N][K], dy [M][N]."""
+    O, tag = _oracle(), TAG[dtype]
+
+    def rowq(t):
+        return O.rowquant(t.float().contiguous().numpy(), "int8")[:2]
+
+    def mm(a, b, sa, sb, b_=None):
+        return torch.from_numpy(O.scaled_mm("int8", a, b, sa, sb, b_, tag)).to(dtype)  # values of `dtype` already: the cast is exact
+    (xq, xs), (wq, ws), (gq, gs) = rowq(x), rowq(w), rowq(dy)
+    (wq_t, wsc), (gq_t, gsc), (xq_t, xsc) = rowq(w.t()), rowq(dy.t()), rowq(x.t())
+    y = mm(xq, wq, xs, ws, None if bias is None else bias.float().numpy())
+    return y, mm(gq, wq_t, gs, wsc), mm(gq_t, xq_t, gsc, xsc)  # (reducing over M instead of M': the pad columns are zero codes)
+
+
 def scaled_mm(a, b_phys, sa, sb, bias, dtype):
     acc = (a.double() @ b_phys.double().t()).float()  # integers below 2^24 * 2^7: exact in float64, and in float32 for these K
     t = (acc * sa.reshape(-1, 1).float()).double() * sb.reshape(1, -1).double()
