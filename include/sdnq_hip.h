@@ -904,6 +904,41 @@ int64_t sdnq_hip_lowrank_grad_workspace_bytes(int64_t m, int64_t p, int rank);
 int sdnq_hip_lowrank_grad(const void* a, int64_t lda, const void* b, int dtype, int64_t m, int64_t p, int rank, float scale, int out_t,
                           void* out, int out_dtype, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* ---- trainable low-rank adapters on frozen quantized Conv1d / Conv2d layers ----------------------------------------------------------------
+ * PEFT's conv adapter: lora_A is a conv with the layer's kernel, stride, padding and dilation from C_in to `rank` channels, lora_B a 1 x 1
+ * conv from `rank` to C_out.  With U = im2col(x) [B OH OW][C kh kw] (sdnq_hip_im2col) the down projection is U . down^T and the gradient of
+ * down is g^T . U; these two compute them from x [batch][channels][height][width] (contiguous, SDNQ_BF16 / SDNQ_F16; SDNQ_F32:
+ * SDNQ_ERR_DTYPE) as implicit GEMMs, so that U -- kh kw times the bytes of x -- is never written.  Geometry as sdnq_hip_im2col: OH =
+ * (height + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1, likewise OW; Conv1d passes height = kh = 1 with stride 1, padding 0 and dilation
+ * 1 on that axis.  The up projection, g_t = dY . up and the gradient of up are sdnq_hip_lowrank_add / _down / _grad on NHWC rows.
+ *
+ * sdnq_hip_conv_lowrank_down:
+ *     t[(b, oh, ow)][r] = round_dtype( sum_{c,i,j} f32(x[b][c][oh s_h - p_h + i d_h][ow s_w - p_w + j d_w]) * f32(down[r][(c kh + i) kw + j]) )
+ *   float32 accumulation on v_mfma_f32_16x16x32; a tap outside the image contributes nothing.  down [rank][C kh kw] contiguous (lora_A.weight
+ *   viewed 2-D), t [B OH OW][rank] contiguous, both of `dtype`.  The value of sdnq_hip_lowrank_down(sdnq_hip_im2col(x), down) up to the order
+ *   of the float32 sum (identical wherever that sum is exact).  One launch, no workspace, no atomics, capturable.
+ *
+ * sdnq_hip_conv_lowrank_grad:
+ *     out[r][(c, i, j)] = round_out_dtype( scale * sum_{b,oh,ow} f32(g[(b, oh, ow)][r]) * f32(x[b][c][ih][iw]) )
+ *   g [B OH OW][rank] contiguous of `dtype`, out [rank][C kh kw] contiguous of out_dtype (SdnqFloat).  Deterministic as sdnq_hip_lowrank_grad:
+ *   the output positions are cut into slabs of 256 -- a constant of the source -- each summed in float32 on the matrix cores, and with more
+ *   than one slab a second launch adds the partial sums in ascending order, scales and rounds.  No atomics; the same bits on every call;
+ *   capturable.  workspace: sdnq_hip_conv_lowrank_grad_workspace_bytes(...) bytes (< 0: SdnqStatus; 0 when the positions fit one slab, and
+ *   NULL is then allowed), 16-byte aligned, owned by the caller until the stream has run the call.
+ *
+ * Both, before any launch: SDNQ_ERR_NULL (x, down / g, t / out; a workspace that is needed); SDNQ_ERR_DTYPE; SDNQ_ERR_SHAPE -- rank % 8 != 0
+ * or outside 8 .. 256, C kh kw % 8 != 0, a non-positive extent, stride or dilation, a negative padding, an empty output, an image, a row
+ * of the unfolded matrix or the positions of one image beyond 2^31 - 1 elements, more than 65535 slabs, a workspace that is too small;
+ * SDNQ_ERR_ALIGN: x, down / g, t / out or the workspace not 16-byte aligned. */
+int sdnq_hip_conv_lowrank_down(const void* x, int dtype, int batch, int channels, int height, int width, int kh, int kw, int stride_h,
+                               int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, const void* down, int rank, void* t,
+                               sdnq_stream_t stream);
+int64_t sdnq_hip_conv_lowrank_grad_workspace_bytes(int batch, int channels, int height, int width, int kh, int kw, int stride_h,
+                                                   int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int rank);
+int sdnq_hip_conv_lowrank_grad(const void* x, int dtype, int batch, int channels, int height, int width, int kh, int kw, int stride_h,
+                               int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, const void* g, int rank, float scale, void* out,
+                               int out_dtype, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

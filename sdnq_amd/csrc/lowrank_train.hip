@@ -31,20 +31,11 @@
 //         32-byte rows (rank <= 16): one pair per row, the two blocks of a half are 256 bytes apart: 2-way, left as it is.
 //       The bank arithmetic is worked out by hand from the guide's tables; no counter run has confirmed it.  The global loads of the
 //       next stage are issued before the MFMAs of the current one; otherwise untuned.
-#include "sdnq_dev.h"
+#include "lowrank_dev.h"  // mfma16, lrg_swz, lrg_frag, lowrank_grad_sum_kernel: shared with conv_lowrank.hip
 
 namespace {
 
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s* lds_v4s_ptr;
-
 constexpr int LRG_SLAB = 256;  // rows of M per partial sum of sdnq_hip_lowrank_grad (tests/lora_util.py restates it)
-
-template <bool IS_BF16>
-__device__ __forceinline__ v4f mfma16(v4i a, v4i b, v4f c) {
-    if constexpr (IS_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-}
 
 // ---- y += scale * t . up^T ------------------------------------------------------------------------------------------------------------
 // RT: 16-row tiles per wave (a workgroup owns 64 RT rows): every fragment of up feeds RT MFMAs
@@ -115,26 +106,6 @@ __global__ __launch_bounds__(256) void lowrank_add_kernel(const uint16_t* __rest
 }
 
 // ---- out = scale * a^T . b ------------------------------------------------------------------------------------------------------------
-template <int NRT> __device__ __forceinline__ int lrg_swz(int i) {
-    if constexpr (NRT == 1) return 0;
-    else if constexpr (NRT == 2) return (i >> 3) & 1;
-    else if constexpr (NRT == 4) return ((i >> 1) & 1) | (((i >> 3) & 1) << 1);
-    else return (i & 3) | (((i >> 3) & 1) << 2);
-}
-
-// the fragment of v_mfma_f32_16x16x32 (A or B alike) for 32 rows i0 .. i0 + 31 and 16 columns of a [rows][16 NP columns] LDS image:
-// lane l gets rows i0 + 8 (l / 16) + 0..7 of column l % 16.  Two transposed reads of 4 rows each; lane 4 q + p of a 16-lane group supplies
-// the address of row q, columns 4 p .. 4 p + 3 of the block.
-template <int NP>
-__device__ __forceinline__ v4i lrg_frag(const uint8_t* img, int i0, int cp, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int r0 = i0 + 8 * g + q, r1 = r0 + 4;
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(img + r0 * (NP * 32) + ((cp ^ lrg_swz<NP>(r0)) << 5) + 8 * p));
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_ptr)(img + r1 * (NP * 32) + ((cp ^ lrg_swz<NP>(r1)) << 5) + 8 * p));
-    const v2i l2 = __builtin_bit_cast(v2i, lo), h2 = __builtin_bit_cast(v2i, hi);
-    return (v4i){l2[0], l2[1], h2[0], h2[1]};
-}
-
 // NRT: rank tiles of 16 (rank <= 16 NRT).  grid (column tiles of a, slabs).  `direct`: one slab -- scale, round and store out; otherwise
 // the float32 partial goes to part [slab][P][R].
 template <bool IS_BF16, int NRT>
@@ -210,17 +181,6 @@ __global__ __launch_bounds__(256) void lowrank_grad_kernel(const uint16_t* __res
             }
         }
     }
-}
-
-// out[j][r] (or [r][j]) = round( scale * (((part[0] + part[1]) + part[2]) + ...) ): one thread per element, slabs in ascending order
-__global__ __launch_bounds__(256) void lowrank_grad_sum_kernel(const float* __restrict__ part, int64_t slabs, int64_t P, int R, float scale,
-                                                               int out_t, void* __restrict__ out, int out_dtype) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x, total = P * R;
-    if (o >= total) return;
-    float s = part[o];
-    for (int64_t k = 1; k < slabs; ++k) s += part[k * total + o];
-    const int64_t j = o / R, r = o % R;
-    st_rt(out, out_t ? r * P + j : o, scale * s, out_dtype);
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-"""Trainable low-rank adapters (LoRA) on the frozen quantized Linear layers of an accelerated model, fused on HIP kernels.
+"""Trainable low-rank adapters (LoRA) on the frozen quantized Linear -- and Conv1d / Conv2d -- layers of an accelerated model, fused on HIP kernels.
 
     y = layer(x) + scale * (x . down^T) . up^T          down [rank][K], up [N][rank], scale = alpha / rank
 
@@ -22,10 +22,30 @@ Per call:
 The wrapper handles input gradients itself; ``enable_input_grad`` called afterwards leaves these layers alone (it lists them as running
 a forward that is not its own).  The parameters go to ``sdnq_amd.optim.AdamW`` (``add_lora(...).parameters``).
 
-Not built, each raising or listed with its sentence: adapters on conv and embedding layers and on float32 layers; dropout, per-layer
-ranks, DoRA / rsLoRA; merging the adapter into the stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque
-whole-layer operator: the values of adapter inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper
-calls the base forward, which keeps its plan).
+``add_lora(model, convs=True)`` serves the accelerated quantized Conv1d / Conv2d layers as well (groups == 1, zero padding), in PEFT's form:
+lora_A a conv with the layer's kernel, stride, padding and dilation from C_in to rank channels (``lora_down`` [rank, C_in, *kernel]), lora_B
+a 1 x 1 conv from rank to C_out (``lora_up`` [C_out, rank, 1(, 1)]).  With L = H_out W_out, M = B L and the free 2-D views of the factors:
+
+    forward      y   = base(layer, x)                          the layer's own route, NCHW
+                 t   = ops.conv_lowrank_down(x, down2d)        [M][rank] = im2col(x) . down2d^T without the unfolded matrix
+                 y_b += scale * up2d . t_b^T                    per image, ops.lowrank_add with its operands swapped on y_b [C_out][L]; where 8
+                                                               does not divide L: on an NHWC copy of y, copied back (two more passes of data
+                                                               movement, the same single rounding)
+    backward     dy2d = dY as NHWC rows [M][C_out]             made once, shared with the col2im route of the base gradient
+                 g_t  = ops.lowrank_down(dy2d, up2d^T)         [M][rank]
+                 grad_up    = scale * dy2d^T . t               ops.lowrank_grad
+                 grad_down  = scale * g_t^T . im2col(x)        ops.conv_lowrank_grad, [rank][C_in kprod]
+                 grad_input = QuantizedConvInputGrad's base gradient (training._conv_base_grad, either of its routes)
+                              + scale * conv^T(g_t, down)      ops.im2col_bwd of g_t and ops.lowrank_add in place (one more rounding) where
+                                                               kprod rank <= 256 and the rows are 16-byte pieces, ops.linear_float + add (two
+                                                               more) elsewhere: _conv_adapter_grad_input
+                 grad_bias  = dY.sum over batch and space
+
+Not built, each raising or listed with its sentence: adapters on grouped and 3-D convs, on transposed-conv and embedding layers and on float32
+layers, on convs with string padding or a padding mode other than zeros; dropout, per-layer ranks, DoRA / rsLoRA; merging the adapter into the
+stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque whole-layer operator: the values of adapter
+inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper calls the base forward, which keeps its
+plan); a batched (single-launch) NCHW add of the conv adapter's up projection (one ops.lowrank_add launch per image).
 """
 from __future__ import annotations
 
@@ -148,6 +168,172 @@ class QuantizedLinearLoRA(torch.autograd.Function):
         return None, None, grad_input, grad_down, grad_up, grad_bias
 
 
+# ---- the same on frozen quantized Conv1d / Conv2d layers (add_lora(..., convs=True)) ----------------------------------------------------
+# PEFT's conv adapter: lora_A is a conv with the layer's kernel, stride, padding and dilation from C_in to rank channels, lora_B a 1 x 1
+# conv from rank to C_out.  On the unfolded activation U = im2col(x) [M = B L][K = C_in kprod] (L = H_out W_out) it is the Linear adapter:
+# t = U . down2d^T, y += scale * t . up2d^T -- but the layer's forward never writes U in float (its w8a8 route writes int8 codes), and U
+# is kprod times the bytes of x.  ops.conv_lowrank_down / ops.conv_lowrank_grad (csrc/conv_lowrank.hip) read x itself; on the eleven SDXL
+# conv problems of tools/conv_lora_bench.py (bf16, batch 1, ranks 16 and 64; profiles/conv_lora_bench.jsonl) they take 0.28 - 0.92 and
+# 0.33 - 0.87 of the time of ops.im2col + the Linear adapter's kernel, so no layer takes that composition.
+def _conv_down_grad(x4: torch.Tensor, g_t: torch.Tensor, kernel, stride, padding, dilation, scale: float, out_dtype: torch.dtype) -> torch.Tensor:
+    """grad_down2d [rank][K] = scale * g_t^T . im2col(x); the float32 partial sums in the fourth scratch buffer (_workspace)."""
+    ws = _workspace(x4.device, ops.conv_lowrank_grad_workspace_bytes(x4.shape, kernel, stride, padding, dilation, g_t.shape[1]))
+    return ops.conv_lowrank_grad(x4, g_t, kernel, stride, padding, dilation, scale, out_dtype=out_dtype, workspace=ws)
+
+
+def _conv_check_call(layer, input: torch.Tensor, nd: int) -> torch.dtype:
+    dt = layer.sdnq_dequantizer.result_dtype
+    if not input.is_cuda:
+        raise _lib.SdnqHipError("a quantized conv with an adapter needs its input on a gfx950 device (got a CPU tensor); there is no CPU path")
+    if input.dtype != dt:
+        raise NotImplementedError(f"input of dtype {input.dtype} through an adapter on a conv whose compute dtype is {dt}: the adapter "
+                                  "products run in the layer's dtype")
+    if input.ndim != nd + 2:
+        raise NotImplementedError(f"a quantized conv with an adapter needs a batched input [B, C, *spatial] (got shape {tuple(input.shape)})")
+    return dt
+
+
+def _conv_run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor, geometry):
+    """(y, x4, t): the three steps of the conv forward with gradients off.  down [rank, C_in, *kernel] / up [C_out, rank, 1(, 1)]: the
+    factors in the layer dtype.  y comes from the layer's own route in NCHW; with 8 | L the up projection is added there, per image, by
+    ops.lowrank_add with its operands swapped -- y_b [C_out][L] += scale * up2d . t_b^T: one read, one write and one rounding of y.
+    Otherwise (the rows of y_b are not 16-byte pieces) y is copied to NHWC rows, ops.lowrank_add runs in its usual orientation and the
+    result is copied back: two more passes of pure data movement, the same single rounding.  Either way an exactly zero sum keeps the
+    element's bits (up == 0: the inference call's output)."""
+    kernel, stride, padding, dilation, nd = geometry
+    y = base(layer, input)
+    x4 = input.unsqueeze(2) if nd == 1 else input
+    rank, n = down.shape[0], up.shape[0]
+    if y.numel() == 0:
+        return y, x4, y.new_empty((0, rank))
+    t = ops.conv_lowrank_down(x4, down.reshape(rank, -1), kernel, stride, padding, dilation)[0]
+    up2d = up.reshape(n, rank)
+    b = y.shape[0]
+    l = y.numel() // (b * n)
+    if not y.is_contiguous():
+        y = y.contiguous()
+    if l % 8 == 0 and y.data_ptr() % 16 == 0:
+        y3 = y.view(b, n, l)
+        for i in range(b):
+            ops.lowrank_add(up2d, t[i * l:(i + 1) * l], y3[i], layer.lora_scale)
+        return y, x4, t
+    rows = y.view(b, n, l).permute(0, 2, 1).contiguous().view(b * l, n)
+    ops.lowrank_add(t, up2d, rows, layer.lora_scale)
+    return rows.view(b, l, n).permute(0, 2, 1).contiguous().view(y.shape), x4, t
+
+
+def _conv_adapter_grad_input(route: str, gi: torch.Tensor, g_t: torch.Tensor, down: torch.Tensor, shape4, out_shape, geometry, scale: float):
+    """grad_x [B][C_in][H][W] = (the base gradient `gi` of training._conv_base_grad's `route`) + scale * conv^T(g_t, down), the adapter
+    term from existing kernels: g_t as [B][rank][H_out][W_out] goes through ops.im2col_bwd -- U_g [B H W][kprod rank], columns (kernel
+    position, r), in the third scratch buffer, which the base gradient is done with -- and meets down rearranged to [C_in][kprod rank].
+    Roundings of an element, after the base gradient's own one:
+      kprod rank <= 256, gather route, 8 | C_in     ops.lowrank_add on the NHWC rows, before the permute: ONE more
+      kprod rank <= 256, col2im route, 8 | H W      ops.lowrank_add per image with its operands swapped, on the NCHW result: ONE more
+      elsewhere                                     ops.linear_float rounds the term to the layer dtype, torch's add_ rounds the sum: TWO more"""
+    kernel, stride, padding, dilation, _ = geometry
+    b, cin, h, w = shape4
+    _, ho, wo = out_shape
+    rank, kprod = down.shape[0], kernel[0] * kernel[1]
+    kr = kprod * rank
+    g4 = g_t.view(b, ho, wo, rank).permute(0, 3, 1, 2).contiguous()
+    u = ops.im2col_bwd(g4, (h, w), kernel, stride, padding, dilation,
+                       out=training._scratch_unfolded(g_t.device, g_t.dtype, b * h * w * kr))
+    d = down.reshape(rank, cin, kprod).permute(1, 2, 0).reshape(cin, kr).contiguous()
+    if route == "gather":  # gi: NHWC rows [B H W][C_in]
+        if kr <= 256 and cin % 8 == 0:
+            ops.lowrank_add(u, d, gi, scale)
+        else:
+            gi.add_(ops.linear_float(u, d, None), alpha=scale)
+        return gi.view(b, h, w, cin).permute(0, 3, 1, 2).contiguous()
+    hw = h * w
+    if kr <= 256 and hw % 8 == 0 and gi.is_contiguous() and gi.data_ptr() % 16 == 0:
+        g3 = gi.view(b, cin, hw)
+        for i in range(b):
+            ops.lowrank_add(d, u[i * hw:(i + 1) * hw], g3[i], scale)
+        return gi
+    return gi.add_(ops.linear_float(u, d, None).view(b, h, w, cin).permute(0, 3, 1, 2), alpha=scale)
+
+
+class QuantizedConvLoRA(torch.autograd.Function):
+    """y = layer(input) + scale * B(A(input)) with a graph, for a frozen quantized Conv1d / Conv2d layer (groups == 1, zero padding):
+    gradients for the input, the two factors and the bias; the weight, scale, zero point and SVD factors of the layer are frozen and get
+    none.  Saves the module, the input (as [B, C, H, W]) and t.  Backward, with dy2d the NHWC copy of dY (made once, shared with the
+    col2im route of the base gradient):
+        g_t        = ops.lowrank_down(dy2d, up2d^T)                          [M][rank]
+        grad_up    = scale * dy2d^T . t                                      ops.lowrank_grad
+        grad_down  = scale * g_t^T . im2col(x)                               ops.conv_lowrank_grad
+        grad_input = training._conv_base_grad (QuantizedConvInputGrad's, either route) + scale * conv^T(g_t, down)  (_conv_adapter_grad_input)
+        grad_bias  = dY.sum over batch and space
+    Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, layer, base, input, down, up, bias=None):
+        geometry = training._conv_geometry(layer)
+        dt = _conv_check_call(layer, input, geometry[4])
+        with torch.no_grad():
+            y, x4, t = _conv_run(layer, base, input, down.detach().to(dt), up.detach().to(dt), geometry)
+        ctx.layer, ctx.input_shape, ctx.geometry = layer, input.shape, geometry
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.save_for_backward(x4, t, down, up)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        layer = ctx.layer
+        dq = layer.sdnq_dequantizer
+        x4, t, down, up = ctx.saved_tensors
+        if grad_output.dtype != dq.result_dtype:
+            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized conv whose compute dtype is "
+                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
+        if not grad_output.is_cuda:
+            raise _lib.SdnqHipError("gradients through a quantized conv with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
+        kernel, stride, padding, dilation, nd = ctx.geometry
+        dt, scale = grad_output.dtype, layer.lora_scale
+        _, _, need_x, need_down, need_up, need_bias = ctx.needs_input_grad
+        grad_input = grad_down = grad_up = grad_bias = None
+        if grad_output.numel() == 0 or 0 in ctx.input_shape:
+            if need_x:
+                grad_input = grad_output.new_zeros(ctx.input_shape)
+            grad_down = torch.zeros_like(down) if need_down else None
+            grad_up = torch.zeros_like(up) if need_up else None
+        else:
+            dy4 = (grad_output.unsqueeze(2) if nd == 1 else grad_output).contiguous()
+            b, n, ho, wo = dy4.shape
+            rank = down.shape[0]
+            dy2d = dy4.permute(0, 2, 3, 1).contiguous().view(b * ho * wo, n)
+            g_t = None
+            if need_x or need_down:
+                g_t = ops.lowrank_down(dy2d, up.to(dt).reshape(n, rank).t().contiguous())
+            if need_x:
+                shape4 = tuple(x4.shape)
+                route, gi = training._conv_base_grad(layer, dy4, shape4, kernel, stride, padding, dilation, dy2d)
+                grad_input = _conv_adapter_grad_input(route, gi, g_t, down.to(dt), shape4, (b, ho, wo), ctx.geometry, scale).view(ctx.input_shape)
+            if need_up:
+                grad_up = _factor_grad(dy2d, t, scale, False, up.dtype).view(up.shape)
+            if need_down:
+                grad_down = _conv_down_grad(x4, g_t, kernel, stride, padding, dilation, scale, down.dtype).view(down.shape)
+        if need_bias:
+            grad_bias = grad_output.sum(dim=[0] + list(range(2, grad_output.ndim))).to(ctx.bias_dtype)
+        return None, None, grad_input, grad_down, grad_up, grad_bias
+
+
+def _with_conv_lora(base, previous):
+    grad_on = torch.is_grad_enabled
+
+    def forward(self, input):
+        down, up = _attr(self, "lora_down"), _attr(self, "lora_up")
+        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad):
+            return QuantizedConvLoRA.apply(self, base, input, down, up, _attr(self, "bias"))
+        geometry = training._conv_geometry(self)
+        dt = _conv_check_call(self, input, geometry[4])
+        with torch.no_grad():
+            return _conv_run(self, base, input, down.detach().to(dt), up.detach().to(dt), geometry)[0]
+    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_lora"
+    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
+    return forward
+
+
 def _with_lora(base, previous):
     grad_on = torch.is_grad_enabled
 
@@ -175,15 +361,22 @@ def _refresh_compile_plan(module) -> None:
             module.__dict__["_sdnq_hip_plan"] = None
 
 
-def lora_unsupported_reason(module) -> str | None:
-    """None when `add_lora` serves `module` (an SDNQ layer); otherwise the sentence that says why not."""
+def lora_unsupported_reason(module, convs: bool = False) -> str | None:
+    """None when `add_lora` serves `module` (an SDNQ layer); otherwise the sentence that says why not.  convs: judge Conv1d / Conv2d
+    layers as `add_lora(model, convs=True)` does."""
     from .common import linear_types
     cls = getattr(module.sdnq_dequantizer, "layer_class_name", None)
-    if cls not in linear_types:
+    conv = cls not in linear_types
+    if conv and not convs:
         return f"{cls}: adapters are built for quantized Linear layers (conv, transposed-conv and embedding layers are not)"
+    if conv and cls not in training._CONV_CLASSES:
+        return (f"{cls}: adapters are built for quantized Linear, Conv1d and Conv2d layers (Conv3d, transposed-conv and embedding "
+                "layers are not)")
     if getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None:
         return "the layer carries an adapter already (remove_lora(model) takes it off)"
-    why = training.input_grad_unsupported_reason(module)
+    if conv and int(getattr(module, "groups", 1)) != 1:
+        return f"{cls} with groups = {int(module.groups)}: conv adapters are built for groups == 1 (grouped convs are not)"
+    why = training.input_grad_unsupported_reason(module, convs=conv)
     if why is not None:
         return why
     dt = module.sdnq_dequantizer.result_dtype
@@ -213,7 +406,7 @@ def _selected(targets):
 
 
 def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None, targets=None, dtype: torch.dtype | None = None,
-             seed: int | None = None) -> LoRAResult:
+             seed: int | None = None, convs: bool = False) -> LoRAResult:
     """Put a trainable rank-`rank` adapter on every accelerated quantized Linear of `model` whose qualified name `targets` selects
     (None: all; a list of substrings; or a predicate on the name).
 
@@ -225,11 +418,19 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
     forwards) in bfloat16 or float16.  float32 layers, conv and embedding layers are left alone and listed in ``.skipped`` and in ONE
     ``warnings.warn``.  8 <= rank <= 256, rank % 8 == 0.  Re-pointing a layer's forward afterwards (``accelerate``,
     ``apply_sdnq_options_to_model``) takes the adapter off that layer's forward, eager and compiled alike, as it drops the switch of
-    ``enable_input_grad``: the parameters stay registered until ``remove_lora``; call ``add_lora`` after those, not before."""
+    ``enable_input_grad``: the parameters stay registered until ``remove_lora``; call ``add_lora`` after those, not before.
+
+    ``convs=True`` serves the accelerated quantized Conv1d / Conv2d layers as well (``QuantizedConvLoRA``): those that
+    ``training.input_grad_unsupported_reason(module, convs=True)`` accepts, with ``groups == 1``, in bfloat16 or float16.  Their parameters
+    have PEFT's shapes: ``lora_down`` [rank, C_in, *kernel] (lora_A, a conv with the layer's geometry; kaiming-uniform with bound
+    1 / sqrt(C_in * prod(kernel)), from `seed` in module order with the Linear layers) and ``lora_up`` [C_out, rank, 1(, 1)] (lora_B, a
+    1 x 1 conv; zeros).  Grouped convs, Conv3d, transposed convs, embeddings, float32 layers, string padding and padding modes other than
+    zeros are listed in ``.skipped``, each with its sentence.  The default leaves every conv layer alone, as before."""
     if rank % 8 or not 8 <= rank <= 256:
         raise ValueError(f"add_lora: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank}): the adapter kernels move 16-byte rank chunks")
     if dtype is not None and dtype not in (torch.float32, *_DTYPES):
         raise ValueError(f"add_lora: dtype must be None (the layer's), torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
+    from .common import linear_types
     pick = _selected(targets)
     gen = None if seed is None else torch.Generator().manual_seed(int(seed))
     scale = float(alpha if alpha else rank) / rank
@@ -238,23 +439,30 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
         if getattr(module, "sdnq_dequantizer", None) is None or not pick(name):
             continue
         try:
-            why = lora_unsupported_reason(module)
+            why = lora_unsupported_reason(module, convs=convs)
         except Exception as e:  # noqa: BLE001  a foreign record the predicate cannot read: leave the layer alone
             why = f"{type(e).__name__} while reading the layer's record: {e}"
         if why is not None:
             skipped.append((name or type(module).__name__, why))
             continue
         dq = module.sdnq_dequantizer
-        n, k = int(dq.out_features), int(dq.in_features)
+        conv = getattr(dq, "layer_class_name", None) not in linear_types
+        if conv:  # PEFT's shapes: lora_A.weight [rank, C_in, *kernel], lora_B.weight [C_out, rank, 1(, 1)]
+            shape = tuple(int(d) for d in dq.original_shape)
+            n, k = shape[0], math.prod(shape[1:])
+            down_shape, up_shape = (rank, *shape[1:]), (n, rank) + (1,) * (len(shape) - 2)
+        else:
+            n, k = int(dq.out_features), int(dq.in_features)
+            down_shape, up_shape = (rank, k), (n, rank)
         pdt = dq.result_dtype if dtype is None else dtype
         dev = module.weight.device
-        bound = 1.0 / math.sqrt(k)  # kaiming_uniform_(a = sqrt(5)) on fan_in = K: sqrt(6 / ((1 + 5) K))
-        down = torch.empty((rank, k), dtype=torch.float32).uniform_(-bound, bound, generator=gen)
+        bound = 1.0 / math.sqrt(k)  # kaiming_uniform_(a = sqrt(5)) on fan_in = K (C_in * prod(kernel)): sqrt(6 / ((1 + 5) K))
+        down = torch.empty(down_shape, dtype=torch.float32).uniform_(-bound, bound, generator=gen)
         module.lora_down = torch.nn.Parameter(down.to(device=dev, dtype=pdt))
-        module.lora_up = torch.nn.Parameter(torch.zeros((n, rank), device=dev, dtype=pdt))
+        module.lora_up = torch.nn.Parameter(torch.zeros(up_shape, device=dev, dtype=pdt))
         module.lora_scale = scale
         fwd = module.forward_func
-        module.forward_func = _with_lora(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
+        module.forward_func = (_with_conv_lora if conv else _with_lora)(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
         _refresh_compile_plan(module)
         params += [module.lora_down, module.lora_up]
         added += 1
@@ -295,7 +503,7 @@ _PEFT_PREFIX = "base_model.model."
 
 def lora_state_dict(model: torch.nn.Module) -> dict:
     """The adapters under PEFT's key names: ``<module>.lora_A.weight`` [rank, K] (lora_down) and ``<module>.lora_B.weight`` [N, rank]
-    (lora_up), detached.  alpha is not a tensor: PEFT keeps it in its config, here it is the `alpha` of `add_lora`."""
+    (lora_up) -- on a conv layer [rank, C_in, *kernel] and [C_out, rank, 1(, 1)] -- detached.  alpha is not a tensor: PEFT keeps it in its config, here it is the `alpha` of `add_lora`."""
     sd = {}
     for name, module in _lora_modules(model):
         sd[f"{name}.lora_A.weight"] = module.lora_down.detach()

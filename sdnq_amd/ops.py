@@ -1105,6 +1105,91 @@ def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bo
     return out
 
 
+def _conv_lowrank_check(what: str, x: torch.Tensor, other: torch.Tensor, kernel, stride, padding, dilation):
+    """The checks the two conv adapter entry points share -- x [B, C, H, W] and a 2-D operand with `rank` rows / columns of ONE 16-bit dtype,
+    8 | C kh kw -- and their integer arguments: (geometry tuple of 12 ints, (B, H_out, W_out), K)."""
+    if x.ndim != 4 or other.ndim != 2:
+        raise _lib.SdnqHipError(f"{what}: x must be [B, C, H, W] and the factor 2-D (got {tuple(x.shape)}, {tuple(other.shape)})")
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise _lib.SdnqHipError(f"{what}: built for bfloat16 / float16 operands (got {x.dtype})")
+    if other.dtype != x.dtype:
+        raise _lib.SdnqHipError(f"{what}: the factor must have the dtype of x (got {other.dtype}, {x.dtype})")
+    b, c, h, w = x.shape
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel, stride, padding, dilation
+    ho = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    wo = (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if b <= 0 or c <= 0 or ho <= 0 or wo <= 0:
+        raise _lib.SdnqHipError(f"{what}: the convolution output would be empty (x {tuple(x.shape)}, output {ho} x {wo})")
+    k = c * kh * kw
+    if k % 8:
+        raise _lib.SdnqHipError(f"{what}: C * kh * kw % 8 == 0 (got {k}): the factor's rows move in 16-byte pieces")
+    return (b, c, h, w, kh, kw, sh, sw, ph, pw, dh, dw), (b, ho, wo), k
+
+
+def conv_lowrank_down(x: torch.Tensor, down: torch.Tensor, kernel, stride, padding, dilation) -> tuple[torch.Tensor, tuple]:
+    """sdnq_hip_conv_lowrank_down: t [B * H_out * W_out, R] = round(im2col(x) @ down [R, C * kh * kw]^T) for x [B, C, H, W] without the
+    unfolded matrix: the down projection of a conv adapter (lora_A.weight viewed 2-D), float32 sums on the matrix cores, one launch.
+    bfloat16 / float16.  The value of lowrank_down(im2col(x), down) up to the order of the float32 sum.  Returns (t, (B, H_out, W_out))."""
+    geo, out_shape, k = _conv_lowrank_check("conv_lowrank_down", x, down, kernel, stride, padding, dilation)
+    r = down.shape[0]
+    if r % 8 or not 8 <= r <= 256:
+        raise _lib.SdnqHipError(f"conv_lowrank_down: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {r})")
+    if down.shape[1] != k or not down.is_contiguous():
+        raise _lib.SdnqHipError(f"conv_lowrank_down: down must be contiguous [R, C * kh * kw = {k}] (got {tuple(down.shape)}, strides {down.stride()})")
+    _require_cuda(x, down)
+    x = x if x.is_contiguous() else x.contiguous()
+    t = torch.empty((out_shape[0] * out_shape[1] * out_shape[2], r), device=x.device, dtype=x.dtype)
+    check(_lib.load().sdnq_hip_conv_lowrank_down(x.data_ptr(), float_code(x.dtype), *geo, down.data_ptr(), r, t.data_ptr(), _stream(x)),
+          "conv_lowrank_down")
+    return t, out_shape
+
+
+def conv_lowrank_grad_workspace_bytes(x_shape, kernel, stride, padding, dilation, rank: int) -> int:
+    """sdnq_hip_conv_lowrank_grad_workspace_bytes: 0 while the B * H_out * W_out positions fit one slab of the deterministic reduction."""
+    b, c, h, w = (int(d) for d in x_shape)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel, stride, padding, dilation
+    nbytes = _lib.load().sdnq_hip_conv_lowrank_grad_workspace_bytes(b, c, h, w, kh, kw, sh, sw, ph, pw, dh, dw, int(rank))
+    if nbytes < 0:
+        check(int(nbytes), "conv_lowrank_grad_workspace_bytes")
+    return int(nbytes)
+
+
+def conv_lowrank_grad(x: torch.Tensor, g: torch.Tensor, kernel, stride, padding, dilation, scale: float = 1.0,
+                      out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_conv_lowrank_grad: round(scale * g [B * H_out * W_out, R]^T @ im2col(x)) -> [R, C * kh * kw] of `out_dtype` (default: the
+    operands') for x [B, C, H, W] without the unfolded matrix: the gradient of a conv adapter's down factor.  float32 sums over slabs of
+    positions added in a fixed order: the same bits on every call, no atomics.  workspace: as ops.lowrank_grad's (a uint8 tensor of
+    conv_lowrank_grad_workspace_bytes(...) bytes, or None for this module's per-(device, stream) buffer)."""
+    geo, out_shape, k = _conv_lowrank_check("conv_lowrank_grad", x, g, kernel, stride, padding, dilation)
+    m, r = g.shape
+    if r % 8 or not 8 <= r <= 256:
+        raise _lib.SdnqHipError(f"conv_lowrank_grad: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {r})")
+    if m != out_shape[0] * out_shape[1] * out_shape[2] or not g.is_contiguous():
+        raise _lib.SdnqHipError(f"conv_lowrank_grad: g must be contiguous [B * H_out * W_out = {out_shape[0] * out_shape[1] * out_shape[2]}, R] "
+                                f"(got {tuple(g.shape)}, strides {g.stride()})")
+    _require_cuda(x, g, workspace)
+    x = x if x.is_contiguous() else x.contiguous()
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    out = torch.empty((r, k), device=x.device, dtype=out_dtype)
+    need = conv_lowrank_grad_workspace_bytes(x.shape, kernel, stride, padding, dilation, r)
+    if need and workspace is None:
+        have = _workspaces.get((x.device.index, _stream(x)))
+        if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
+            raise _lib.SdnqHipError("conv_lowrank_grad: the module's workspace would have to grow inside a graph capture; pass workspace= or "
+                                    "run one eager call on this stream first")
+        workspace = _workspace(x.device, _stream(x), need + 16)
+    if need and (not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need):
+        raise _lib.SdnqHipError(f"conv_lowrank_grad: workspace must be a uint8 device tensor of at least {need} bytes")
+    wp = 0
+    if need:
+        wp = (workspace.data_ptr() + 15) & ~15
+        if wp + need > workspace.data_ptr() + workspace.numel():
+            raise _lib.SdnqHipError(f"conv_lowrank_grad: workspace must hold {need} bytes behind its first 16-byte boundary")
+    check(_lib.load().sdnq_hip_conv_lowrank_grad(x.data_ptr(), float_code(x.dtype), *geo, g.data_ptr(), r, float(scale), out.data_ptr(),
+                                                 float_code(out_dtype), wp or None, need, _stream(x)), "conv_lowrank_grad")
+    return out
+
+
 _workspaces: dict = {}
 
 

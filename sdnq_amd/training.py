@@ -442,11 +442,11 @@ def _conv_grad_input(layer, dy4: torch.Tensor, in_hw, kernel, stride, padding, d
     return grad2d
 
 
-def _conv_grad_input_col2im(layer, dy4: torch.Tensor, in_shape, kernel, stride, padding, dilation) -> torch.Tensor:
+def _conv_grad_input_col2im(layer, dy4: torch.Tensor, in_shape, kernel, stride, padding, dilation, dy2d=None) -> torch.Tensor:
     """grad_x [B][C_in][H][W] of an ungrouped conv layer by the kernels of the transposed convolution: cols[(b, oh, ow)][(ci, kpos)] =
     dY (NHWC) . W in float32 -- the weight operand is ops.weight_t's [C_in kprod][C_out] as it stands -- then every input pixel gathers the
     taps that reach it (ops.col2im): float32 sums, one rounding.  `cols` lives in the third scratch buffer, whole images per slab (one
-    image at least, whatever the bound says)."""
+    image at least, whatever the bound says).  dy2d: the NHWC copy of dY [B L_out][C_out] where the caller has made it already."""
     from . import linear
     dq = layer.sdnq_dequantizer
     qw = linear._state(layer).qw
@@ -458,7 +458,8 @@ def _conv_grad_input_col2im(layer, dy4: torch.Tensor, in_shape, kernel, stride, 
     per_image = ho * wo * qw.k
     imgs = _slab_rows(b, per_image * 4)
     cols = _scratch_unfolded(dev, torch.float32, imgs * per_image)
-    dy2d = dy4.permute(0, 2, 3, 1).contiguous().view(b * ho * wo, cout)
+    if dy2d is None:
+        dy2d = dy4.permute(0, 2, 3, 1).contiguous().view(b * ho * wo, cout)
     pieces = []
     for b0 in range(0, b, imgs):
         n = min(imgs, b - b0)
@@ -466,6 +467,16 @@ def _conv_grad_input_col2im(layer, dy4: torch.Tensor, in_shape, kernel, stride, 
         ops.linear_float_f32_into(dy2d[b0 * ho * wo:(b0 + n) * ho * wo], wt, c, 0)
         pieces.append(ops.col2im(c, None, dt, n, cin, (ho, wo), (h, w), kernel, stride, padding, dilation))
     return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=0)
+
+
+def _conv_base_grad(layer, dy4: torch.Tensor, shape4, kernel, stride, padding, dilation, dy2d=None):
+    """grad_x of a frozen conv layer on the route _takes_col2im_route picks, as QuantizedConvInputGrad and the conv adapter of
+    sdnq_amd.lora both compute it: ("col2im", grad_x [B][C_in][H][W]) or ("gather", grad2d [B H W][C_in] -- NHWC rows, which the caller
+    permutes to NCHW).  dy4 [B][C_out][H_out][W_out], shape4 = (B, C_in, H, W); dy2d: see _conv_grad_input_col2im."""
+    in_hw = (shape4[2], shape4[3])
+    if _takes_col2im_route(int(layer.groups), kernel[0] * kernel[1], stride, shape4[0] * in_hw[0] * in_hw[1]):
+        return "col2im", _conv_grad_input_col2im(layer, dy4, shape4, kernel, stride, padding, dilation, dy2d)
+    return "gather", _conv_grad_input(layer, dy4, in_hw, kernel, stride, padding, dilation)
 
 
 class QuantizedConvInputGrad(torch.autograd.Function):
@@ -506,11 +517,9 @@ class QuantizedConvInputGrad(torch.autograd.Function):
             else:
                 dy4 = grad_output.unsqueeze(2) if nd == 1 else grad_output
                 in_hw = (1, shape[2]) if nd == 1 else (shape[2], shape[3])
-                if _takes_col2im_route(int(layer.groups), kernel[0] * kernel[1], stride, shape[0] * in_hw[0] * in_hw[1]):
-                    grad_input = _conv_grad_input_col2im(layer, dy4, (shape[0], shape[1], *in_hw), kernel, stride, padding, dilation)
-                else:
-                    grad2d = _conv_grad_input(layer, dy4, in_hw, kernel, stride, padding, dilation)
-                    grad_input = grad2d.view(shape[0], *in_hw, shape[1]).permute(0, 3, 1, 2).contiguous()
+                route, grad_input = _conv_base_grad(layer, dy4, (shape[0], shape[1], *in_hw), kernel, stride, padding, dilation)
+                if route == "gather":
+                    grad_input = grad_input.view(shape[0], *in_hw, shape[1]).permute(0, 3, 1, 2).contiguous()
                 grad_input = grad_input.view(shape)  # (Conv1d: the H = 1 axis goes)
         if ctx.needs_input_grad[2]:
             grad_bias = grad_output.sum(dim=[0] + list(range(2, grad_output.ndim))).to(ctx.bias_dtype)
