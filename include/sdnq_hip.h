@@ -904,6 +904,38 @@ int64_t sdnq_hip_lowrank_grad_workspace_bytes(int64_t m, int64_t p, int rank);
 int sdnq_hip_lowrank_grad(const void* a, int64_t lda, const void* b, int dtype, int64_t m, int64_t p, int rank, float scale, int out_t,
                           void* out, int out_dtype, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* ---- LoRA dropout on the Linear adapters: the mask recomputed inside the three adapter kernels ------------------------------------------
+ * PEFT's y = layer(x) + scale * B(A(dropout(x))): replaces `F.dropout(x)` in front of the adapter branch (a full pass over x [M][K] and a
+ * second [M][K] tensor saved for the backward).  No mask and no dropped copy of x exists in memory: every kernel recomputes the mask of
+ * the 16-byte chunk it moves from (seed, offset, logical element index).
+ *
+ * The mask of a matrix v [rows][cols] (cols % 8 == 0): element (i, j) has the logical index e = i * cols + j -- never the row stride --
+ * and gets 16 random bits r16(e) of Philox4x32-10 with
+ *     key     = (seed low, seed high)
+ *     counter = (e8 low, e8 high | 5 << 28, offset low, offset high),  e8 = e / 8        (stream 5; the AdamW step uses 0 .. 4)
+ *     r16(e)  = half (e & 1) of output word ((e % 8) >> 1)                               (low half first)
+ *   the convention of sdnq_hip_adamw_step's stochastic stores.  The element is KEPT iff r16(e) >= threshold, 1 <= threshold <= 65535: it is
+ *   dropped with probability threshold / 65536.  Survivors are NOT rescaled in the operand; the caller folds 1 / (1 - p) = 65536 / (65536 -
+ *   threshold) into the float32 `scale` these kernels (and their plain siblings) take.
+ *
+ * sdnq_hip_lowrank_down_dropout: t [m][rank] = round_dtype((mask . x) . down^T), the matrix-core kernel of sdnq_hip_lowrank_down with the
+ *   mask of x [m][k] applied to the fragments in registers: the bits of sdnq_hip_lowrank_down on a pre-masked x.  dtype SDNQ_BF16 / SDNQ_F16
+ *   for x, down and t (else SDNQ_ERR_DTYPE: there is no float32 path); k % 16 == 0, ldx >= k, m, rank > 0 (else SDNQ_ERR_SHAPE: there is no
+ *   few-row fallback); x, down and ldx * 2 bytes 16-byte aligned (SDNQ_ERR_ALIGN).
+ * sdnq_hip_lowrank_grad_dropout: out = round(scale * (mask . a)^T . b), sdnq_hip_lowrank_grad with the mask of a [m][p] applied as a is
+ *   staged: the bits of sdnq_hip_lowrank_grad on a pre-masked a; the same slabs, workspace and statuses.
+ * sdnq_hip_lowrank_add_dropout: y[i][j] = round_dtype(fmaf(scale, sum_r t[i][r] up[j][r], y[i][j])) where the mask of y [m][n] keeps (i, j);
+ *   a dropped element is stored back as it was read (a -0.0 included), as an exactly zero sum is.  Otherwise sdnq_hip_lowrank_add: the
+ *   term scale * mask . (g_t . down) of grad_input.
+ * All three: threshold outside 1 .. 65535 is SDNQ_ERR_SHAPE; every other status as the plain sibling's, validated before any launch. */
+int sdnq_hip_lowrank_down_dropout(const void* x, int dtype, int64_t m, int64_t k, int64_t ldx, const void* down, int rank, void* t,
+                                  int threshold, uint64_t seed, uint64_t offset, sdnq_stream_t stream);
+int sdnq_hip_lowrank_add_dropout(const void* t, const void* up, int dtype, int rank, float scale, void* y, int64_t m, int64_t n, int64_t ldy,
+                                 int threshold, uint64_t seed, uint64_t offset, sdnq_stream_t stream);
+int sdnq_hip_lowrank_grad_dropout(const void* a, int64_t lda, const void* b, int dtype, int64_t m, int64_t p, int rank, float scale,
+                                  int out_t, void* out, int out_dtype, void* workspace, int64_t workspace_bytes, int threshold,
+                                  uint64_t seed, uint64_t offset, sdnq_stream_t stream);
+
 /* ---- trainable low-rank adapters on frozen quantized Conv1d / Conv2d layers ----------------------------------------------------------------
  * PEFT's conv adapter: lora_A is a conv with the layer's kernel, stride, padding and dilation from C_in to `rank` channels, lora_B a 1 x 1
  * conv from `rank` to C_out.  With U = im2col(x) [B OH OW][C kh kw] (sdnq_hip_im2col) the down projection is U . down^T and the gradient of

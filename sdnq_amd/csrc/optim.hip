@@ -49,7 +49,7 @@
 // arguments the compiler appends to a kernel that uses them (these do not) = 3840.  The shared scalars take 48, a tensor 56 + 4 (dense: four pointers) or 88 + 4 (uint8 state:
 // eight), which gives (3840 - 48) / 60 = 63 and (3840 - 48) / 92 = 41 tensors per launch.  The entry points cut a longer list into
 // launches.
-#include "sdnq_dev.h"
+#include "philox_dev.h"  // aw_philox: shared with the dropout of the adapter kernels
 
 namespace {
 
@@ -84,16 +84,6 @@ __device__ __forceinline__ float aw_lerp(float a, float b, float w) {
     return (w < 0.5f) ? fmaf(w, diff, a) : fmaf(w - 1.0f, diff, b);
 }
 
-__device__ __forceinline__ uint4 aw_philox(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const u32 hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const u32 hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
 __device__ __forceinline__ uint4 aw_random(const AdamWScalars& a, int64_t e8, u32 stream) {
     return aw_philox((u32)e8, (u32)((uint64_t)e8 >> 32) | (stream << 28), a.off_lo, a.off_hi, a.seed_lo, a.seed_hi);
 }

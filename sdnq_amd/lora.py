@@ -19,6 +19,27 @@ Per call:
                  grad_down  = scale * g_t^T . x                ops.lowrank_grad(out_t=True), [rank][K]
                  grad_bias  = dY.sum(0)                        when the bias requires grad
 
+``add_lora(model, dropout=p)`` is PEFT's ``lora_dropout``: y = layer(x) + scale * B(A(dropout(x))), on the adapter branch only, in training
+mode only (``module.training`` and p > 0, with or without gradients, as nn.Dropout).  No mask and no dropped copy of x is ever written: the
+mask is a pure function of (seed, offset, element index) -- Philox4x32-10 in the counter convention of the AdamW step, stream 5
+(include/sdnq_hip.h) -- and the three kernels that need it recompute it for the 16-byte chunk they move:
+
+    forward      t   = ops.lowrank_down_dropout(x, down)       the mask on the fragments of x in registers
+                 y  += scale_d * t . up^T                       ops.lowrank_add, unchanged
+    backward     g_t = ops.lowrank_down(dY, up^T)              unchanged
+                 grad_up    = scale_d * dY^T . t                ops.lowrank_grad, unchanged
+                 grad_down  = scale_d * g_t^T . (mask * x)      ops.lowrank_grad_dropout: the mask on x as it is staged
+                 grad_input = dY . W + scale_d * mask * (g_t . down)   ops.lowrank_add_dropout: the mask in the epilogue
+
+An element is dropped iff its 16 random bits are below T = min(65535, max(1, round(p * 65536))) (``dropout_threshold``): the effective
+probability is T / 65536, within 2^-17 of p (at least 2^-16).  The survivors are not rescaled in the operand; 1 / (1 - p) goes into the
+float32 scale the kernels take anyway, scale_d = float32(scale * 65536 / (65536 - T)) (``dropout_scale``).  Each forward call reads
+(initial_seed, offset) from torch's device generator and advances the offset by 4, as ``sdnq_amd.optim`` does for its stochastic stores;
+the backward keeps (seed, offset, T) as three Python ints beside what it saves anyway.  ``torch.cuda.manual_seed`` reproduces a run, and
+``torch.utils.checkpoint`` (which restores the generator state for its recomputation) replays the same mask.  While a stream is being
+captured an active dropout raises (the offset is drawn on the host: a replay would repeat one mask); ``dropout=0`` and ``eval()`` capture
+as before.  ``eval()`` and ``dropout=0`` run exactly the calls above without the mask: the same entry points and bits as before.
+
 The wrapper handles input gradients itself; ``enable_input_grad`` called afterwards leaves these layers alone (it lists them as running
 a forward that is not its own).  The parameters go to ``sdnq_amd.optim.AdamW`` (``add_lora(...).parameters``).
 
@@ -42,13 +63,14 @@ a 1 x 1 conv from rank to C_out (``lora_up`` [C_out, rank, 1(, 1)]).  With L = H
                  grad_bias  = dY.sum over batch and space
 
 Not built, each raising or listed with its sentence: adapters on grouped and 3-D convs, on transposed-conv and embedding layers and on float32
-layers, on convs with string padding or a padding mode other than zeros; dropout, per-layer ranks, DoRA / rsLoRA; merging the adapter into the
+layers, on convs with string padding or a padding mode other than zeros; dropout on conv adapters; per-layer ranks, DoRA / rsLoRA; merging the adapter into the
 stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque whole-layer operator: the values of adapter
 inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper calls the base forward, which keeps its
 plan); a batched (single-launch) NCHW add of the conv adapter's up projection (one ops.lowrank_add launch per image).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -75,9 +97,12 @@ def _workspace(dev: torch.device, nbytes: int):
     return bufs[3]
 
 
-def _factor_grad(a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype: torch.dtype) -> torch.Tensor:
+def _factor_grad(a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype: torch.dtype, drop=None) -> torch.Tensor:
+    """scale * a^T . b; drop = (seed, offset, T): a under its dropout mask."""
     ws = _workspace(a.device, ops.lowrank_grad_workspace_bytes(a.shape[0], a.shape[1], b.shape[1])) if a.shape[0] else None
-    return ops.lowrank_grad(a, b, scale, out_t=out_t, out_dtype=out_dtype, workspace=ws)
+    if drop is None:
+        return ops.lowrank_grad(a, b, scale, out_t=out_t, out_dtype=out_dtype, workspace=ws)
+    return ops.lowrank_grad_dropout(a, b, scale, drop[2], drop[0], drop[1], out_t=out_t, out_dtype=out_dtype, workspace=ws)
 
 
 def _check_call(layer, input: torch.Tensor) -> torch.dtype:
@@ -90,14 +115,45 @@ def _check_call(layer, input: torch.Tensor) -> torch.dtype:
     return dt
 
 
-def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor):
-    """(y, x2d, t): the three steps of the forward with gradients off.  down / up: the factors in the layer dtype."""
+def dropout_threshold(p: float) -> int:
+    """T of ``add_lora(dropout=p)``: an element is dropped iff its 16 random bits are < T = min(65535, max(1, round(p * 65536))) -- the
+    effective probability is T / 65536."""
+    return min(65535, max(1, round(float(p) * 65536)))
+
+
+def dropout_scale(scale: float, threshold: int) -> float:
+    """scale_d = float32(scale * 65536 / (65536 - T)), the quotient in double: the adapter's scale with the 1 / (1 - p) of the survivors."""
+    return ctypes.c_float(float(scale) * 65536.0 / (65536 - int(threshold))).value
+
+
+def _draw_dropout(layer, dev: torch.device):
+    """None when dropout is off for this call; otherwise (seed, offset, T) -- (initial_seed, offset) of torch's device generator, whose
+    offset advances by 4 (torch keeps it a multiple of 4), as SDNQOptimizer.step draws for its stochastic stores."""
+    p = float(getattr(layer, "lora_dropout", 0.0))
+    if p <= 0.0 or not layer.training:
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("adapter dropout draws its (seed, offset) on the host and cannot be captured in a graph: a replay would repeat "
+                           "one mask; capture with model.eval() or add_lora(dropout=0)")
+    gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
+    seed, offset = int(gen.initial_seed()), int(gen.get_offset())
+    gen.set_offset(offset + 4)
+    return seed, offset, dropout_threshold(p)
+
+
+def _scale(layer, drop) -> float:
+    return layer.lora_scale if drop is None else dropout_scale(layer.lora_scale, drop[2])
+
+
+def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor, drop=None):
+    """(y, x2d, t): the three steps of the forward with gradients off.  down / up: the factors in the layer dtype.  drop: None or the
+    (seed, offset, T) of _draw_dropout -- then t comes from the masked x and the scale carries 1 / (1 - p)."""
     y = base(layer, input)
     x2d = training._rows(input)
     n = up.shape[0]
     if x2d.shape[0] == 0:
         return y, x2d, x2d.new_empty((0, down.shape[0]))
-    t = ops.lowrank_down(x2d, down)
+    t = ops.lowrank_down(x2d, down) if drop is None else ops.lowrank_down_dropout(x2d, down, drop[2], drop[0], drop[1])
     try:
         y2d = y.view(-1, n)
     except RuntimeError:
@@ -108,20 +164,22 @@ def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor)
     if y2d.stride(1) != 1 or ld < n or y2d.data_ptr() % 16 or (ld * y2d.element_size()) % 16:
         y = y.clone(memory_format=torch.contiguous_format)
         y2d = y.view(-1, n)
-    ops.lowrank_add(t, up, y2d, layer.lora_scale)
+    ops.lowrank_add(t, up, y2d, _scale(layer, drop))
     return y, x2d, t
 
 
 class QuantizedLinearLoRA(torch.autograd.Function):
     """y = layer(input) + scale * (input . down^T) . up^T with a graph: gradients for the input, the two factors and the bias; the
-    weight, scale, zero point and SVD factors of the layer are frozen and get none.  Saves the module, the flattened input and t.  Not
-    differentiable twice."""
+    weight, scale, zero point and SVD factors of the layer are frozen and get none.  Saves the module, the flattened input and t -- and,
+    with dropout active, the three ints (seed, offset, T) from which the backward's kernels recompute the mask.  Not differentiable
+    twice."""
 
     @staticmethod
     def forward(ctx, layer, base, input, down, up, bias=None):
         dt = _check_call(layer, input)
+        ctx.drop = drop = _draw_dropout(layer, input.device)
         with torch.no_grad():
-            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt))
+            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), drop)
         ctx.layer, ctx.input_shape = layer, input.shape
         ctx.bias_dtype = None if bias is None else bias.dtype
         ctx.save_for_backward(x2d, t, down, up)
@@ -140,7 +198,8 @@ class QuantizedLinearLoRA(torch.autograd.Function):
         if not grad_output.is_cuda:
             raise _lib.SdnqHipError("gradients through a quantized Linear with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
         g2d = training._rows(grad_output)
-        dt, scale = g2d.dtype, layer.lora_scale
+        drop = ctx.drop
+        dt, scale = g2d.dtype, _scale(layer, drop)
         _, _, need_x, need_down, need_up, need_bias = ctx.needs_input_grad
         grad_input = grad_down = grad_up = grad_bias = None
         if g2d.shape[0] == 0:
@@ -157,12 +216,15 @@ class QuantizedLinearLoRA(torch.autograd.Function):
                 had = dq.hadamard_group_size if dq.use_hadamard else 0
                 scratch = training._scratch(g2d.device, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)
                 gi2d = ops.linear_float(g2d, ops.weight_t(qw, dt, had, scratch), None)
-                ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
+                if drop is None:
+                    ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
+                else:
+                    ops.lowrank_add_dropout(g_t, down.to(dt).t().contiguous(), gi2d, scale, drop[2], drop[0], drop[1])
                 grad_input = gi2d.view(ctx.input_shape)
             if need_up:
                 grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
             if need_down:
-                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype)
+                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype, drop)
         if need_bias:
             grad_bias = g2d.sum(0).to(ctx.bias_dtype)
         return None, None, grad_input, grad_down, grad_up, grad_bias
@@ -343,7 +405,7 @@ def _with_lora(base, previous):
             return QuantizedLinearLoRA.apply(self, base, input, down, up, _attr(self, "bias"))
         dt = _check_call(self, input)
         with torch.no_grad():
-            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt))[0]
+            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(self, input.device))[0]
     forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_lora"
     forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
     return forward
@@ -406,7 +468,7 @@ def _selected(targets):
 
 
 def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None, targets=None, dtype: torch.dtype | None = None,
-             seed: int | None = None, convs: bool = False) -> LoRAResult:
+             seed: int | None = None, convs: bool = False, dropout: float = 0.0) -> LoRAResult:
     """Put a trainable rank-`rank` adapter on every accelerated quantized Linear of `model` whose qualified name `targets` selects
     (None: all; a list of substrings; or a predicate on the name).
 
@@ -425,7 +487,19 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
     have PEFT's shapes: ``lora_down`` [rank, C_in, *kernel] (lora_A, a conv with the layer's geometry; kaiming-uniform with bound
     1 / sqrt(C_in * prod(kernel)), from `seed` in module order with the Linear layers) and ``lora_up`` [C_out, rank, 1(, 1)] (lora_B, a
     1 x 1 conv; zeros).  Grouped convs, Conv3d, transposed convs, embeddings, float32 layers, string padding and padding modes other than
-    zeros are listed in ``.skipped``, each with its sentence.  The default leaves every conv layer alone, as before."""
+    zeros are listed in ``.skipped``, each with its sentence.  The default leaves every conv layer alone, as before.
+
+    ``dropout`` (0 <= dropout < 1, PEFT's ``lora_dropout``; stored as ``module.lora_dropout``) drops elements of the adapter branch's
+    input in training mode, fused into the adapter kernels (module docstring): the effective probability is
+    ``dropout_threshold(dropout) / 65536``; each call draws (seed, offset) from torch's device generator, so ``torch.cuda.manual_seed``
+    reproduces a run and ``torch.utils.checkpoint``, which restores the generator state, recomputes with the same mask.  0.0, the
+    default, changes nothing.  With ``convs=True`` a dropout > 0 raises NotImplementedError before any module is touched."""
+    dropout = float(dropout)
+    if not 0.0 <= dropout < 1.0:
+        raise ValueError(f"add_lora: 0 <= dropout < 1 (got dropout = {dropout})")
+    if convs and dropout > 0.0:
+        raise NotImplementedError("add_lora: dropout on conv adapters is not built (the conv adapter kernels have no mask); call "
+                                  "add_lora(..., convs=True) with dropout=0, or add_lora(..., dropout=p) for the Linear layers alone")
     if rank % 8 or not 8 <= rank <= 256:
         raise ValueError(f"add_lora: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank}): the adapter kernels move 16-byte rank chunks")
     if dtype is not None and dtype not in (torch.float32, *_DTYPES):
@@ -461,6 +535,7 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
         module.lora_down = torch.nn.Parameter(down.to(device=dev, dtype=pdt))
         module.lora_up = torch.nn.Parameter(torch.zeros(up_shape, device=dev, dtype=pdt))
         module.lora_scale = scale
+        module.lora_dropout = dropout
         fwd = module.forward_func
         module.forward_func = (_with_conv_lora if conv else _with_lora)(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
         _refresh_compile_plan(module)
@@ -480,9 +555,9 @@ def _lora_modules(model: torch.nn.Module):
 
 
 def remove_lora(model: torch.nn.Module) -> int:
-    """Take the adapters off: every layer gets back the very forward it had before `add_lora` and loses lora_down, lora_up and
-    lora_scale.  A layer whose forward was re-pointed after `add_lora` (see there) keeps the forward it has now and loses the three
-    attributes.  Returns the number of layers changed."""
+    """Take the adapters off: every layer gets back the very forward it had before `add_lora` and loses lora_down, lora_up,
+    lora_scale and lora_dropout.  A layer whose forward was re-pointed after `add_lora` (see there) keeps the forward it has now and
+    loses the four attributes.  Returns the number of layers changed."""
     count = 0
     for module in list(model.modules()):
         wrapped = getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None
@@ -491,7 +566,7 @@ def remove_lora(model: torch.nn.Module) -> int:
         if wrapped:
             module.forward_func = module.forward_func._sdnq_lora_previous
             _refresh_compile_plan(module)
-        for attr in ("lora_down", "lora_up", "lora_scale"):
+        for attr in ("lora_down", "lora_up", "lora_scale", "lora_dropout"):
             if hasattr(module, attr):
                 delattr(module, attr)
         count += 1

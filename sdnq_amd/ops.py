@@ -1032,26 +1032,36 @@ def _lowrank_check(what: str, rank: int, **tensors) -> None:
                                     f"{t.storage_offset()}, row stride {t.stride(0)} elements)")
 
 
+def _lowrank_add(what: str, t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float, drop=None) -> torch.Tensor:
+    """lowrank_add (drop None) and lowrank_add_dropout (drop = (threshold, seed, offset)): the same checks under the caller's name."""
+    if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
+        raise _lib.SdnqHipError(f"{what}: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    (m, r), (n, r2) = t.shape, up.shape
+    _lowrank_check(what, r, t=t, up=up, y=y)
+    if r2 != r or tuple(y.shape) != (m, n):
+        raise _lib.SdnqHipError(f"{what}: t [M, R], up [N, R], y [M, N] (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    if n % 8:
+        raise _lib.SdnqHipError(f"{what}: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
+    if not t.is_contiguous() or not up.is_contiguous():
+        raise _lib.SdnqHipError(f"{what}: t and up must be contiguous")
+    if drop is not None:
+        drop = _dropout_args(what, *drop)
+    _require_cuda(t, up, y)
+    if m == 0:
+        return y
+    head = (t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y))
+    if drop is None:
+        check(_lib.load().sdnq_hip_lowrank_add(*head, _stream(y)), what)
+    else:
+        check(_lib.load().sdnq_hip_lowrank_add_dropout(*head, *drop, _stream(y)), what)
+    return y
+
+
 def lowrank_add(t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     """sdnq_hip_lowrank_add: y [M, N] += scale * t [M, R] @ up [N, R]^T IN PLACE on the matrix cores, every element rounded once:
     y = round(fma(scale, sum_r t up, y)).  bfloat16 / float16; y may be a column slice of a wider buffer (unit column stride, 16-byte
     aligned rows); t and up contiguous.  Returns y."""
-    if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
-        raise _lib.SdnqHipError(f"lowrank_add: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
-    (m, r), (n, r2) = t.shape, up.shape
-    _lowrank_check("lowrank_add", r, t=t, up=up, y=y)
-    if r2 != r or tuple(y.shape) != (m, n):
-        raise _lib.SdnqHipError(f"lowrank_add: t [M, R], up [N, R], y [M, N] (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
-    if n % 8:
-        raise _lib.SdnqHipError(f"lowrank_add: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
-    if not t.is_contiguous() or not up.is_contiguous():
-        raise _lib.SdnqHipError("lowrank_add: t and up must be contiguous")
-    _require_cuda(t, up, y)
-    if m == 0:
-        return y
-    check(_lib.load().sdnq_hip_lowrank_add(t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y),
-                                           _stream(y)), "lowrank_add")
-    return y
+    return _lowrank_add("lowrank_add", t, up, y, scale)
 
 
 def lowrank_grad_workspace_bytes(m: int, p: int, rank: int) -> int:
@@ -1062,24 +1072,20 @@ def lowrank_grad_workspace_bytes(m: int, p: int, rank: int) -> int:
     return int(nbytes)
 
 
-def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bool = False, out_dtype: torch.dtype | None = None,
-                 workspace: torch.Tensor | None = None) -> torch.Tensor:
-    """sdnq_hip_lowrank_grad: round(scale * a [M, P]^T @ b [M, R]) -> [P, R] (out_t: [R, P]) of `out_dtype` (default: the operands'),
-    float32 sums on the matrix cores over slabs of rows added in a fixed order: the same bits on every call, no atomics.  a may be a
-    column slice (unit column stride, 16-byte aligned rows), b contiguous; bfloat16 / float16.  workspace: a uint8 tensor of at least
-    lowrank_grad_workspace_bytes(M, P, R) bytes, or None -- then the per-(device, stream) buffer of this module (_workspace: at least 1 MB,
-    kept for the life of the process, NOT counted by training.scratch_bytes() nor freed by training.release_scratch(); sdnq_amd.lora passes
-    its own, which is) is used, and a call that would have to grow it while its stream is being captured raises before any launch."""
+def _lowrank_grad(what: str, a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype, workspace, drop=None) -> torch.Tensor:
+    """lowrank_grad (drop None) and lowrank_grad_dropout (drop = (threshold, seed, offset)): the same checks under the caller's name."""
     if a.ndim != 2 or b.ndim != 2:
-        raise _lib.SdnqHipError(f"lowrank_grad: a and b must be 2-D (got {tuple(a.shape)}, {tuple(b.shape)})")
+        raise _lib.SdnqHipError(f"{what}: a and b must be 2-D (got {tuple(a.shape)}, {tuple(b.shape)})")
     (m, p), (m2, r) = a.shape, b.shape
-    _lowrank_check("lowrank_grad", r, a=a, b=b)
+    _lowrank_check(what, r, a=a, b=b)
     if m2 != m:
-        raise _lib.SdnqHipError(f"lowrank_grad: a [M, P] and b [M, R] must have the same rows (got {tuple(a.shape)}, {tuple(b.shape)})")
+        raise _lib.SdnqHipError(f"{what}: a [M, P] and b [M, R] must have the same rows (got {tuple(a.shape)}, {tuple(b.shape)})")
     if p % 8:
-        raise _lib.SdnqHipError(f"lowrank_grad: p % 8 == 0 (got p = {p}): a is read in 16-byte pieces")
+        raise _lib.SdnqHipError(f"{what}: p % 8 == 0 (got p = {p}): a is read in 16-byte pieces")
     if not b.is_contiguous():
-        raise _lib.SdnqHipError("lowrank_grad: b must be contiguous")
+        raise _lib.SdnqHipError(f"{what}: b must be contiguous")
+    if drop is not None:
+        drop = _dropout_args(what, *drop)
     _require_cuda(a, b, workspace)
     out_dtype = a.dtype if out_dtype is None else out_dtype
     out = torch.empty((r, p) if out_t else (p, r), device=a.device, dtype=out_dtype)
@@ -1090,19 +1096,83 @@ def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bo
     if need and workspace is None:
         have = _workspaces.get((a.device.index, _stream(a)))
         if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
-            raise _lib.SdnqHipError("lowrank_grad: the module's workspace would have to grow inside a graph capture; pass workspace= or run "
+            raise _lib.SdnqHipError(f"{what}: the module's workspace would have to grow inside a graph capture; pass workspace= or run "
                                     "one eager call on this stream first")
         workspace = _workspace(a.device, _stream(a), need + 16)
     if need and (not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need):
-        raise _lib.SdnqHipError(f"lowrank_grad: workspace must be a uint8 device tensor of at least {need} bytes")
+        raise _lib.SdnqHipError(f"{what}: workspace must be a uint8 device tensor of at least {need} bytes")
     wp = 0
     if need:
         wp = (workspace.data_ptr() + 15) & ~15
         if wp + need > workspace.data_ptr() + workspace.numel():
-            raise _lib.SdnqHipError(f"lowrank_grad: workspace must hold {need} bytes behind its first 16-byte boundary")
-    check(_lib.load().sdnq_hip_lowrank_grad(a.data_ptr(), _ld(a), b.data_ptr(), float_code(a.dtype), m, p, r, float(scale), int(bool(out_t)),
-                                            out.data_ptr(), code, wp or None, need, _stream(a)), "lowrank_grad")
+            raise _lib.SdnqHipError(f"{what}: workspace must hold {need} bytes behind its first 16-byte boundary")
+    head = (a.data_ptr(), _ld(a), b.data_ptr(), float_code(a.dtype), m, p, r, float(scale), int(bool(out_t)), out.data_ptr(), code, wp or None, need)
+    if drop is None:
+        check(_lib.load().sdnq_hip_lowrank_grad(*head, _stream(a)), what)
+    else:
+        check(_lib.load().sdnq_hip_lowrank_grad_dropout(*head, *drop, _stream(a)), what)
     return out
+
+
+def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bool = False, out_dtype: torch.dtype | None = None,
+                 workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_lowrank_grad: round(scale * a [M, P]^T @ b [M, R]) -> [P, R] (out_t: [R, P]) of `out_dtype` (default: the operands'),
+    float32 sums on the matrix cores over slabs of rows added in a fixed order: the same bits on every call, no atomics.  a may be a
+    column slice (unit column stride, 16-byte aligned rows), b contiguous; bfloat16 / float16.  workspace: a uint8 tensor of at least
+    lowrank_grad_workspace_bytes(M, P, R) bytes, or None -- then the per-(device, stream) buffer of this module (_workspace: at least 1 MB,
+    kept for the life of the process, NOT counted by training.scratch_bytes() nor freed by training.release_scratch(); sdnq_amd.lora passes
+    its own, which is) is used, and a call that would have to grow it while its stream is being captured raises before any launch."""
+    return _lowrank_grad("lowrank_grad", a, b, scale, out_t, out_dtype, workspace)
+
+
+# ---- LoRA dropout: the three adapter kernels with the mask recomputed inside (include/sdnq_hip.h has the counter convention) -----------------
+def _dropout_args(what: str, threshold: int, seed: int, offset: int) -> tuple:
+    """(threshold, seed, offset) as the library takes them: an element is dropped iff its 16 random bits are < threshold."""
+    threshold, seed, offset = int(threshold), int(seed), int(offset)
+    if not 1 <= threshold <= 65535:
+        raise _lib.SdnqHipError(f"{what}: 1 <= threshold <= 65535 (got threshold = {threshold}): the probability of a drop is threshold / 65536")
+    if not (0 <= seed < 1 << 64 and 0 <= offset < 1 << 64):
+        raise _lib.SdnqHipError(f"{what}: seed and offset are unsigned 64-bit integers (got seed = {seed}, offset = {offset})")
+    return threshold, seed, offset
+
+
+def lowrank_down_dropout(x2d: torch.Tensor, down: torch.Tensor, threshold: int, seed: int, offset: int) -> torch.Tensor:
+    """sdnq_hip_lowrank_down_dropout: t [M, R] = round((mask * x2d) @ down [R, K]^T), the bits of ``lowrank_down`` on a pre-masked x2d
+    without that tensor: element (i, j) of x2d is kept iff the 16 Philox bits of its LOGICAL index i K + j (key `seed`, `offset`, stream 5)
+    are >= `threshold`.  Survivors are not rescaled (the caller's scale carries 1 / (1 - p)).  bfloat16 / float16, 16 | K; x2d may be
+    row-strided (unit column stride, 16-byte aligned rows), down contiguous.  There is no float32 and no few-row path."""
+    if x2d.ndim != 2 or down.ndim != 2:
+        raise _lib.SdnqHipError(f"lowrank_down_dropout: x and down must be 2-D (got {tuple(x2d.shape)}, {tuple(down.shape)})")
+    (m, k), (r, k2) = x2d.shape, down.shape
+    _lowrank_check("lowrank_down_dropout", r, x=x2d, down=down)
+    if k2 != k:
+        raise _lib.SdnqHipError(f"lowrank_down_dropout: x [M, K] and down [R, K] (got {tuple(x2d.shape)}, {tuple(down.shape)})")
+    if k % 16:
+        raise _lib.SdnqHipError(f"lowrank_down_dropout: k % 16 == 0 (got k = {k}): the matrix-core kernel is the only path")
+    if not down.is_contiguous():
+        raise _lib.SdnqHipError("lowrank_down_dropout: down must be contiguous")
+    threshold, seed, offset = _dropout_args("lowrank_down_dropout", threshold, seed, offset)
+    _require_cuda(x2d, down)
+    t = torch.empty((m, r), device=x2d.device, dtype=x2d.dtype)
+    if m == 0:
+        return t
+    check(_lib.load().sdnq_hip_lowrank_down_dropout(x2d.data_ptr(), float_code(x2d.dtype), m, k, _ld(x2d), down.data_ptr(), r, t.data_ptr(),
+                                                    threshold, seed, offset, _stream(x2d)), "lowrank_down_dropout")
+    return t
+
+
+def lowrank_add_dropout(t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float, threshold: int, seed: int, offset: int) -> torch.Tensor:
+    """sdnq_hip_lowrank_add_dropout: ``lowrank_add`` on the elements of y [M, N] that the mask keeps (logical index i N + j, as
+    ``lowrank_down_dropout``); a dropped element keeps its bits.  IN PLACE; returns y."""
+    return _lowrank_add("lowrank_add_dropout", t, up, y, scale, (threshold, seed, offset))
+
+
+def lowrank_grad_dropout(a: torch.Tensor, b: torch.Tensor, scale: float, threshold: int, seed: int, offset: int, out_t: bool = False,
+                         out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """sdnq_hip_lowrank_grad_dropout: round(scale * (mask * a [M, P])^T @ b [M, R]), the bits of ``lowrank_grad`` on a pre-masked a
+    without that tensor (logical index i P + j, as ``lowrank_down_dropout``).  Everything else -- slabs, workspace, out_t, out_dtype -- as
+    ``lowrank_grad``."""
+    return _lowrank_grad("lowrank_grad_dropout", a, b, scale, out_t, out_dtype, workspace, (threshold, seed, offset))
 
 
 def _conv_lowrank_check(what: str, x: torch.Tensor, other: torch.Tensor, kernel, stride, padding, dilation):

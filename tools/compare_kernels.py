@@ -2,8 +2,9 @@
 """Compare the kernels of two builds of the library: the proof a kernel refactor wants ("the generated code did not change").
 For every kernel symbol of either build: the resource notes (VGPRs, AGPRs, SGPRs, LDS, scratch, spills, kernarg bytes) and whether
 the instruction listings are equal.  The listings are `llvm-objdump -d --no-show-raw-insn` without what only says WHERE the code
-lies: the address / encoding comments, the resolved branch targets (the relative offsets stay) and the literals of
-pc-relative address computations (s_getpc_b64 and the add pair behind it).
+lies: the address / encoding comments, the resolved branch targets (the relative offsets stay), the literals of
+pc-relative address computations (s_getpc_b64 and the add pair behind it) and the `...` objdump prints for the zero padding between
+one function's end and the next one's aligned start (it depends on which function the linker placed behind).
 
 usage: tools/compare_kernels.py <parent lib> <branch lib> [--diff <substr>]
 One line per kernel: name, resources, `same` | `differs (<+/- instructions>)` | `resources differ` | `only in ...`; then totals.
@@ -30,7 +31,7 @@ def listings(lib):
                     cur = out.setdefault(m.group(1), [])
                     continue
                 ins = line.split("//")[0].strip()
-                if cur is None or not ins:
+                if cur is None or not ins or ins == "...":
                     continue
                 if pcrel and re.match(r"s_addc?_u32 ", ins):
                     ins = re.sub(r"(0x[0-9a-f]+|\d+)$", "<pcrel>", ins)
