@@ -13,7 +13,7 @@ Per call:
     backward     g_t = ops.lowrank_down(dY, up^T)              [M][rank]; its matrix-core kernel needs 16 | N: a layer with N % 16 == 8 (which
                                                                add_lora serves) takes sdnq_hip_linear_float's few-row kernel there --
                                                                the same values, much slower; not measured
-                 grad_input = ops.linear_float(dY, W^T)        as QuantizedLinearInputGrad computes it (ops.weight_t into the scratch)
+                 grad_input = ops.linear_float(dY, W^T)        training._linear_base_grad: ops.weight_t into the "operand" scratch slot
                  grad_input += scale * g_t . down              ops.lowrank_add, in place: one more rounding of grad_input
                  grad_up    = scale * dY^T . t                 ops.lowrank_grad, [N][rank]
                  grad_down  = scale * g_t^T . x                ops.lowrank_grad(out_t=True), [rank][K]
@@ -75,26 +75,15 @@ import math
 
 import torch
 
-from . import _lib, ops, training
+from . import _lib, ops, scratch, training
 from .linear import _attr
 
 _DTYPES = (torch.bfloat16, torch.float16)
 
 
 def _workspace(dev: torch.device, nbytes: int):
-    """The float32 partial sums of ops.lowrank_grad: a fourth buffer of the per-device input-gradient scratch (training._SCRATCH), under
-    the rules of the other three -- grown to the largest seen, counted by training.scratch_bytes(), freed by training.release_scratch()."""
-    if nbytes == 0:
-        return None
-    bufs = training._SCRATCH.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [None, None, None])
-    while len(bufs) < 4:
-        bufs.append(None)
-    if bufs[3] is None or bufs[3].numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.SdnqHipError("adapter scratch: run one eager backward before capturing a graph (the buffer is not sized yet)")
-        bufs[3] = None
-        bufs[3] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return bufs[3]
+    """The float32 partial sums of ops.lowrank_grad / ops.conv_lowrank_grad: the "partials" slot of sdnq_amd.scratch, None for no bytes."""
+    return scratch.take(dev, "adapter scratch", nbytes, "partials")[0] if nbytes else None
 
 
 def _factor_grad(a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype: torch.dtype, drop=None) -> torch.Tensor:
@@ -188,7 +177,6 @@ class QuantizedLinearLoRA(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        from . import linear
         layer = ctx.layer
         dq = layer.sdnq_dequantizer
         x2d, t, down, up = ctx.saved_tensors
@@ -212,10 +200,7 @@ class QuantizedLinearLoRA(torch.autograd.Function):
             if need_x or need_down:
                 g_t = ops.lowrank_down(g2d, up.to(dt).t().contiguous())
             if need_x:
-                qw = linear._state(layer).qw
-                had = dq.hadamard_group_size if dq.use_hadamard else 0
-                scratch = training._scratch(g2d.device, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)
-                gi2d = ops.linear_float(g2d, ops.weight_t(qw, dt, had, scratch), None)
+                gi2d = training._linear_base_grad(layer, g2d)
                 if drop is None:
                     ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
                 else:
@@ -237,12 +222,6 @@ class QuantizedLinearLoRA(torch.autograd.Function):
 # is kprod times the bytes of x.  ops.conv_lowrank_down / ops.conv_lowrank_grad (csrc/conv_lowrank.hip) read x itself; on the eleven SDXL
 # conv problems of tools/conv_lora_bench.py (bf16, batch 1, ranks 16 and 64; profiles/conv_lora_bench.jsonl) they take 0.28 - 0.92 and
 # 0.33 - 0.87 of the time of ops.im2col + the Linear adapter's kernel, so no layer takes that composition.
-def _conv_down_grad(x4: torch.Tensor, g_t: torch.Tensor, kernel, stride, padding, dilation, scale: float, out_dtype: torch.dtype) -> torch.Tensor:
-    """grad_down2d [rank][K] = scale * g_t^T . im2col(x); the float32 partial sums in the fourth scratch buffer (_workspace)."""
-    ws = _workspace(x4.device, ops.conv_lowrank_grad_workspace_bytes(x4.shape, kernel, stride, padding, dilation, g_t.shape[1]))
-    return ops.conv_lowrank_grad(x4, g_t, kernel, stride, padding, dilation, scale, out_dtype=out_dtype, workspace=ws)
-
-
 def _conv_check_call(layer, input: torch.Tensor, nd: int) -> torch.dtype:
     dt = layer.sdnq_dequantizer.result_dtype
     if not input.is_cuda:
@@ -287,7 +266,7 @@ def _conv_run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Te
 def _conv_adapter_grad_input(route: str, gi: torch.Tensor, g_t: torch.Tensor, down: torch.Tensor, shape4, out_shape, geometry, scale: float):
     """grad_x [B][C_in][H][W] = (the base gradient `gi` of training._conv_base_grad's `route`) + scale * conv^T(g_t, down), the adapter
     term from existing kernels: g_t as [B][rank][H_out][W_out] goes through ops.im2col_bwd -- U_g [B H W][kprod rank], columns (kernel
-    position, r), in the third scratch buffer, which the base gradient is done with -- and meets down rearranged to [C_in][kprod rank].
+    position, r), in the "unfolded" scratch slot, which the base gradient is done with -- and meets down rearranged to [C_in][kprod rank].
     Roundings of an element, after the base gradient's own one:
       kprod rank <= 256, gather route, 8 | C_in     ops.lowrank_add on the NHWC rows, before the permute: ONE more
       kprod rank <= 256, col2im route, 8 | H W      ops.lowrank_add per image with its operands swapped, on the NCHW result: ONE more
@@ -374,7 +353,8 @@ class QuantizedConvLoRA(torch.autograd.Function):
             if need_up:
                 grad_up = _factor_grad(dy2d, t, scale, False, up.dtype).view(up.shape)
             if need_down:
-                grad_down = _conv_down_grad(x4, g_t, kernel, stride, padding, dilation, scale, down.dtype).view(down.shape)
+                ws = _workspace(x4.device, ops.conv_lowrank_grad_workspace_bytes(x4.shape, kernel, stride, padding, dilation, rank))
+                grad_down = ops.conv_lowrank_grad(x4, g_t, kernel, stride, padding, dilation, scale, out_dtype=down.dtype, workspace=ws).view(down.shape)
         if need_bias:
             grad_bias = grad_output.sum(dim=[0] + list(range(2, grad_output.ndim))).to(ctx.bias_dtype)
         return None, None, grad_input, grad_down, grad_up, grad_bias

@@ -1013,6 +1013,11 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _rank_check(what: str, rank: int) -> None:
+    if rank % 8 or not 8 <= rank <= 256:
+        raise _lib.SdnqHipError(f"{what}: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank})")
+
+
 def _lowrank_check(what: str, rank: int, **tensors) -> None:
     """The checks the two adapter entry points share: device tensors of ONE 16-bit dtype, 8 <= rank <= 256 a multiple of 8, 2-D operands
     with contiguous, 16-byte aligned rows -- each failure names what is wrong.  (The device check comes last, in the callers: what a call
@@ -1020,8 +1025,7 @@ def _lowrank_check(what: str, rank: int, **tensors) -> None:
     dt = next(iter(tensors.values())).dtype
     if dt not in (torch.bfloat16, torch.float16):
         raise _lib.SdnqHipError(f"{what}: built for bfloat16 / float16 operands (got {dt})")
-    if rank % 8 or not 8 <= rank <= 256:
-        raise _lib.SdnqHipError(f"{what}: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank})")
+    _rank_check(what, rank)
     for name, t in tensors.items():
         if t.dtype != dt:
             raise _lib.SdnqHipError(f"{what}: {name} must have the dtype of the other operands (got {t.dtype}, {dt})")
@@ -1072,6 +1076,25 @@ def lowrank_grad_workspace_bytes(m: int, p: int, rank: int) -> int:
     return int(nbytes)
 
 
+def _grad_workspace(what: str, device: torch.device, stream: int, need: int, workspace):
+    """The 16-byte aligned address of `need` bytes (None for 0) inside `workspace`, which the caller's _require_cuda has seen to be on the
+    device, or for None inside the per-(device, stream) buffer of _workspace, which does not grow while its stream is being captured."""
+    if not need:
+        return None
+    if workspace is None:
+        have = _workspaces.get((device.index, stream))
+        if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
+            raise _lib.SdnqHipError(f"{what}: the module's workspace would have to grow inside a graph capture; pass workspace= or run "
+                                    "one eager call on this stream first")
+        workspace = _workspace(device, stream, need + 16)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise _lib.SdnqHipError(f"{what}: workspace must be a uint8 device tensor of at least {need} bytes")
+    wp = (workspace.data_ptr() + 15) & ~15
+    if wp + need > workspace.data_ptr() + workspace.numel():
+        raise _lib.SdnqHipError(f"{what}: workspace must hold {need} bytes behind its first 16-byte boundary")
+    return wp
+
+
 def _lowrank_grad(what: str, a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype, workspace, drop=None) -> torch.Tensor:
     """lowrank_grad (drop None) and lowrank_grad_dropout (drop = (threshold, seed, offset)): the same checks under the caller's name."""
     if a.ndim != 2 or b.ndim != 2:
@@ -1093,20 +1116,8 @@ def _lowrank_grad(what: str, a: torch.Tensor, b: torch.Tensor, scale: float, out
     if m == 0:
         return out.zero_()
     need = lowrank_grad_workspace_bytes(m, p, r)
-    if need and workspace is None:
-        have = _workspaces.get((a.device.index, _stream(a)))
-        if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
-            raise _lib.SdnqHipError(f"{what}: the module's workspace would have to grow inside a graph capture; pass workspace= or run "
-                                    "one eager call on this stream first")
-        workspace = _workspace(a.device, _stream(a), need + 16)
-    if need and (not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need):
-        raise _lib.SdnqHipError(f"{what}: workspace must be a uint8 device tensor of at least {need} bytes")
-    wp = 0
-    if need:
-        wp = (workspace.data_ptr() + 15) & ~15
-        if wp + need > workspace.data_ptr() + workspace.numel():
-            raise _lib.SdnqHipError(f"{what}: workspace must hold {need} bytes behind its first 16-byte boundary")
-    head = (a.data_ptr(), _ld(a), b.data_ptr(), float_code(a.dtype), m, p, r, float(scale), int(bool(out_t)), out.data_ptr(), code, wp or None, need)
+    wp = _grad_workspace(what, a.device, _stream(a), need, workspace)
+    head = (a.data_ptr(), _ld(a), b.data_ptr(), float_code(a.dtype), m, p, r, float(scale), int(bool(out_t)), out.data_ptr(), code, wp, need)
     if drop is None:
         check(_lib.load().sdnq_hip_lowrank_grad(*head, _stream(a)), what)
     else:
@@ -1121,7 +1132,7 @@ def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bo
     column slice (unit column stride, 16-byte aligned rows), b contiguous; bfloat16 / float16.  workspace: a uint8 tensor of at least
     lowrank_grad_workspace_bytes(M, P, R) bytes, or None -- then the per-(device, stream) buffer of this module (_workspace: at least 1 MB,
     kept for the life of the process, NOT counted by training.scratch_bytes() nor freed by training.release_scratch(); sdnq_amd.lora passes
-    its own, which is) is used, and a call that would have to grow it while its stream is being captured raises before any launch."""
+    the "partials" slot of sdnq_amd.scratch, which is) is used, and a call that would grow it while its stream is captured raises before any launch."""
     return _lowrank_grad("lowrank_grad", a, b, scale, out_t, out_dtype, workspace)
 
 
@@ -1202,8 +1213,7 @@ def conv_lowrank_down(x: torch.Tensor, down: torch.Tensor, kernel, stride, paddi
     bfloat16 / float16.  The value of lowrank_down(im2col(x), down) up to the order of the float32 sum.  Returns (t, (B, H_out, W_out))."""
     geo, out_shape, k = _conv_lowrank_check("conv_lowrank_down", x, down, kernel, stride, padding, dilation)
     r = down.shape[0]
-    if r % 8 or not 8 <= r <= 256:
-        raise _lib.SdnqHipError(f"conv_lowrank_down: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {r})")
+    _rank_check("conv_lowrank_down", r)
     if down.shape[1] != k or not down.is_contiguous():
         raise _lib.SdnqHipError(f"conv_lowrank_down: down must be contiguous [R, C * kh * kw = {k}] (got {tuple(down.shape)}, strides {down.stride()})")
     _require_cuda(x, down)
@@ -1232,8 +1242,7 @@ def conv_lowrank_grad(x: torch.Tensor, g: torch.Tensor, kernel, stride, padding,
     conv_lowrank_grad_workspace_bytes(...) bytes, or None for this module's per-(device, stream) buffer)."""
     geo, out_shape, k = _conv_lowrank_check("conv_lowrank_grad", x, g, kernel, stride, padding, dilation)
     m, r = g.shape
-    if r % 8 or not 8 <= r <= 256:
-        raise _lib.SdnqHipError(f"conv_lowrank_grad: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {r})")
+    _rank_check("conv_lowrank_grad", r)
     if m != out_shape[0] * out_shape[1] * out_shape[2] or not g.is_contiguous():
         raise _lib.SdnqHipError(f"conv_lowrank_grad: g must be contiguous [B * H_out * W_out = {out_shape[0] * out_shape[1] * out_shape[2]}, R] "
                                 f"(got {tuple(g.shape)}, strides {g.stride()})")
@@ -1242,21 +1251,9 @@ def conv_lowrank_grad(x: torch.Tensor, g: torch.Tensor, kernel, stride, padding,
     out_dtype = x.dtype if out_dtype is None else out_dtype
     out = torch.empty((r, k), device=x.device, dtype=out_dtype)
     need = conv_lowrank_grad_workspace_bytes(x.shape, kernel, stride, padding, dilation, r)
-    if need and workspace is None:
-        have = _workspaces.get((x.device.index, _stream(x)))
-        if (have is None or have.numel() < need + 16) and torch.cuda.is_current_stream_capturing():
-            raise _lib.SdnqHipError("conv_lowrank_grad: the module's workspace would have to grow inside a graph capture; pass workspace= or "
-                                    "run one eager call on this stream first")
-        workspace = _workspace(x.device, _stream(x), need + 16)
-    if need and (not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need):
-        raise _lib.SdnqHipError(f"conv_lowrank_grad: workspace must be a uint8 device tensor of at least {need} bytes")
-    wp = 0
-    if need:
-        wp = (workspace.data_ptr() + 15) & ~15
-        if wp + need > workspace.data_ptr() + workspace.numel():
-            raise _lib.SdnqHipError(f"conv_lowrank_grad: workspace must hold {need} bytes behind its first 16-byte boundary")
+    wp = _grad_workspace("conv_lowrank_grad", x.device, _stream(x), need, workspace)
     check(_lib.load().sdnq_hip_conv_lowrank_grad(x.data_ptr(), float_code(x.dtype), *geo, g.data_ptr(), r, float(scale), out.data_ptr(),
-                                                 float_code(out_dtype), wp or None, need, _stream(x)), "conv_lowrank_grad")
+                                                 float_code(out_dtype), wp, need, _stream(x)), "conv_lowrank_grad")
     return out
 
 

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, ops
+from . import _lib, linear, ops, scratch
 from ._lib import MM_I8
 
 _FLOATS = (torch.float32, torch.bfloat16, torch.float16)
@@ -211,48 +211,42 @@ globals().update({name: _not_built(name, what) for name, what in NOT_BUILT.items
 # The reference's QuantizedLinearBackward (training/layers/linear/forward.py): the forward is the layer, grad_input = grad_output @
 # weight.dequantize().  Here the forward is the layer's own accelerated forward_func -- whatever it is: w8a8, fp8, uint8, float16 matmul,
 # dequantize mode, the few-row branch, plans, linked projections -- so its output bits are the inference call's, and the backward decodes
-# the stored codes transposed into ONE scratch buffer per device (ops.weight_t) and runs the float GEMM on it.  No float copy per layer:
-# peak extra memory is one float copy of the LARGEST layer seen (two when a layer has SVD factors or a Hadamard rotation).
-_SCRATCH = {}  # device index -> [first, second | None, unfolded | None]: uint8 buffers, grown to the largest seen and reused by every layer
-
-
+# the stored codes transposed into the "operand" slot of sdnq_amd.scratch (ops.weight_t) and runs the float GEMM on it.  No float copy per
+# layer: peak extra memory is one float copy of the LARGEST layer seen (two, the "decoded" slot, with SVD factors or a Hadamard rotation).
 def _scratch(dev: torch.device, dtype: torch.dtype, numel: int, two: bool):
-    """(first, second | None) as 1-D tensors of `dtype` with at least `numel` elements.  `second` exists once a layer with SVD factors or a
-    Hadamard rotation was seen and then has the size of `first`.  The buffers are used in stream order by the stream the backward runs on
-    (autograd runs a node's backward on its forward's stream); a model whose backwards run on several streams at once is not served."""
-    nbytes = numel * dtype.itemsize
-    bufs = _SCRATCH.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [None, None, None])
-    have = 0 if bufs[0] is None else bufs[0].numel()
-    want = max(have, nbytes)
-    grow = [i for i in range(2) if (i == 0 or two or bufs[1] is not None) and (bufs[i] is None or bufs[i].numel() < want)]
-    if grow and torch.cuda.is_current_stream_capturing():
-        raise _lib.SdnqHipError("input-gradient scratch: run one eager backward before capturing a graph (the buffer is not sized yet)")
-    for i in grow:
-        bufs[i] = None  # (the old block goes back to the allocator before the new one is taken)
-        bufs[i] = torch.empty(want, device=dev, dtype=torch.uint8)
-    return bufs[0].view(dtype), (None if bufs[1] is None else bufs[1].view(dtype))
+    """(operand, decoded | None) as 1-D tensors of `dtype` with at least `numel` elements: the "operand" and "decoded" slots of
+    sdnq_amd.scratch.  "decoded" exists once a layer with SVD factors or a Hadamard rotation was seen and then has the size of "operand"."""
+    have = scratch.held(dev)
+    want = max(have["operand"].numel() if "operand" in have else 0, numel * dtype.itemsize)
+    both = two or "decoded" in have
+    bufs = scratch.take(dev, "input-gradient scratch", want, "operand", *(("decoded",) if both else ()))
+    return bufs[0].view(dtype), (bufs[1].view(dtype) if both else None)
 
 
 def _scratch_unfolded(dev: torch.device, dtype: torch.dtype, numel: int) -> torch.Tensor:
-    """The third buffer of a device, under the rules of the first two: the unfolded grad_output (one slab of U) of a conv backward."""
-    nbytes = numel * dtype.itemsize
-    bufs = _SCRATCH.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [None, None, None])
-    if bufs[2] is None or bufs[2].numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.SdnqHipError("input-gradient scratch: run one eager backward before capturing a graph (the buffer is not sized yet)")
-        bufs[2] = None
-        bufs[2] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return bufs[2].view(dtype)
+    """The whole "unfolded" slot as `dtype`, at least `numel` elements: the unfolded grad_output (one slab of U) of a conv backward."""
+    return scratch.take(dev, "input-gradient scratch", numel * dtype.itemsize, "unfolded")[0].view(dtype)
 
 
 def scratch_bytes(device=None) -> int:
-    """Bytes the input-gradient scratch holds on `device` (default: the current one)."""
-    idx = torch.cuda.current_device() if device is None else torch.device(device).index
-    return sum(b.numel() for b in _SCRATCH.get(idx, ()) if b is not None)
+    """Bytes the input-gradient and adapter scratch holds on `device` (default: the current one)."""
+    return sum(b.numel() for b in scratch.held(torch.device("cuda" if device is None else device)).values())
 
 
 def release_scratch() -> None:
-    _SCRATCH.clear()
+    scratch.release()
+
+
+def _weight_t_operand(layer, qw, dtype: torch.dtype, dev: torch.device) -> torch.Tensor:
+    """ops.weight_t of a frozen layer -- W^T [K][N], SVD product added, Hadamard rotation undone -- in the "operand" slot."""
+    dq = layer.sdnq_dequantizer
+    had = dq.hadamard_group_size if dq.use_hadamard else 0
+    return ops.weight_t(qw, dtype, had, _scratch(dev, dtype, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0))
+
+
+def _linear_base_grad(layer, g2d: torch.Tensor) -> torch.Tensor:
+    """grad_input [M][K] = dY . W of a frozen Linear layer, as QuantizedLinearInputGrad and the adapter of sdnq_amd.lora both compute it."""
+    return ops.linear_float(g2d, _weight_t_operand(layer, linear._state(layer).qw, g2d.dtype, g2d.device), None)
 
 
 class QuantizedLinearInputGrad(torch.autograd.Function):
@@ -273,7 +267,6 @@ class QuantizedLinearInputGrad(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        from . import linear
         layer = ctx.layer
         dq = layer.sdnq_dequantizer
         if grad_output.dtype != dq.result_dtype:
@@ -287,10 +280,7 @@ class QuantizedLinearInputGrad(torch.autograd.Function):
             if g2d.shape[0] == 0:
                 grad_input = grad_output.new_zeros(ctx.input_shape)
             else:
-                qw = linear._state(layer).qw
-                had = dq.hadamard_group_size if dq.use_hadamard else 0
-                scratch = _scratch(g2d.device, g2d.dtype, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)
-                grad_input = ops.linear_float(g2d, ops.weight_t(qw, g2d.dtype, had, scratch), None).view(ctx.input_shape)
+                grad_input = _linear_base_grad(layer, g2d).view(ctx.input_shape)
         if ctx.needs_input_grad[2]:
             grad_bias = g2d.sum(0).to(ctx.bias_dtype)
         return None, grad_input, grad_bias
@@ -400,16 +390,15 @@ def _group_weights(layer, qw, groups: int):
 
 
 def _conv_weight_operands(layer, qw, groups: int, dtype: torch.dtype, dev: torch.device):
-    """[one per conv group] the weight operand [C_in / groups][kprod * C_out / groups] of the backward GEMM, all inside the first scratch
-    buffer (the groups one after the other: together N * K elements, the size of the whole weight)."""
+    """[one per conv group] the weight operand [C_in / groups][kprod * C_out / groups] of the backward GEMM, all inside the "operand" slot
+    of the scratch (the groups one after the other: together N * K elements, the size of the whole weight)."""
     dq = layer.sdnq_dequantizer
-    had = dq.hadamard_group_size if dq.use_hadamard else 0
-    whole = bool(qw.desc.svd_up) or had != 0
     ng, k = qw.n // groups, qw.k
     cg = int(dq.original_shape[1])
     if groups == 1:
-        return [ops.weight_t(qw, dtype, had, _scratch(dev, dtype, qw.n * k, whole)).view(cg, (k // cg) * ng)]
-    slabs = None if whole else _group_weights(layer, qw, groups)
+        return [_weight_t_operand(layer, qw, dtype, dev).view(cg, (k // cg) * ng)]
+    had = dq.hadamard_group_size if dq.use_hadamard else 0
+    slabs = None if qw.desc.svd_up or had else _group_weights(layer, qw, groups)
     first, second = _scratch(dev, dtype, qw.n * k, slabs is None)
     if slabs is None:
         # a Hadamard rotation (or a stored layout that cannot be cut by rows): the whole weight by the kernels of the forward, then one
@@ -422,7 +411,6 @@ def _conv_weight_operands(layer, qw, groups: int, dtype: torch.dtype, dev: torch
 def _conv_grad_input(layer, dy4: torch.Tensor, in_hw, kernel, stride, padding, dilation) -> torch.Tensor:
     """grad2d [B * H * W][C_in] (NHWC rows) of a conv layer from dY [B][C_out][H_out][W_out]: per slab of rows one im2col_bwd and one float
     GEMM per conv group into the slab's rows of grad2d."""
-    from . import linear
     dq = layer.sdnq_dequantizer
     groups = int(layer.groups)
     dt, dev = dy4.dtype, dy4.device
@@ -445,16 +433,13 @@ def _conv_grad_input(layer, dy4: torch.Tensor, in_hw, kernel, stride, padding, d
 def _conv_grad_input_col2im(layer, dy4: torch.Tensor, in_shape, kernel, stride, padding, dilation, dy2d=None) -> torch.Tensor:
     """grad_x [B][C_in][H][W] of an ungrouped conv layer by the kernels of the transposed convolution: cols[(b, oh, ow)][(ci, kpos)] =
     dY (NHWC) . W in float32 -- the weight operand is ops.weight_t's [C_in kprod][C_out] as it stands -- then every input pixel gathers the
-    taps that reach it (ops.col2im): float32 sums, one rounding.  `cols` lives in the third scratch buffer, whole images per slab (one
+    taps that reach it (ops.col2im): float32 sums, one rounding.  `cols` lives in the "unfolded" scratch slot, whole images per slab (one
     image at least, whatever the bound says).  dy2d: the NHWC copy of dY [B L_out][C_out] where the caller has made it already."""
-    from . import linear
-    dq = layer.sdnq_dequantizer
     qw = linear._state(layer).qw
     dt, dev = dy4.dtype, dy4.device
     b, cout, ho, wo = dy4.shape
     cin, h, w = in_shape[1], in_shape[2], in_shape[3]
-    had = dq.hadamard_group_size if dq.use_hadamard else 0
-    wt = ops.weight_t(qw, dt, had, _scratch(dev, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0))
+    wt = _weight_t_operand(layer, qw, dt, dev)
     per_image = ho * wo * qw.k
     imgs = _slab_rows(b, per_image * 4)
     cols = _scratch_unfolded(dev, torch.float32, imgs * per_image)
@@ -636,7 +621,7 @@ def enable_input_grad(model: torch.nn.Module, enabled: bool = True, convs: bool 
     Linear layers plus one slab of the unfolded grad_output, at most ``SDNQ_HIP_CONV_GRAD_SLAB_MB`` (default ``CONV_GRAD_SLAB_MB`` = 256)
     megabytes; all of it is counted by ``scratch_bytes()`` and freed by ``release_scratch()``.  Ungrouped layers with a stride, and ungrouped
     layers larger than 1 x 1 on at most 1024 input positions, take the kernels of the transposed convolution instead (float32-out GEMM +
-    ``ops.col2im``, its float32 matrix in the same third buffer, whole images per slab): the rule and the measurements behind it are at
+    ``ops.col2im``, its float32 matrix in the same "unfolded" slot, whole images per slab): the rule and the measurements behind it are at
     ``_takes_col2im_route``; both routes round every element once.  The default stays ``convs=False``: nothing changes for callers that do
     not ask."""
     count, skipped = 0, []

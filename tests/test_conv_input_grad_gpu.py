@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import sdnq_amd
-from sdnq_amd import linear as L, ops, training as T
+from sdnq_amd import linear as L, ops, scratch, training as T
 from tests import conv_grad_util as U
 from tests.golden_util import ConvCase, conv_case_names
 from tests.modules_util import to_f32_numpy
@@ -268,10 +268,11 @@ def test_scratch_is_the_largest_operand_plus_the_largest_unfolded_slab(gpu_devic
     assert T.scratch_bytes(gpu_device) == 0
     model(x.clone().requires_grad_()).float().sum().backward()
     operand, unfolded = 55296, 331776
-    assert T.scratch_bytes(gpu_device) == operand + unfolded and T._SCRATCH[gpu_device.index][1] is None
-    ptrs = [b.data_ptr() for b in T._SCRATCH[gpu_device.index] if b is not None]
+    assert T.scratch_bytes(gpu_device) == operand + unfolded and "decoded" not in scratch.held(gpu_device)
+    ptrs = [b.data_ptr() for b in scratch.held(gpu_device).values()]
+    assert len(ptrs) == 2
     model(x.clone().requires_grad_()).float().sum().backward()
-    assert [b.data_ptr() for b in T._SCRATCH[gpu_device.index] if b is not None] == ptrs            # reused, not regrown
+    assert [b.data_ptr() for b in scratch.held(gpu_device).values()] == ptrs                        # reused, not regrown
     # a capped slab caps the third buffer: 0.125 MB = 131072 B hold 113 rows of c1's U (1152 B each) or 151 of c2's (864 B each)
     T.release_scratch()
     monkeypatch.setenv("SDNQ_HIP_CONV_GRAD_SLAB_MB", "0.125")

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import sdnq_amd
-from sdnq_amd import linear as L, ops, training as T
+from sdnq_amd import linear as L, ops, scratch, training as T
 from tests.golden_util import Case, case_names
 from tests.modules_util import module_from_case, to_f32_numpy
 from tests.test_codebook_host import cb_case_names, load_case
@@ -261,7 +261,7 @@ def test_scratch_is_one_buffer_of_the_largest_layer(gpu_device):
     after = torch.cuda.memory_allocated(gpu_device)
     largest = max(n * k for n, k in sizes) * 2
     print("scratch", T.scratch_bytes(gpu_device), "allocated", after - before)
-    assert T.scratch_bytes(gpu_device) == largest and T._SCRATCH[gpu_device.index][1] is None
+    assert T.scratch_bytes(gpu_device) == largest and "decoded" not in scratch.held(gpu_device)
     grads = 2 * xg.numel() * 2                            # xg and xg.grad
     assert after - before <= largest + grads + 3 * 512, (after - before, largest, grads)   # (the allocator rounds a block up to 512 bytes)
     # a Hadamard layer brings the second buffer, of the same size
@@ -271,7 +271,7 @@ def test_scratch_is_one_buffer_of_the_largest_layer(gpu_device):
     hx = torch.randn(48, 128, device=gpu_device).to(torch.bfloat16).requires_grad_()
     T.quantized_linear_input_grad(had, hx).float().sum().backward()
     assert T.scratch_bytes(gpu_device) == 2 * largest
-    first = T._SCRATCH[gpu_device.index][0].data_ptr()
+    first = scratch.held(gpu_device)["operand"].data_ptr()
     model(x.clone().requires_grad_()).float().sum().backward()
-    assert T.scratch_bytes(gpu_device) == 2 * largest and T._SCRATCH[gpu_device.index][0].data_ptr() == first   # reused, not regrown
+    assert T.scratch_bytes(gpu_device) == 2 * largest and scratch.held(gpu_device)["operand"].data_ptr() == first   # reused, not regrown
     T.release_scratch()

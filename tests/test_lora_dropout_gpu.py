@@ -9,7 +9,7 @@ import torch.utils.checkpoint
 
 import sdnq_amd
 from oracle import oracle as O
-from sdnq_amd import linear as LIN, lora, ops, training as T
+from sdnq_amd import linear as LIN, lora, ops
 from tests.test_lora_gpu import RANK, adapted, bits, randomize
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +52,8 @@ def composition(layer, x, dy, base, seed, offset):
     g_t = ops.lowrank_down(dy, up.t().contiguous())
     dq, qw = layer.sdnq_dequantizer, LIN._state(layer).qw
     had = dq.hadamard_group_size if dq.use_hadamard else 0
-    gi = ops.linear_float(dy, ops.weight_t(qw, dt, had, T._scratch(dev, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)), None)
+    two = [torch.empty(qw.n * qw.k, device=dev, dtype=dt) for _ in range(2)]          # buffers of the test's own, not the layer's scratch
+    gi = ops.linear_float(dy, ops.weight_t(qw, dt, had, two), None)
     gi = torch.where(keep, ops.lowrank_add(g_t, down.t().contiguous(), gi.clone(), sd), gi)
     return y, gi, ops.lowrank_grad(xm, g_t, sd, out_t=True), ops.lowrank_grad(dy, t, sd)
 

@@ -127,7 +127,8 @@ def test_outputs_and_gradients_within_the_derived_bound(name, m, gpu_device, mon
     # grad_input = linear_float(dY, W^T) + scale * g_t . down
     dq, qw = layer.sdnq_dequantizer, LIN._state(layer).qw
     had = dq.hadamard_group_size if dq.use_hadamard else 0
-    gi_base = ops.linear_float(dy, ops.weight_t(qw, dt, had, T._scratch(gpu_device, dt, qw.n * qw.k, bool(qw.desc.svd_up) or had != 0)), None)
+    two = [torch.empty(qw.n * qw.k, device=gpu_device, dtype=dt) for _ in range(2)]   # buffers of the test's own, not the layer's scratch
+    gi_base = ops.linear_float(dy, ops.weight_t(qw, dt, had, two), None)
     assert xg.grad.dtype == dt and xg.grad.shape == x.shape
     check(xg.grad, f64(gi_base) + scale * (gt64 @ down64), np.abs(f64(gi_base)) + abs(scale) * (np.abs(gt64) @ np.abs(down64)), RANK,
           (name, m, "grad_input"))

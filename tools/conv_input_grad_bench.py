@@ -80,8 +80,8 @@ def bench(out, iters, rounds):
                 finally:
                     training.CONV_GRAD_ROUTE = None
             gather()
-            scratch = training._scratch(DEV, torch.bfloat16, qw.n * qw.k, False)
-            ubuf = training._scratch_unfolded(DEV, torch.bfloat16, hw * hw * k * k * cout)
+            scratch = (sdnq_amd.scratch.take(DEV, "input-gradient scratch", 2 * qw.n * qw.k, "operand")[0].view(torch.bfloat16), None)
+            ubuf = sdnq_amd.scratch.take(DEV, "input-gradient scratch", 2 * hw * hw * k * k * cout, "unfolded")[0].view(torch.bfloat16)
 
             def route_b():
                 return col2im_route(qw, dy, cin, hw, k, s, p, scratch)

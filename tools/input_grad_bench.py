@@ -61,7 +61,7 @@ def bench(out, iters, rounds):
             qw = linear._state(layer).qw
             dy = torch.randn(m, n, device=DEV, dtype=torch.bfloat16, generator=g) * 0.01
             w_float = ops.dequant(qw, torch.bfloat16, 0)                      # [N, K], resident for (c)
-            scratch = training._scratch(DEV, torch.bfloat16, n * k, False)
+            scratch = (sdnq_amd.scratch.take(DEV, "input-gradient scratch", 2 * n * k, "operand")[0].view(torch.bfloat16), None)
 
             def backward():
                 return ops.linear_float(dy, ops.weight_t(qw, torch.bfloat16, 0, scratch), None)
