@@ -936,6 +936,53 @@ int sdnq_hip_lowrank_grad_dropout(const void* a, int64_t lda, const void* b, int
                                   int out_t, void* out, int out_dtype, void* workspace, int64_t workspace_bytes, int threshold,
                                   uint64_t seed, uint64_t offset, sdnq_stream_t stream);
 
+/* ---- DoRA (weight-decomposed LoRA, PEFT's use_dora) on the Linear adapters ---------------------------------------------------------------
+ * y = c . (W x + scale * up . (down . x)) + b with the column scale c[n] = magnitude[n] / || W[n,:] + scale * (up . down)[n,:] ||_2, the
+ * norm detached.  The caller computes c from normsq with [N]-sized float32 ops; these entry points are the passes over [N][K] and [M][N].
+ *
+ * sdnq_hip_dora_normsq: the squared row norms from the STORED CODES,
+ *     out[n] = sum_k e^2 ,  e = fmaf(scale, sum_r f32(up[n][r]) * f32(down[r][k]), w32[n][k])          all float32
+ *   w32 is the float32 value sdnq_hip_dequant(w, 0, .., SDNQ_F32) writes for a weight without SVD factors and without rotation, bit for
+ *   bit (every storage format, group and row scales, zero points, codebooks, a 16-bit scale_dtype).  Replaces PEFT's
+ *   `torch.linalg.norm(dequantize(weight) + scaling * lora_B @ lora_A, dim=1)`: the codes are read once, nothing of size N x K is written.
+ *   up [n][rank], down [rank][k] contiguous of `dtype` = SDNQ_BF16 / SDNQ_F16 (else SDNQ_ERR_DTYPE); up == down == NULL: no low-rank term,
+ *   out = || W[n,:] ||^2 (one of the two NULL: SDNQ_ERR_NULL).  The rank sum runs on v_mfma_f32_16x16x32 in rank steps of 32.  The order
+ *   of the float32 sum over k is a constant of the source (16 partial sums per row, one per 16-column run modulo 256, each ascending in k
+ *   by fmaf, added in ascending order): the same bits on every call, whatever the device or the grid.  One launch, no atomics, no
+ *   workspace, capturable.  k % 16 == 0, n % 8 == 0, rank % 8 == 0, 8 <= rank <= 256 (SDNQ_ERR_SHAPE); up, down 16-byte, out 4-byte aligned
+ *   (SDNQ_ERR_ALIGN); a descriptor with SVD factors: SDNQ_ERR_UNSUPPORTED (take the _dense form); the descriptor's own faults as
+ *   sdnq_hip_dequant_t reports them.  Everything is validated before the launch.
+ * sdnq_hip_dora_normsq_dense: the same kernel on a dense operand wd [n] rows of ldw elements (ldw >= k) of `dtype`, w32 = f32(wd[n][k]):
+ *   the route of layers with SVD factors or a Hadamard rotation, whose full weight sdnq_hip_dequant writes first (one more pass over the
+ *   weight).  wd and ldw * 2 bytes 16-byte aligned.
+ *
+ * sdnq_hip_lowrank_add_dora: sdnq_hip_lowrank_add with DoRA's epilogue, in place on y = the base layer's output z (bias included):
+ *     acc = sum_r f32(t[i][r]) * f32(up[j][r]) ;  y[i][j] = round_dtype( fmaf(c[j] * scale, acc, fmaf(c[j] - 1.0f, z - f32(bias[j]), z)) )
+ *   c[j] * scale and c[j] - 1.0f are one float32 operation each; bias NULL: 0.0f.  Where c[j] == 1.0f the inner term is z as read, and an
+ *   exactly zero acc stores the inner term rounded: with c == 1 every element is what sdnq_hip_lowrank_add stores, so a layer that has
+ *   never taken an optimizer step keeps the bits of the inference call.  Replaces PEFT's `mag_norm_scale * (base + scaling * lora_B(lora_A(x)))`.
+ *   c [n] float32, bias [n] of `dtype` or NULL, both 16-byte aligned (SDNQ_ERR_ALIGN); c NULL: SDNQ_ERR_NULL; shapes, launch forms and every
+ *   other status as sdnq_hip_lowrank_add.
+ *
+ * sdnq_hip_dora_bwd: one pass over dY (and the saved output y) for the backward,
+ *     g[i][j] = round_dtype( f32(dy[i][j]) * c[j] )                 [m][n] contiguous, the operand of the adapter's backward chain
+ *     q[j]    = sum_i f32(dy[i][j]) * ( f32(y[i][j]) - f32(bias[j]) )   float32; grad_c = q / c, since y - bias = c . u
+ *   Replaces `dY * mag_norm_scale` and `(dY * u).sum(0)`.  dy, y: [m] rows of lddy / ldy elements of `dtype`; q == NULL skips y and the
+ *   reduction (a frozen magnitude; y may then be NULL).  Deterministic as sdnq_hip_lowrank_grad: m is cut into slabs of 256 rows -- a
+ *   constant of the source -- each summed in float32 in a fixed order, and with more than one slab a second launch adds the slab sums in
+ *   ascending order.  No atomics; the same bits on every call; capturable.  workspace: sdnq_hip_dora_bwd_workspace_bytes(m, n) bytes (< 0:
+ *   SdnqStatus; 0 when m fits one slab or q == NULL, and NULL is then allowed), 16-byte aligned; a smaller one: SDNQ_ERR_SHAPE.  n % 8 == 0,
+ *   m > 0, at most 65535 slabs (SDNQ_ERR_SHAPE); dy, y, g, c, bias and the row strides 16-byte aligned (SDNQ_ERR_ALIGN). */
+int sdnq_hip_dora_normsq(const SdnqWeight* w, const void* up, const void* down, int dtype, int rank, float scale, float* out,
+                         sdnq_stream_t stream);
+int sdnq_hip_dora_normsq_dense(const void* wd, int dtype, int64_t n, int64_t k, int64_t ldw, const void* up, const void* down, int rank,
+                               float scale, float* out, sdnq_stream_t stream);
+int sdnq_hip_lowrank_add_dora(const void* t, const void* up, int dtype, int rank, float scale, void* y, int64_t m, int64_t n, int64_t ldy,
+                              const float* c, const void* bias, sdnq_stream_t stream);
+int64_t sdnq_hip_dora_bwd_workspace_bytes(int64_t m, int64_t n);
+int sdnq_hip_dora_bwd(const void* dy, int64_t lddy, const void* y, int64_t ldy, const void* bias, const float* c, int dtype, int64_t m,
+                      int64_t n, void* g, float* q, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 /* ---- trainable low-rank adapters on frozen quantized Conv1d / Conv2d layers ----------------------------------------------------------------
  * PEFT's conv adapter: lora_A is a conv with the layer's kernel, stride, padding and dilation from C_in to `rank` channels, lora_B a 1 x 1
  * conv from `rank` to C_out.  With U = im2col(x) [B OH OW][C kh kw] (sdnq_hip_im2col) the down projection is U . down^T and the gradient of

@@ -1,8 +1,11 @@
 // lowrank_add_kernel of lowrank_train.hip (its header comment is there) and its dropout form: the epilogue's 8 columns of a lane
 // are one 16-byte chunk of y, and one Philox call (philox_dev.h) says which of them take the adapter's term.
-// No include guard: the unit includes this file twice, with LR_DROP 0 (the plain kernel, whose text -- and therefore whose code -- is what it
-// was before the mask existed) and with LR_DROP 1 (the _dropout kernel: five more arguments and the lines between #if LR_DROP).
-#if LR_DROP
+// No include guard: the unit includes this file once per form, with LR_DROP 0 (the plain kernel, whose text -- and therefore whose code -- is
+// what it was before the mask existed), with LR_DROP 1 (the _dropout kernel: five more arguments and the lines between #if LR_DROP) and
+// with LR_DORA 1 (sdnq_hip_lowrank_add_dora: the magnitude column scale c [N] and the bias as two more arguments, and its own epilogue).
+#if LR_DORA
+#define LR_KERNEL lowrank_add_dora_kernel
+#elif LR_DROP
 #define LR_KERNEL lowrank_add_dropout_kernel
 #else
 #define LR_KERNEL lowrank_add_kernel
@@ -14,7 +17,13 @@ __global__ __launch_bounds__(256) void LR_KERNEL(const uint16_t* __restrict__ t,
 #if LR_DROP
     , u32 thr, u32 seed_lo, u32 seed_hi, u32 off_lo, u32 off_hi
 #endif
+#if LR_DORA
+    , const float* __restrict__ cvec, const uint16_t* __restrict__ bias
+#endif
 ) {
+#if LR_DORA
+    SDNQ_KERNARGS_NOW("s"(cvec), "s"(bias));
+#endif
 #if LR_DROP
     SDNQ_KERNARGS_NOW("s"(thr), "s"(seed_lo), "s"(seed_hi), "s"(off_lo), "s"(off_hi));
     const DropArgs drop = {thr, seed_lo, seed_hi, off_lo, off_hi};
@@ -82,12 +91,31 @@ __global__ __launch_bounds__(256) void LR_KERNEL(const uint16_t* __restrict__ t,
                     }
                 }
 #endif
+#if LR_DORA
+                // DoRA: y = c (u + scale acc) + b from the stored z = u + b, as round(fmaf(c scale, acc, fmaf(c - 1, z - b, z))).  With
+                // c == 1 the inner term IS z (kept as read, so that a -0.0 or an infinity is not touched by 0 * (z - b)) and the store is the
+                // plain kernel's below, its exactly-zero-sum rule included: a fresh adapter leaves every bit of y alone
+                {
+                    float cj[8], bj[8];
+                    Vec16<SDNQ_F32>::unpack(*(const uint4*)(cvec + n), cj);
+                    Vec16<SDNQ_F32>::unpack(*(const uint4*)(cvec + n + 4), cj + 4);
+                    if (bias) Vec16<T_ID>::unpack(*(const uint4*)(bias + n), bj);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        if (!bias) bj[e] = 0.0f;
+                        const float a = acc[r][c][e >> 2][e & 3], cm1 = cj[e] - 1.0f, cs = cj[e] * scale;
+                        const float inner = cm1 == 0.0f ? f[e] : fmaf(cm1, f[e] - bj[e], f[e]);
+                        f[e] = a == 0.0f ? inner : fmaf(cs, a, inner);
+                    }
+                }
+#else
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {  // a sum that is exactly zero leaves the element as it is: fmaf(scale, +0, -0.0) is +0.0
                     const float a0 = acc[r][c][0][e], a1 = acc[r][c][1][e];
                     f[e] = a0 == 0.0f ? f[e] : fmaf(scale, a0, f[e]);
                     f[4 + e] = a1 == 0.0f ? f[4 + e] : fmaf(scale, a1, f[4 + e]);
                 }
+#endif
                 *p = Vec16<T_ID>::pack(f);
             }
         }

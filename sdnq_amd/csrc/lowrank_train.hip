@@ -39,14 +39,22 @@ namespace {
 constexpr int LRG_SLAB = 256;  // rows of M per partial sum of sdnq_hip_lowrank_grad (tests/lora_util.py restates it)
 
 // The kernels' text lives in lowrank_add_kernel.h and lowrank_grad_kernel.h, each included once per form: the plain kernel (LR_DROP 0) and
-// the _dropout one (LR_DROP 1: sdnq_hip_lowrank_add_dropout, sdnq_hip_lowrank_grad_dropout).
+// the _dropout one (LR_DROP 1: sdnq_hip_lowrank_add_dropout, sdnq_hip_lowrank_grad_dropout); the add kernel a third time for DoRA's
+// epilogue (LR_DORA 1: sdnq_hip_lowrank_add_dora).
 // ---- y += scale * t . up^T ------------------------------------------------------------------------------------------------------------
+#define LR_DORA 0
 #define LR_DROP 0
 #include "lowrank_add_kernel.h"
 #undef LR_DROP
 #define LR_DROP 1
 #include "lowrank_add_kernel.h"
 #undef LR_DROP
+#undef LR_DORA
+#define LR_DORA 1
+#define LR_DROP 0
+#include "lowrank_add_kernel.h"
+#undef LR_DROP
+#undef LR_DORA
 
 // ---- out = scale * a^T . b ------------------------------------------------------------------------------------------------------------
 #define LR_DROP 0
@@ -58,14 +66,15 @@ constexpr int LRG_SLAB = 256;  // rows of M per partial sum of sdnq_hip_lowrank_
 
 }  // namespace
 
-// drop == nullptr: the plain kernels
+// drop == nullptr: the plain kernels; c != nullptr: the DoRA epilogue (no mask: its dropout lives in t)
 static int lowrank_add_launch(const void* t, const void* up, int dtype, int rank, float scale, void* y, int64_t m, int64_t n, int64_t ldy,
-                              const DropArgs* drop, sdnq_stream_t stream) {
+                              const DropArgs* drop, sdnq_stream_t stream, const float* c = nullptr, const void* bias = nullptr) {
     if (!t || !up || !y) return SDNQ_ERR_NULL;
     if (dtype != SDNQ_BF16 && dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;
     if (m <= 0 || n <= 0 || ldy < n || (n % 8) != 0 || rank < 8 || rank > 256 || (rank % 8) != 0) return SDNQ_ERR_SHAPE;
     if (drop && (drop->thr < 1u || drop->thr > 65535u)) return SDNQ_ERR_SHAPE;  // (a negative threshold arrives as a large unsigned one)
     if (((uintptr_t)t % 16) || ((uintptr_t)up % 16) || ((uintptr_t)y % 16) || ((ldy * 2) % 16)) return SDNQ_ERR_ALIGN;
+    if (((uintptr_t)c % 16) || ((uintptr_t)bias % 16)) return SDNQ_ERR_ALIGN;
     // two row tiles per wave halve the fragment loads of up per element of y; taken once the launch still has two workgroups per CU
     const int64_t gx = (n + 127) / 128;
     const bool two = gx * ((m + 127) / 128) >= 512;
@@ -80,7 +89,14 @@ static int lowrank_add_launch(const void* t, const void* up, int dtype, int rank
         hipLaunchKernelGGL(kern, grid, block, 0, s, (const uint16_t*)t, (const uint16_t*)up, (uint16_t*)y, m, n, ldy, rank, scale, drop->thr,
                            drop->seed_lo, drop->seed_hi, drop->off_lo, drop->off_hi);
     };
-    if (drop) {
+    auto launch_dora = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, 0, s, (const uint16_t*)t, (const uint16_t*)up, (uint16_t*)y, m, n, ldy, rank, scale, c,
+                           (const uint16_t*)bias);
+    };
+    if (c) {
+        if (dtype == SDNQ_BF16) { if (two) launch_dora(lowrank_add_dora_kernel<SDNQ_BF16, 2>); else launch_dora(lowrank_add_dora_kernel<SDNQ_BF16, 1>); }
+        else { if (two) launch_dora(lowrank_add_dora_kernel<SDNQ_F16, 2>); else launch_dora(lowrank_add_dora_kernel<SDNQ_F16, 1>); }
+    } else if (drop) {
         if (dtype == SDNQ_BF16) { if (two) launch_drop(lowrank_add_dropout_kernel<SDNQ_BF16, 2>); else launch_drop(lowrank_add_dropout_kernel<SDNQ_BF16, 1>); }
         else { if (two) launch_drop(lowrank_add_dropout_kernel<SDNQ_F16, 2>); else launch_drop(lowrank_add_dropout_kernel<SDNQ_F16, 1>); }
     } else if (dtype == SDNQ_BF16) { if (two) launch(lowrank_add_kernel<SDNQ_BF16, 2>); else launch(lowrank_add_kernel<SDNQ_BF16, 1>); }
@@ -98,6 +114,12 @@ extern "C" int sdnq_hip_lowrank_add_dropout(const void* t, const void* up, int d
                                             int64_t ldy, int threshold, uint64_t seed, uint64_t offset, sdnq_stream_t stream) {
     const DropArgs drop = {(u32)threshold, (u32)seed, (u32)(seed >> 32), (u32)offset, (u32)(offset >> 32)};
     return lowrank_add_launch(t, up, dtype, rank, scale, y, m, n, ldy, &drop, stream);
+}
+
+extern "C" int sdnq_hip_lowrank_add_dora(const void* t, const void* up, int dtype, int rank, float scale, void* y, int64_t m, int64_t n,
+                                         int64_t ldy, const float* c, const void* bias, sdnq_stream_t stream) {
+    if (!c) return SDNQ_ERR_NULL;
+    return lowrank_add_launch(t, up, dtype, rank, scale, y, m, n, ldy, nullptr, stream, c, bias);
 }
 
 extern "C" int64_t sdnq_hip_lowrank_grad_workspace_bytes(int64_t m, int64_t p, int rank) {

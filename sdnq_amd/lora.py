@@ -62,8 +62,35 @@ a 1 x 1 conv from rank to C_out (``lora_up`` [C_out, rank, 1(, 1)]).  With L = H
                                                                more) elsewhere: _conv_adapter_grad_input
                  grad_bias  = dY.sum over batch and space
 
+``add_lora(model, use_dora=True)`` is PEFT's ``use_dora`` (weight-decomposed LoRA) on the Linear adapters.  Each adapted layer gets a
+trainable magnitude ``lora_magnitude`` m [N] (float32), and with W [N][K] the weight the layer's forward multiplies by (what ``ops.dequant``
+returns: SVD product added, Hadamard rotation undone), s = lora_scale:
+
+    normsq[n] = sum_k ( W[n][k] + s * sum_r up[n][r] down[r][k] )^2    ops.dora_normsq: float32, from the STORED CODES in one launch -- each
+                                                                       e = fma(s, acc, w32), the rank sum on the matrix cores, no [N][K]
+                                                                       tensor; DETACHED, as PEFT's weight_norm.  Always s, never the
+                                                                       dropout scale or a mask (PEFT's lora_weight is B @ A).  A layer with
+                                                                       SVD factors or a rotation: ops.dequant into the "decoded" scratch slot
+                                                                       + ops.dora_normsq_dense (one more pass over the weight)
+    c[n]      = m[n] / sqrt(normsq[n])                                 torch ops on [N]: autograd turns grad_c into grad_m
+    y         = c * ( W x + s_d * up (down (mask * x)) ) + b           the layer's own route, ops.lowrank_down(_dropout), then
+                                                                       ops.lowrank_add_dora in place: with z the base output and acc = t . up^T,
+                                                                       y = round(fma(c s_d, acc, fma(c - 1, z - b, z))), c s_d and c - 1 one
+                                                                       float32 operation each
+    backward  g = round(dY * c), q[n] = sum_i dY[i][n] (y[i][n] - b[n])   ops.dora_bwd: one pass over dY and the SAVED OUTPUT y (y - b = c * u;
+                                                                       slabs of 256 rows in a fixed order, no atomics)
+              grad_c = q / c where c != 0, else 0                      a magnitude entry that is exactly zero gets gradient 0
+              g_t, grad_input, grad_up, grad_down                      the chain above with g in place of dY (dropout variants included)
+              grad_bias = dY.sum(0)                                    the unscaled dY
+
+m is initialised to sqrt(normsq) by the same kernel (up == 0: || W[n,:] ||), so c == 1.0f exactly and a layer that has never taken an
+optimizer step returns the bits of the inference call.  normsq is recomputed on every call and never cached: ``sdnq_amd.optim`` writes the
+parameters through raw pointers without bumping ``_version``.  The wrapper runs the same three kernels under ``torch.no_grad()`` / ``eval()``.
+Measured (tools/dora_bench.py, profiles/dora_bench.jsonl): see README.md.
+
 Not built, each raising or listed with its sentence: adapters on grouped and 3-D convs, on transposed-conv and embedding layers and on float32
-layers, on convs with string padding or a padding mode other than zeros; dropout on conv adapters; per-layer ranks, DoRA / rsLoRA; merging the adapter into the
+layers, on convs with string padding or a padding mode other than zeros; dropout on conv adapters; DoRA on conv adapters, caching the norm of
+frozen adapters; per-layer ranks, rsLoRA; merging the adapter into the
 stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque whole-layer operator: the values of adapter
 inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper calls the base forward, which keeps its
 plan); a batched (single-launch) NCHW add of the conv adapter's up projection (one ops.lowrank_add launch per image).
@@ -75,7 +102,7 @@ import math
 
 import torch
 
-from . import _lib, ops, scratch, training
+from . import _lib, linear, ops, scratch, training
 from .linear import _attr
 
 _DTYPES = (torch.bfloat16, torch.float16)
@@ -134,9 +161,10 @@ def _scale(layer, drop) -> float:
     return layer.lora_scale if drop is None else dropout_scale(layer.lora_scale, drop[2])
 
 
-def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor, drop=None):
+def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor, drop=None, dora=None):
     """(y, x2d, t): the three steps of the forward with gradients off.  down / up: the factors in the layer dtype.  drop: None or the
-    (seed, offset, T) of _draw_dropout -- then t comes from the masked x and the scale carries 1 / (1 - p)."""
+    (seed, offset, T) of _draw_dropout -- then t comes from the masked x and the scale carries 1 / (1 - p).  dora: None or (c [N] float32,
+    bias in the layer dtype | None) -- then the add is ops.lowrank_add_dora."""
     y = base(layer, input)
     x2d = training._rows(input)
     n = up.shape[0]
@@ -153,7 +181,10 @@ def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor,
     if y2d.stride(1) != 1 or ld < n or y2d.data_ptr() % 16 or (ld * y2d.element_size()) % 16:
         y = y.clone(memory_format=torch.contiguous_format)
         y2d = y.view(-1, n)
-    ops.lowrank_add(t, up, y2d, _scale(layer, drop))
+    if dora is None:
+        ops.lowrank_add(t, up, y2d, _scale(layer, drop))
+    else:
+        ops.lowrank_add_dora(t, up, y2d, _scale(layer, drop), *dora)
     return y, x2d, t
 
 
@@ -213,6 +244,127 @@ class QuantizedLinearLoRA(torch.autograd.Function):
         if need_bias:
             grad_bias = g2d.sum(0).to(ctx.bias_dtype)
         return None, None, grad_input, grad_down, grad_up, grad_bias
+
+
+# ---- DoRA (add_lora(..., use_dora=True)) ------------------------------------------------------------------------------------------------
+def _layer_normsq(layer, down, up) -> torch.Tensor:
+    """normsq [N] float32 of a Linear layer: sum_k (W[n][k] + lora_scale * (up . down)[n][k])^2 -- down / up in the layer dtype, or both None
+    for || W[n,:] ||^2.  A plain layer: ops.dora_normsq on the stored codes.  A layer with SVD factors or a Hadamard rotation: ops.dequant
+    into the "decoded" slot of sdnq_amd.scratch and ops.dora_normsq_dense on it (one more pass over the weight)."""
+    qw = linear._state(layer).qw
+    dq = layer.sdnq_dequantizer
+    had = dq.hadamard_group_size if dq.use_hadamard else 0
+    scale = layer.lora_scale if up is not None else 1.0  # (without factors the scale multiplies nothing)
+    if not qw.desc.svd_up and not had:
+        return ops.dora_normsq(qw, up, down, scale)
+    dt = dq.result_dtype
+    nk = qw.n * qw.k
+    _, decoded = training._scratch(qw.keep[0].device, dt, nk, True)
+    return ops.dora_normsq_dense(ops.dequant(qw, dt, had, out=decoded[:nk].view(qw.n, qw.k)), up, down, scale)
+
+
+def _dora_bias(bias, dt: torch.dtype):
+    """The bias as the DoRA kernels read it: the layer dtype, contiguous, 16-byte aligned (None stays None)."""
+    if bias is None:
+        return None
+    b = bias.detach().to(dt).contiguous()
+    return b.clone() if b.data_ptr() % 16 else b
+
+
+def _dora_c(layer, down: torch.Tensor, up: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
+    """c [N] float32 = lora_magnitude / sqrt(normsq), normsq recomputed by the norm kernel on every call and detached (PEFT's
+    weight_norm.detach()): plain torch ops on [N], so autograd turns grad_c into the gradient of the magnitude."""
+    with torch.no_grad():
+        normsq = _layer_normsq(layer, down.detach().to(dt), up.detach().to(dt))
+    return _attr(layer, "lora_magnitude") / torch.sqrt(normsq)
+
+
+class QuantizedLinearDoRA(torch.autograd.Function):
+    """y = c . (W x + scale * up . (down . x)) + b with a graph, c [N] float32 an INPUT (the wrapper computes it from lora_magnitude and the
+    detached norm): gradients for the input, the two factors, c and the bias.  Saves x2d, t, down, up, c, the OUTPUT y and the bias; the
+    backward recovers c . u = y - b from the saved output (the op that consumes y usually saves the same tensor), so
+        g      = round(dY * c),  q[n] = sum_i dY[i][n] (y[i][n] - b[n])        ops.dora_bwd, one pass
+        grad_c = q / c where c != 0, else 0                                    (a magnitude entry that is exactly zero gets gradient 0)
+        g_t, grad_input, grad_up, grad_down: QuantizedLinearLoRA's chain on g (dropout variants included)
+        grad_bias = dY.sum(0)                                                  the unscaled dY
+    Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, layer, base, input, down, up, c, bias=None):
+        dt = _check_call(layer, input)
+        ctx.drop = drop = _draw_dropout(layer, input.device)
+        with torch.no_grad():
+            c32 = c.detach().contiguous()
+            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), drop, (c32, _dora_bias(bias, dt)))
+        ctx.layer, ctx.input_shape = layer, input.shape
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x2d, t, down, up, c32, y, *(() if bias is None else (bias,)))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        layer = ctx.layer
+        dq = layer.sdnq_dequantizer
+        x2d, t, down, up, c, y = ctx.saved_tensors[:6]
+        bias = ctx.saved_tensors[6] if ctx.has_bias else None
+        if grad_output.dtype != dq.result_dtype:
+            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
+                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
+        if not grad_output.is_cuda:
+            raise _lib.SdnqHipError("gradients through a quantized Linear with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
+        dy2d = training._rows(grad_output)
+        drop = ctx.drop
+        dt, scale = dy2d.dtype, _scale(layer, drop)
+        _, _, need_x, need_down, need_up, need_c, need_bias = ctx.needs_input_grad
+        grad_input = grad_down = grad_up = grad_c = grad_bias = None
+        m, n = dy2d.shape
+        if m == 0:
+            if need_x:
+                grad_input = grad_output.new_zeros(ctx.input_shape)
+            grad_down = torch.zeros_like(down) if need_down else None
+            grad_up = torch.zeros_like(up) if need_up else None
+            grad_c = torch.zeros_like(c) if need_c else None
+        else:
+            ws = _workspace(dy2d.device, ops.dora_bwd_workspace_bytes(m, n)) if need_c else None
+            g2d, q = ops.dora_bwd(dy2d, training._rows(y) if need_c else None, _dora_bias(bias, dt), c, want_q=need_c, workspace=ws)
+            if need_c:
+                grad_c = torch.where(c != 0, q / c, torch.zeros_like(q))
+            g_t = None
+            if need_x or need_down:
+                g_t = ops.lowrank_down(g2d, up.to(dt).t().contiguous())
+            if need_x:
+                gi2d = training._linear_base_grad(layer, g2d)
+                if drop is None:
+                    ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
+                else:
+                    ops.lowrank_add_dropout(g_t, down.to(dt).t().contiguous(), gi2d, scale, drop[2], drop[0], drop[1])
+                grad_input = gi2d.view(ctx.input_shape)
+            if need_up:
+                grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
+            if need_down:
+                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype, drop)
+        if need_bias:
+            grad_bias = dy2d.sum(0).to(ctx.bias_dtype)
+        return None, None, grad_input, grad_down, grad_up, grad_c, grad_bias
+
+
+def _with_dora(base, previous):
+    grad_on = torch.is_grad_enabled
+
+    def forward(self, input):
+        down, up, mag = _attr(self, "lora_down"), _attr(self, "lora_up"), _attr(self, "lora_magnitude")
+        dt = _check_call(self, input)
+        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad or mag.requires_grad):
+            return QuantizedLinearDoRA.apply(self, base, input, down, up, _dora_c(self, down, up, dt), _attr(self, "bias"))
+        with torch.no_grad():
+            c = _dora_c(self, down, up, dt).contiguous()
+            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(self, input.device),
+                        (c, _dora_bias(_attr(self, "bias"), dt)))[0]
+    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_dora"
+    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
+    return forward
 
 
 # ---- the same on frozen quantized Conv1d / Conv2d layers (add_lora(..., convs=True)) ----------------------------------------------------
@@ -448,7 +600,7 @@ def _selected(targets):
 
 
 def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None, targets=None, dtype: torch.dtype | None = None,
-             seed: int | None = None, convs: bool = False, dropout: float = 0.0) -> LoRAResult:
+             seed: int | None = None, convs: bool = False, dropout: float = 0.0, use_dora: bool = False) -> LoRAResult:
     """Put a trainable rank-`rank` adapter on every accelerated quantized Linear of `model` whose qualified name `targets` selects
     (None: all; a list of substrings; or a predicate on the name).
 
@@ -473,13 +625,26 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
     input in training mode, fused into the adapter kernels (module docstring): the effective probability is
     ``dropout_threshold(dropout) / 65536``; each call draws (seed, offset) from torch's device generator, so ``torch.cuda.manual_seed``
     reproduces a run and ``torch.utils.checkpoint``, which restores the generator state, recomputes with the same mask.  0.0, the
-    default, changes nothing.  With ``convs=True`` a dropout > 0 raises NotImplementedError before any module is touched."""
+    default, changes nothing.  With ``convs=True`` a dropout > 0 raises NotImplementedError before any module is touched.
+
+    ``use_dora=True`` is PEFT's ``use_dora`` (weight-decomposed LoRA; module docstring): every adapted Linear also gets
+    ``module.lora_magnitude`` [N] -- ALWAYS float32, whatever `dtype` says (a 16-bit magnitude would lose c == 1 at initialisation) --
+    initialised to || W[n,:] || by the norm kernel itself, appended to ``.parameters`` after the layer's lora_down and lora_up, and
+    ``module.lora_dora = True``.  The norm is recomputed by the kernel on EVERY call, never cached: ``sdnq_amd.optim`` updates parameters
+    through raw pointers without bumping ``_version``, so a cache keyed on the factors would go stale silently (caching for frozen adapters
+    is not built).  A layer with an all-zero weight row (norm 0) is listed in ``.skipped`` and gets no adapter.  A magnitude entry that is
+    exactly zero makes u unrecoverable from the saved output: its gradient is reported as 0.  With ``convs=True`` it raises
+    NotImplementedError before any module is touched.  False, the default, runs exactly the code and entry points of plain LoRA."""
     dropout = float(dropout)
     if not 0.0 <= dropout < 1.0:
         raise ValueError(f"add_lora: 0 <= dropout < 1 (got dropout = {dropout})")
     if convs and dropout > 0.0:
         raise NotImplementedError("add_lora: dropout on conv adapters is not built (the conv adapter kernels have no mask); call "
                                   "add_lora(..., convs=True) with dropout=0, or add_lora(..., dropout=p) for the Linear layers alone")
+    if convs and use_dora:
+        raise NotImplementedError("add_lora: DoRA on conv adapters is not built (the norm kernel reads Linear weights, the conv add has no "
+                                  "column-scale epilogue); call add_lora(..., convs=True) with use_dora=False, or add_lora(..., "
+                                  "use_dora=True) for the Linear layers alone")
     if rank % 8 or not 8 <= rank <= 256:
         raise ValueError(f"add_lora: rank % 8 == 0 and 8 <= rank <= 256 (got rank = {rank}): the adapter kernels move 16-byte rank chunks")
     if dtype is not None and dtype not in (torch.float32, *_DTYPES):
@@ -510,6 +675,13 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
             down_shape, up_shape = (rank, k), (n, rank)
         pdt = dq.result_dtype if dtype is None else dtype
         dev = module.weight.device
+        magnitude = None
+        if use_dora:  # the initial magnitude comes from the kernel every forward runs: c == 1.0f exactly until a parameter moves
+            magnitude = torch.sqrt(_layer_normsq(module, None, None).detach().to(torch.float32))
+            if not bool((magnitude > 0).all()):
+                skipped.append((name or type(module).__name__, "DoRA needs a non-zero norm of every weight row (the layer has an all-zero "
+                                                                "row: magnitude / norm is undefined there)"))
+                continue
         bound = 1.0 / math.sqrt(k)  # kaiming_uniform_(a = sqrt(5)) on fan_in = K (C_in * prod(kernel)): sqrt(6 / ((1 + 5) K))
         down = torch.empty(down_shape, dtype=torch.float32).uniform_(-bound, bound, generator=gen)
         module.lora_down = torch.nn.Parameter(down.to(device=dev, dtype=pdt))
@@ -517,9 +689,14 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
         module.lora_scale = scale
         module.lora_dropout = dropout
         fwd = module.forward_func
-        module.forward_func = (_with_conv_lora if conv else _with_lora)(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
+        wrap = _with_conv_lora if conv else (_with_dora if use_dora else _with_lora)
+        module.forward_func = wrap(getattr(fwd, "_sdnq_inference_forward", None) or fwd, fwd)
         _refresh_compile_plan(module)
         params += [module.lora_down, module.lora_up]
+        if use_dora:
+            module.lora_magnitude = torch.nn.Parameter(magnitude.to(dev))
+            module.lora_dora = True
+            params.append(module.lora_magnitude)
         added += 1
     if skipped:
         import warnings
@@ -536,8 +713,8 @@ def _lora_modules(model: torch.nn.Module):
 
 def remove_lora(model: torch.nn.Module) -> int:
     """Take the adapters off: every layer gets back the very forward it had before `add_lora` and loses lora_down, lora_up,
-    lora_scale and lora_dropout.  A layer whose forward was re-pointed after `add_lora` (see there) keeps the forward it has now and
-    loses the four attributes.  Returns the number of layers changed."""
+    lora_scale and lora_dropout (a DoRA layer lora_magnitude and lora_dora as well).  A layer whose forward was re-pointed after
+    `add_lora` (see there) keeps the forward it has now and loses the attributes.  Returns the number of layers changed."""
     count = 0
     for module in list(model.modules()):
         wrapped = getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None
@@ -546,7 +723,7 @@ def remove_lora(model: torch.nn.Module) -> int:
         if wrapped:
             module.forward_func = module.forward_func._sdnq_lora_previous
             _refresh_compile_plan(module)
-        for attr in ("lora_down", "lora_up", "lora_scale", "lora_dropout"):
+        for attr in ("lora_down", "lora_up", "lora_scale", "lora_dropout", "lora_magnitude", "lora_dora"):
             if hasattr(module, attr):
                 delattr(module, attr)
         count += 1
@@ -558,35 +735,53 @@ _PEFT_PREFIX = "base_model.model."
 
 def lora_state_dict(model: torch.nn.Module) -> dict:
     """The adapters under PEFT's key names: ``<module>.lora_A.weight`` [rank, K] (lora_down) and ``<module>.lora_B.weight`` [N, rank]
-    (lora_up) -- on a conv layer [rank, C_in, *kernel] and [C_out, rank, 1(, 1)] -- detached.  alpha is not a tensor: PEFT keeps it in its config, here it is the `alpha` of `add_lora`."""
+    (lora_up) -- on a conv layer [rank, C_in, *kernel] and [C_out, rank, 1(, 1)] -- detached.  alpha is not a tensor: PEFT keeps it in its config, here it is the `alpha` of `add_lora`.
+    A DoRA layer adds ``<module>.lora_magnitude_vector.weight`` [N] float32 (lora_magnitude)."""
     sd = {}
     for name, module in _lora_modules(model):
         sd[f"{name}.lora_A.weight"] = module.lora_down.detach()
         sd[f"{name}.lora_B.weight"] = module.lora_up.detach()
+        if getattr(module, "lora_dora", False):
+            sd[f"{name}.lora_magnitude_vector.weight"] = module.lora_magnitude.detach()
     return sd
 
 
 def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
     """Copy `sd` (the keys of `lora_state_dict`; a leading ``base_model.model.`` and an adapter name as in ``lora_A.default.weight`` are
     accepted) into the adapters `add_lora` put on `model`.  Every layer with an adapter must find both its keys and every key its layer,
-    with the shapes of the registered parameters: KeyError / ValueError otherwise.  Returns the number of layers loaded."""
+    with the shapes of the registered parameters: KeyError / ValueError otherwise.  A DoRA layer needs its magnitude as well, as
+    ``<module>.lora_magnitude_vector.weight``, PEFT's ``lora_magnitude_vector.<adapter>.weight`` or the bare ``lora_magnitude_vector.<adapter>``;
+    a magnitude key for a layer without DoRA is a KeyError, as any unknown key.  Returns the number of layers loaded."""
     import re
     found = {}
     for key, value in sd.items():
-        m = re.fullmatch(r"(.*)\.lora_([AB])(?:\.[^.]+)?\.weight", key[len(_PEFT_PREFIX):] if key.startswith(_PEFT_PREFIX) else key)
-        if m is None:
-            raise KeyError(f"load_lora_state_dict: {key!r} is not a <module>.lora_A.weight / <module>.lora_B.weight key")
+        bare = key[len(_PEFT_PREFIX):] if key.startswith(_PEFT_PREFIX) else key
+        m = re.fullmatch(r"(.*)\.lora_([AB])(?:\.[^.]+)?\.weight", bare)
+        if m is None:  # DoRA's magnitude: .weight, .<adapter>.weight, or the bare .<adapter> of older PEFT files
+            mm = re.fullmatch(r"(.*)\.lora_magnitude_vector(?:\.weight|\.[^.]+\.weight|\.[^.]+)", bare)
+            if mm is None:
+                raise KeyError(f"load_lora_state_dict: {key!r} is not a <module>.lora_A.weight / <module>.lora_B.weight key")
+            found.setdefault(mm.group(1), {})["M"] = value
+            continue
         found.setdefault(m.group(1), {})[m.group(2)] = value
     mods = dict(_lora_modules(model))
     missing = [n for n in found if n not in mods]
     if missing:
         raise KeyError(f"load_lora_state_dict: no adapter on {missing[:4]} (add_lora(model) registers them first)")
+    stray = [n for n, got in found.items() if "M" in got and not getattr(mods[n], "lora_dora", False)]
+    if stray:
+        raise KeyError(f"load_lora_state_dict: a lora_magnitude_vector key for {stray[:4]}, which carry no DoRA magnitude "
+                       "(add_lora(model, use_dora=True) registers it)")
     count = 0
     for name, module in mods.items():
         got = found.get(name, {})
-        if set(got) != {"A", "B"}:
+        dora = bool(getattr(module, "lora_dora", False))
+        if not {"A", "B"} <= set(got):
             raise KeyError(f"load_lora_state_dict: {name} needs both lora_A.weight and lora_B.weight (got {sorted(got)})")
-        for p, v, what in ((module.lora_down, got["A"], "lora_A"), (module.lora_up, got["B"], "lora_B")):
+        if dora and "M" not in got:
+            raise KeyError(f"load_lora_state_dict: {name} is a DoRA layer and needs lora_magnitude_vector.weight as well (got {sorted(got)})")
+        for p, v, what in ((module.lora_down, got["A"], "lora_A"), (module.lora_up, got["B"], "lora_B"),
+                           *(((module.lora_magnitude, got["M"], "lora_magnitude_vector"),) if dora else ())):
             if tuple(v.shape) != tuple(p.shape):
                 raise ValueError(f"load_lora_state_dict: {name}.{what}.weight has shape {tuple(v.shape)}, the adapter {tuple(p.shape)}")
             with torch.no_grad():

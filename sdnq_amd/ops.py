@@ -1186,6 +1186,123 @@ def lowrank_grad_dropout(a: torch.Tensor, b: torch.Tensor, scale: float, thresho
     return _lowrank_grad("lowrank_grad_dropout", a, b, scale, out_t, out_dtype, workspace, (threshold, seed, offset))
 
 
+# ---- DoRA on the Linear adapters (include/sdnq_hip.h has the arithmetic) ---------------------------------------------------------------------
+def _dora_factors(what: str, n: int, k: int, up, down):
+    """(rank, dtype code | None) of the optional factors up [N, R] / down [R, K] of the norm entry points."""
+    if (up is None) != (down is None):
+        raise _lib.SdnqHipError(f"{what}: up and down come together (both or neither)")
+    if n % 8 or k % 16:
+        raise _lib.SdnqHipError(f"{what}: n % 8 == 0 and k % 16 == 0 (got n = {n}, k = {k})")
+    if up is None:
+        return 0, None
+    if up.ndim != 2 or down.ndim != 2:
+        raise _lib.SdnqHipError(f"{what}: up and down must be 2-D (got {tuple(up.shape)}, {tuple(down.shape)})")
+    r = up.shape[1]
+    _lowrank_check(what, r, up=up, down=down)
+    if tuple(up.shape) != (n, r) or tuple(down.shape) != (r, k):
+        raise _lib.SdnqHipError(f"{what}: up [N, R] and down [R, K] for a weight [{n}, {k}] (got {tuple(up.shape)}, {tuple(down.shape)})")
+    if not up.is_contiguous() or not down.is_contiguous():
+        raise _lib.SdnqHipError(f"{what}: up and down must be contiguous")
+    return r, float_code(up.dtype)
+
+
+def dora_normsq(qw: QuantWeight, up: torch.Tensor | None = None, down: torch.Tensor | None = None, scale: float = 1.0) -> torch.Tensor:
+    """sdnq_hip_dora_normsq: out [N] float32 = sum_k (w32[n][k] + scale * (up @ down)[n][k])^2 from the stored codes of `qw` (no SVD
+    factors), each element e = fma(scale, acc, w32) in float32 with the rank sum on the matrix cores; up [N, R] / down [R, K] contiguous,
+    bfloat16 / float16, or both None for the plain squared row norms.  One launch, no [N, K] tensor, the same bits on every call."""
+    r, code = _dora_factors("dora_normsq", qw.n, qw.k, up, down)
+    dev = qw.keep[0].device
+    _require_cuda(qw.keep[0], up, down)
+    out = torch.empty(qw.n, device=dev, dtype=torch.float32)
+    check(_lib.load().sdnq_hip_dora_normsq(ctypes.byref(qw.desc), _ptr(up), _ptr(down), BF16 if code is None else code, r, float(scale),
+                                           out.data_ptr(), _stream(out)), "dora_normsq")
+    return out
+
+
+def dora_normsq_dense(wd: torch.Tensor, up: torch.Tensor | None = None, down: torch.Tensor | None = None, scale: float = 1.0) -> torch.Tensor:
+    """sdnq_hip_dora_normsq_dense: ``dora_normsq`` on a dense weight wd [N, K] (bfloat16 / float16, unit column stride, 16-byte aligned
+    rows) of the factors' dtype: the route of layers with SVD factors or a Hadamard rotation, on what ``dequant`` wrote."""
+    if wd.ndim != 2:
+        raise _lib.SdnqHipError(f"dora_normsq_dense: wd must be 2-D (got {tuple(wd.shape)})")
+    n, k = wd.shape
+    r, _ = _dora_factors("dora_normsq_dense", n, k, up, down)
+    _lowrank_check("dora_normsq_dense", r or 8, wd=wd, **({} if up is None else {"up": up}))
+    _require_cuda(wd, up, down)
+    out = torch.empty(n, device=wd.device, dtype=torch.float32)
+    check(_lib.load().sdnq_hip_dora_normsq_dense(wd.data_ptr(), float_code(wd.dtype), n, k, _ld(wd), _ptr(up), _ptr(down), r, float(scale),
+                                                 out.data_ptr(), _stream(out)), "dora_normsq_dense")
+    return out
+
+
+def _dora_vectors(what: str, n: int, dt: torch.dtype, c: torch.Tensor, bias) -> None:
+    if c.dtype != torch.float32 or tuple(c.shape) != (n,) or not c.is_contiguous() or c.data_ptr() % 16:
+        raise _lib.SdnqHipError(f"{what}: c must be a contiguous, 16-byte aligned float32 vector [N = {n}] (got {c.dtype}, {tuple(c.shape)})")
+    if bias is not None and (bias.dtype != dt or tuple(bias.shape) != (n,) or not bias.is_contiguous() or bias.data_ptr() % 16):
+        raise _lib.SdnqHipError(f"{what}: bias must be a contiguous, 16-byte aligned {dt} vector [N = {n}] (got {bias.dtype}, {tuple(bias.shape)})")
+
+
+def lowrank_add_dora(t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float, c: torch.Tensor, bias=None) -> torch.Tensor:
+    """sdnq_hip_lowrank_add_dora: ``lowrank_add`` with DoRA's epilogue IN PLACE on y [M, N] = the base output z (bias included):
+    y = round(fma(c * scale, t @ up^T, fma(c - 1, z - bias, z))), c [N] float32, bias [N] of y's dtype or None.  With c == 1 the bits of
+    ``lowrank_add``.  Returns y."""
+    what = "lowrank_add_dora"
+    if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
+        raise _lib.SdnqHipError(f"{what}: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    (m, r), (n, r2) = t.shape, up.shape
+    _lowrank_check(what, r, t=t, up=up, y=y)
+    if r2 != r or tuple(y.shape) != (m, n):
+        raise _lib.SdnqHipError(f"{what}: t [M, R], up [N, R], y [M, N] (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
+    if n % 8:
+        raise _lib.SdnqHipError(f"{what}: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
+    if not t.is_contiguous() or not up.is_contiguous():
+        raise _lib.SdnqHipError(f"{what}: t and up must be contiguous")
+    _dora_vectors(what, n, y.dtype, c, bias)
+    _require_cuda(t, up, y, c, bias)
+    if m == 0:
+        return y
+    check(_lib.load().sdnq_hip_lowrank_add_dora(t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y),
+                                                c.data_ptr(), _ptr(bias), _stream(y)), what)
+    return y
+
+
+def dora_bwd_workspace_bytes(m: int, n: int) -> int:
+    """sdnq_hip_dora_bwd_workspace_bytes: 0 while the m rows fit one slab of the deterministic reduction."""
+    nbytes = _lib.load().sdnq_hip_dora_bwd_workspace_bytes(m, n)
+    if nbytes < 0:
+        check(int(nbytes), "dora_bwd_workspace_bytes")
+    return int(nbytes)
+
+
+def dora_bwd(dy: torch.Tensor, y: torch.Tensor | None, bias, c: torch.Tensor, want_q: bool = True, workspace: torch.Tensor | None = None):
+    """sdnq_hip_dora_bwd: (g, q) in one pass -- g [M, N] = round(dy * c) in dy's dtype, q [N] float32 = sum_i dy[i] * (y[i] - bias) (None
+    with want_q=False: y is then not read and may be None).  dy, y: bfloat16 / float16 with unit column stride and 16-byte aligned rows; c
+    [N] float32; bias [N] of dy's dtype or None.  Slabs of 256 rows added in a fixed order: the same bits on every call.  workspace as
+    ``lowrank_grad``: at least dora_bwd_workspace_bytes(M, N) bytes of uint8, or None for this module's per-stream buffer."""
+    what = "dora_bwd"
+    if dy.ndim != 2:
+        raise _lib.SdnqHipError(f"{what}: dy must be 2-D (got {tuple(dy.shape)})")
+    m, n = dy.shape
+    ops_t = {"dy": dy}
+    if want_q:
+        if y is None or tuple(y.shape) != (m, n):
+            raise _lib.SdnqHipError(f"{what}: y must have dy's shape {(m, n)} (got {None if y is None else tuple(y.shape)})")
+        ops_t["y"] = y
+    _lowrank_check(what, 8, **ops_t)
+    if n % 8:
+        raise _lib.SdnqHipError(f"{what}: n % 8 == 0 (got n = {n}): the rows move in 16-byte pieces")
+    _dora_vectors(what, n, dy.dtype, c, bias)
+    _require_cuda(dy, y if want_q else None, c, bias, workspace)
+    g = torch.empty((m, n), device=dy.device, dtype=dy.dtype)
+    q = torch.empty(n, device=dy.device, dtype=torch.float32) if want_q else None
+    if m == 0:
+        return g, (q.zero_() if want_q else None)
+    need = dora_bwd_workspace_bytes(m, n) if want_q else 0
+    wp = _grad_workspace(what, dy.device, _stream(dy), need, workspace)
+    check(_lib.load().sdnq_hip_dora_bwd(dy.data_ptr(), _ld(dy), y.data_ptr() if want_q else None, _ld(y) if want_q else 0, _ptr(bias),
+                                        c.data_ptr(), float_code(dy.dtype), m, n, g.data_ptr(), _ptr(q), wp, need, _stream(dy)), what)
+    return g, q
+
+
 def _conv_lowrank_check(what: str, x: torch.Tensor, other: torch.Tensor, kernel, stride, padding, dilation):
     """The checks the two conv adapter entry points share -- x [B, C, H, W] and a 2-D operand with `rank` rows / columns of ONE 16-bit dtype,
     8 | C kh kw -- and their integer arguments: (geometry tuple of 12 ints, (B, H_out, W_out), K)."""
