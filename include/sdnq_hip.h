@@ -518,6 +518,22 @@ int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dtype, int64_t
                                const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n, sdnq_stream_t stream);
 int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, int out_dtype, int64_t m, int64_t n, int64_t k);
 
+/* The fragment-ordered copy of an int8 weight for the one-launch Linear's 32 x 256 tile (nothing in the reference: its Triton kernel reads
+ * the stored operand).  For 32-row block g, K stage j (128 bytes), sub-step ks (32 bytes) and lane l, the 16 bytes
+ * b[32 g + (l & 31)][128 j + 32 ks + 16 (l >> 5) ..] lie at ((g (K / 128) + j) 4 + ks) 1024 + 16 l: what one wave's MFMA operand load reads
+ * is 1 KiB contiguous.  Rows past N repeat row N - 1.  sdnq_hip_aq_slab_bytes: the size of the copy (0 where none is defined: K % 128 != 0);
+ * sdnq_hip_aq_slab_pack writes it on `stream` (b [N][K] with row stride ldb, 16-byte aligned like `out`; K <= 1280);
+ * sdnq_hip_aq_slab_wanted: 1 where sdnq_hip_linear_w8a8_fused_slab on (M, N, K) would read the copy -- hosts build it for those layers only.
+ * sdnq_hip_linear_w8a8_fused_slab is sdnq_hip_linear_w8a8_fused with that copy of `b` beside it: where the launch runs the 32 x 256 tile on
+ * int8 codes, its waves load their weight fragments from the copy straight into registers; with b_slab NULL, or any other tile or operand
+ * type, it is sdnq_hip_linear_w8a8_fused exactly.  Same bits either way (SDNQ_HIP_FUSED_ROWQUANT_DIRECT=0 ignores the copy). */
+int64_t sdnq_hip_aq_slab_bytes(int64_t n, int64_t k);
+int sdnq_hip_aq_slab_wanted(int mm_dtype, int64_t m, int64_t n, int64_t k);
+int sdnq_hip_aq_slab_pack(const void* b, int64_t n, int64_t k, int64_t ldb, void* out, sdnq_stream_t stream);
+int sdnq_hip_linear_w8a8_fused_slab(int mm_dtype, const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* b,
+                                    const float* sb, const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n,
+                                    const void* b_slab, sdnq_stream_t stream);
+
 /* ---- the whole quantized-matmul forward of one layer behind ONE call -------------------------------------------------
  * int8_matmul / fp8_matmul / uint8_matmul (layers/linear/linear_int8.py:75-97, linear_fp8.py:58-78, linear_uint8.py:80-102) for every
  * layer form: row quantization of the activation (Hadamard-rotated when the layer is, asymmetric for the uint8 matmul), the low-rank

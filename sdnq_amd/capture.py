@@ -59,7 +59,7 @@ def _fingerprint(model: torch.nn.Module):
     for mod in model.modules():
         st = mod.__dict__.get("_sdnq_hip_state")
         if st is not None:
-            for name in ("mm_weight", "mm_scale"):
+            for name in ("mm_weight", "mm_scale", "mm_slab"):
                 t = getattr(st, name, None)
                 if isinstance(t, torch.Tensor):
                     fp.append((t.data_ptr(), t.numel(), t.dtype))

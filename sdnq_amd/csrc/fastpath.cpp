@@ -42,7 +42,7 @@
 namespace {
 
 decltype(&sdnq_hip_linear_w8a8) f_linear_w8a8 = nullptr;
-decltype(&sdnq_hip_linear_w8a8_fused) f_fused = nullptr;
+decltype(&sdnq_hip_linear_w8a8_fused_slab) f_fused = nullptr;  // (with the slab copy of the weight, or NULL: then sdnq_hip_linear_w8a8_fused)
 decltype(&sdnq_hip_linear_w8a8_fused_supported) f_fused_supported = nullptr;
 decltype(&sdnq_hip_prefetch_hint) f_hint = nullptr;
 decltype(&sdnq_hip_stream_capture_id) f_capture_id = nullptr;
@@ -350,6 +350,7 @@ struct PlanObj {
     vectorcallfunc vc;
     std::vector<KeyEnt>* keys;
     at::Tensor* wq;
+    at::Tensor* wslab;  // undefined tensor: no slab copy of wq (linear._aq_slab)
     at::Tensor* ws;
     at::Tensor* bias;  // undefined tensor: none
     int mm, had, device, bias_code;
@@ -445,7 +446,7 @@ PyObject* plan_call(PyObject* self, PyObject* const* args, size_t nargsf, PyObje
         int rc;
         if (fused) {
             rc = f_fused(p->mm, x2.data_ptr(), code, m, p->k, x2.stride(0), p->wq->data_ptr(), (const float*)p->ws->data_ptr(), bias, p->bias_code,
-                         out.data_ptr(), code, p->n, stream);
+                         out.data_ptr(), code, p->n, p->wslab->defined() ? p->wslab->data_ptr() : nullptr, stream);
             g_fused_calls.fetch_add(1, std::memory_order_relaxed);
         } else {
             const int64_t xq_bytes = (m * p->k + 255) & ~(int64_t)255;
@@ -466,12 +467,12 @@ PyObject* plan_call(PyObject* self, PyObject* const* args, size_t nargsf, PyObje
 }
 
 PyObject* plan_new(PyTypeObject* type, PyObject* args, PyObject* kw) {
-    static const char* kwlist[] = {"names", "refs", "mm", "n", "k", "wq", "ws", "bias", "had", "allow_fused", "allow_ws", "unit", "group", "idx", nullptr};
-    PyObject *names, *refs, *wq = Py_None, *ws = Py_None, *bias = Py_None, *unit = Py_None, *group = Py_None;
+    static const char* kwlist[] = {"names", "refs", "mm", "n", "k", "wq", "ws", "bias", "had", "allow_fused", "allow_ws", "unit", "group", "idx", "wslab", nullptr};
+    PyObject *names, *refs, *wq = Py_None, *ws = Py_None, *bias = Py_None, *unit = Py_None, *group = Py_None, *wslab = Py_None;
     int mm = 0, had = 0, allow_fused = 0, allow_ws = 0, idx = 0;
     long long n = 0, k = 0;
-    if (!PyArg_ParseTupleAndKeywords(args, kw, "OOiLL|OOOippOOi", (char**)kwlist, &names, &refs, &mm, &n, &k, &wq, &ws, &bias, &had, &allow_fused, &allow_ws, &unit,
-                                     &group, &idx))
+    if (!PyArg_ParseTupleAndKeywords(args, kw, "OOiLL|OOOippOOiO", (char**)kwlist, &names, &refs, &mm, &n, &k, &wq, &ws, &bias, &had, &allow_fused, &allow_ws, &unit,
+                                     &group, &idx, &wslab))
         return nullptr;
     if (!PyTuple_Check(names) || !PyTuple_Check(refs) || PyTuple_GET_SIZE(names) != PyTuple_GET_SIZE(refs)) {
         PyErr_SetString(PyExc_TypeError, "names and refs must be tuples of one length");
@@ -481,11 +482,13 @@ PyObject* plan_new(PyTypeObject* type, PyObject* args, PyObject* kw) {
     if (group != Py_None && !PyObject_TypeCheck(group, &GroupType)) { PyErr_SetString(PyExc_TypeError, "group must be a Group"); return nullptr; }
     if (group == Py_None && (!THPVariable_Check(wq) || !THPVariable_Check(ws))) { PyErr_SetString(PyExc_TypeError, "wq / ws must be tensors"); return nullptr; }
     if (bias != Py_None && !THPVariable_Check(bias)) { PyErr_SetString(PyExc_TypeError, "bias must be a tensor or None"); return nullptr; }
+    if (wslab != Py_None && !THPVariable_Check(wslab)) { PyErr_SetString(PyExc_TypeError, "wslab must be a tensor or None"); return nullptr; }
     PlanObj* p = (PlanObj*)type->tp_alloc(type, 0);
     if (!p) return nullptr;
     p->vc = plan_call;
     p->keys = new std::vector<KeyEnt>();
     p->wq = new at::Tensor();
+    p->wslab = new at::Tensor();
     p->ws = new at::Tensor();
     p->bias = new at::Tensor();
     p->unit = nullptr;
@@ -529,6 +532,14 @@ PyObject* plan_new(PyTypeObject* type, PyObject* args, PyObject* kw) {
                 return nullptr;
             }
             p->device = (int)p->wq->device().index();
+            if (wslab != Py_None) {
+                *p->wslab = THPVariable_Unpack(wslab);
+                if (!p->wslab->is_cuda() || p->wslab->device() != p->wq->device() || !p->wslab->is_contiguous()) {
+                    PyErr_SetString(PyExc_ValueError, "wslab must be a contiguous tensor on wq's device");
+                    Py_DECREF(p);
+                    return nullptr;
+                }
+            }
             if (bias != Py_None) {
                 *p->bias = THPVariable_Unpack(bias);
                 p->bias_code = float_code(p->bias->scalar_type());
@@ -559,6 +570,7 @@ void plan_dealloc(PlanObj* p) {
         delete p->keys;
     }
     delete p->wq;
+    delete p->wslab;
     delete p->ws;
     delete p->bias;
     delete p->unit;
@@ -583,7 +595,7 @@ PyObject* m_init(PyObject*, PyObject* arg) {
     var = (decltype(var))dlsym(h, #name);                                                                           \
     if (!var) { PyErr_Format(PyExc_OSError, "%s does not export " #name, path); return nullptr; }
     RESOLVE(f_linear_w8a8, sdnq_hip_linear_w8a8)
-    RESOLVE(f_fused, sdnq_hip_linear_w8a8_fused)
+    RESOLVE(f_fused, sdnq_hip_linear_w8a8_fused_slab)
     RESOLVE(f_fused_supported, sdnq_hip_linear_w8a8_fused_supported)
     RESOLVE(f_hint, sdnq_hip_prefetch_hint)
     RESOLVE(f_capture_id, sdnq_hip_stream_capture_id)

@@ -25,7 +25,9 @@
 // are drained under the quantization, the others in a K loop without a barrier, in the ring form's order of stages and sub-steps: the
 // same bits (tests/test_gemm_aq_regslab.py: a placement census of every weight byte, every stage count and edge).  Draining ALL stages
 // into registers under the quantization (160 registers per lane; built and measured) lost: the MFMAs then start only when the last
-// weight byte has landed.
+// weight byte has landed.  Where the caller holds the fragment-ordered copy of an int8 weight
+// (sdnq_hip_linear_w8a8_fused_slab), the tile runs its DIRECT form instead: no ring, the fragments loaded from the copy straight into a
+// three-stage ring of registers (DIRECT in the kernel; tests/test_gemm_aq_direct.py).
 //
 // Quantization layout (64 x 128 tile; the 32 x 256 tile: rows 4w .. 4w+3, one pass): wave w owns tile rows 8w .. 8w+7 in two passes of 4 rows; a row is read by a QUARTER wave (16 lanes x 16 bytes
 // = 128 elements per load instruction = one K stage), so the row amax is a reduction inside one 16-lane DPP row (four DPP exchanges,
@@ -92,7 +94,9 @@ template <> struct AqMma<SDNQ_MM_FP8> {
     static __device__ __forceinline__ float tof(const acc_t& c, int i) { return c[i]; }
 };
 
-// X_T: activation dtype (bf16 / f16) = output dtype; NJ: K stages held (K <= 128 NJ); NSB: weight ring depth; BM x BN: tile geometry
+// X_T: activation dtype (bf16 / f16) = output dtype; NJ: K stages held (K <= 128 NJ); NSB: weight ring depth; BM x BN: tile geometry.
+// NSB < 0 is the DIRECT form of the slab tile (int8): no LDS ring at all, -NSB weight stages in a ring of REGISTERS, loaded from the
+// fragment-ordered copy of the weight (see DIRECT below)
 template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN>
 __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ w, int ldx, int ldb, int M, int N,
                                                        int K, int tiles_m, int tiles_n, int group_m, AqParams p_) {
@@ -111,10 +115,24 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     constexpr bool SLAB = BN / 32 == NW;
     constexpr int KS = BK / MT::KB;
     static_assert(!SLAB || (NSB <= NJ && PPW == 4), "register slab: the ring is no deeper than the stages held; a wave's 32 rows are four pieces");
+    // DIRECT: the slab form without the ring.  A wave's weight fragment of (stage j, sub-step ks) IS one 16-byte load per lane -- row
+    // n0 + 32 wave + (lane & 31), bytes 128 j + 32 ks + 16 (lane >> 5) --, so the wave loads it from global memory straight into the
+    // four registers the MFMA reads: no LDS-DMA piece to issue, no write into and fragment read out of LDS, no lgkmcnt wait before a
+    // refill.  `w` is then the fragment-ordered COPY of the weight (sdnq_hip_aq_slab_pack: block g, stage j, sub-step ks at
+    // ((g nk + j) 4 + ks) 1024, 16 bytes per lane), so that one load instruction reads 1 KiB = 8 lines; on the stored row-major operand
+    // the same instruction touches 32 lines for 32 bytes each and the CU's address path takes 4 x as long over it (12.6 against 8.0 us
+    // per launch, whatever the depth: DESIGN.md 7).  RD stages are in flight behind the activation rows; loads return in order, so the
+    // counted vmcnt in front of a sub-step's MFMA (the compiler's: the fragments are ordinary values) lets stage 0 multiply while the
+    // later stages are still on their way, and each fragment register is refilled with stage j + RD right behind the MFMA that read
+    // it.  Stages and sub-steps in the ring form's order: the same bits (tests/test_gemm_aq_direct.py).
+    constexpr bool DIRECT = NSB < 0;
+    constexpr int RD = !DIRECT ? 0 : (-NSB < NJ ? -NSB : NJ);  // register stages: no more than the stages held
+    constexpr int NSL = DIRECT ? 0 : NSB;                      // ring slots in LDS
+    static_assert(!DIRECT || (SLAB && MM == SDNQ_MM_I8 && KS == 4 && RD >= 1 && KS * RD <= 48), "direct form: the int8 slab tile; the loads in flight fit the vmcnt counter");
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     uint8_t* const ldsA = lds;                       // [NJ][BM rows][128 B] quantized activation rows, resident
     uint8_t* const ldsB = lds + NJ * A_STAGE;        // [NSB][BN rows][128 B] weight ring
-    float* const s_sb = (float*)(ldsB + NSB * B_STAGE);
+    float* const s_sb = (float*)(ldsB + NSL * B_STAGE);
     float* const s_bias = s_sb + BN;
     float* const s_xs = s_bias + BN;                 // [BM] activation row scales
 
@@ -148,7 +166,10 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // ---- weight ring prologue: piece = 8 rows x 128 B, lane l -> row l / 8, physical chunk l % 8 (source chunk = swizzle-inverse);
     // wave w owns pieces w, w + 8, ... (PPW of them) of every stage -- in the register-slab form pieces PPW w ..: its own 32 weight rows;
     // constant per-lane offsets, the K advance in the scalar operand
-    const auto rsB = SDNQ_MAKE_RSRC_N(w + (int64_t)n0 * ldb, (int64_t)(n_lim - 1) * ldb + K);
+    // (direct form: the descriptor spans the 32-row blocks of this tile that exist in the copy)
+    const int nblk = (n_lim + 31) >> 5;
+    const auto rsB = DIRECT ? SDNQ_MAKE_RSRC_N(w + (int64_t)tile_n * (BN / 32) * nk * 4096, nblk * nk * 4096)
+                            : SDNQ_MAKE_RSRC_N(w + (int64_t)n0 * ldb, (int64_t)(n_lim - 1) * ldb + K);
     int voB[PPW];
     auto pieceB = [&](int u) { return SLAB ? wave * PPW + u : wave + u * NW; };
 #pragma unroll
@@ -162,9 +183,27 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #pragma unroll
         for (int u = 0; u < PPW; ++u) SDNQ_DMA16(rsB, ldsB + slot * B_STAGE + pieceB(u) * 1024, voB[u], s * BK);
     };
-    constexpr int AHEAD = SLAB ? NSB : NSB - 1;  // ring stages in flight behind the rows (the slab form has no slot to hold back: it refills as it drains)
+    constexpr int AHEAD = DIRECT ? RD : (SLAB ? NSB : NSB - 1);  // stages in flight behind the rows (the slab forms have no slot to hold back: they refill as they drain)
+    // direct form: the wave's own block of the copy, one fragment per load; a wave whose block lies past N reads the tile's last block
+    // (valid memory, never stored)
+    typename MT::frag_t fbd[DIRECT ? RD : 1][KS];
+    const int voD = lane << 4, soD = (wave < nblk ? wave : nblk - 1) * nk * 4096;
+    auto issueD = [&](auto slotc, auto ksc, int st) {  // stages past the end re-fetch stage 0, as issueB does (never multiplied)
+        constexpr int ks = decltype(ksc)::value;
+        if constexpr (DIRECT) fbd[decltype(slotc)::value][ks] = SDNQ_BUF_LOAD16(rsB, voD, soD + (st < nk ? st : 0) * 4096 + ks * 1024);
+    };
+    if constexpr (DIRECT) {
+        // (pinned one by one: the counted waits of the K loop follow the order of issue, and the scheduler put stage 1 in front of stage 0's last sub-step)
+        static_for_up<RD>([&](auto sc) {
+            static_for_up<KS>([&](auto ksc) {
+                issueD(sc, ksc, decltype(sc)::value);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        });
+    } else {
 #pragma unroll
-    for (int s = 0; s < AHEAD; ++s) issueB(s, s);
+        for (int s = 0; s < AHEAD; ++s) issueB(s, s);
+    }
     __builtin_amdgcn_sched_barrier(0);
     SDNQ_KERNARGS_NOW("s"(p_.sb), "s"(p_.bias), "s"(p_.out), "s"(p_.ldc), "s"(p_.bias_dtype), "s"(p_.trace));
     if (p.trace != nullptr && tid == 0 && blockIdx.x < 1024) p.trace[blockIdx.x * 8] = t_entry;
@@ -190,7 +229,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // stage, statically indexed); every later stage in the K loop, in front of its MFMAs.  DF = 2 measured best in the step: 0 leaves the
     // fill path idle behind the three prologue stages, 3 / 4 / all ten hold up the quantization -- and with it the barrier every wave's
     // MFMAs wait for -- on weights that have not landed yet (profiles/linear_aq_32x256_regslab.txt).
-    constexpr int DF = !SLAB ? 0 : (NJ < 2 ? NJ : 2);
+    constexpr int DF = !SLAB || DIRECT ? 0 : (NJ < 2 ? NJ : 2);
     typename MT::frag_t fbr[DF > 0 ? DF : 1][KS], fbs[KS];
     auto drainB = [&](int j, typename MT::frag_t* dst) {
         if (j < nk) {
@@ -314,7 +353,35 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     constexpr int lab = 0;  // (run-time switches inside the K loop cost it 35 %: a lab build only)
 #endif
     typename MT::frag_t fa[2][NACC][KS];
-    if constexpr (SLAB) {
+    if constexpr (DIRECT) {
+        // Direct form: the slab loop below with the weight fragments already in registers.  Sub-step ks of stage kt multiplies
+        // fbd[kt % RD][ks] as soon as that load has landed, and the register is reloaded with the same sub-step of stage kt + RD.
+        auto read_a = [&](auto setc, auto ksc, int st) {
+            constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
+#pragma unroll
+            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+        };
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        static_for_up<KS>([&](auto ksc) { read_a(std::integral_constant<int, 0>{}, ksc, 0); });
+        static_for_up<NJ>([&](auto ktc) {
+            constexpr int kt = decltype(ktc)::value, sx = kt & 1, slot = kt % (RD > 0 ? RD : 1);
+            if (kt < nk) {
+                __builtin_amdgcn_sched_barrier(0);
+                static_for_up<KS>([&](auto ksc) {
+                    constexpr int ks = decltype(ksc)::value;
+                    if (!(lab & 4)) {
+#pragma unroll
+                        for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fbd[slot][ks], fa[sx][a][ks]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (kt + 1 < NJ) { if (!(lab & 2)) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1); }
+                    if constexpr (kt + RD < NJ) issueD(std::integral_constant<int, slot>{}, ksc, kt + RD);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            }
+        });
+    } else if constexpr (SLAB) {
         // Slab form: the one barrier below publishes the A image; behind it a wave depends on nobody -- it waits for its OWN pieces of a
         // stage (counted vmcnt), takes them into registers, refills the slot and multiplies, so the waves drift apart and every wave
         // keeps NSB stages in flight of its own accord (the ring form refills a slot only once all eight waves have left it).  Stages
@@ -404,7 +471,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     // ---- epilogue in the MFMA register layout: lane owns row wm*32 + (lane & 31), channels wn*32 + (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5);
     // out = cast(fma(f32(acc) * xs, ws, bias)) (kernel_wrappers.py:132-144); final 16-bit values leave through LDS as 16-byte row pieces
     constexpr int OUT_ROW = BN * 2 + 16;
-    static_assert(BM * OUT_ROW <= NJ * A_STAGE + NSB * B_STAGE, "output staging fits the operand area");
+    static_assert(BM * OUT_ROW <= NJ * A_STAGE + NSL * B_STAGE, "output staging fits the operand area");
 #pragma unroll
     for (int a = 0; a < NACC; ++a) {
         const int ml = (wm + a) * 32 + frow;
@@ -438,6 +505,18 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 
 std::atomic<unsigned long long*> g_aq_trace{nullptr};
 std::atomic<int> g_aq_geometry{-1};  // tests / labs: -1 by shape, else a geometry id of the table above
+std::atomic<int> g_aq_direct{-1};    // tests / labs: -1 the default, 0 the ring form of geometry 1 whatever the caller passes, else its direct form
+
+// The form geometry 1 runs in on int8 where the caller passes the slab copy of the weight (sdnq_hip_linear_w8a8_fused_slab): the direct
+// form with AQ_DIRECT_STAGES register stages, or 0: the LDS ring (as without a copy).  Depths 3, 4, 6 and 8 were built and measured in
+// the step: 3 and 4 level, 6 and 8 behind; 3 takes the fewest registers.
+constexpr int AQ_DIRECT_STAGES = 3;
+inline int aq_direct_norm(int f) { return f == 0 ? 0 : AQ_DIRECT_STAGES; }
+inline int aq_direct_stages() {
+    static const int env = aq_direct_norm((int)env_int("SDNQ_HIP_FUSED_ROWQUANT_DIRECT", AQ_DIRECT_STAGES));  // tuning aid (0: the ring form)
+    const int forced = g_aq_direct.load(std::memory_order_relaxed);
+    return forced < 0 ? env : aq_direct_norm(forced);
+}
 
 constexpr int64_t AQ_TALL_MAX_K = 640;
 
@@ -486,7 +565,9 @@ inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
 
 template <int X_T, int MM, bool HAS_BIAS, int NJ, int NSB, int BM, int BN, int RESIDENT = 1>
 int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, int64_t k, const AqPlan& pl, AqParams p, hipStream_t s) {
-    constexpr int LDS_BYTES = NJ * BM * BK + NSB * BN * BK + (2 * BN + BM) * 4;
+    // the direct form (NSB < 0) has no ring, but asks for the three slots of the ring form all the same: one tile workgroup per CU, so
+    // that the hosted prefetch workgroups (aq_plan's prefetch_room) never share a CU with a tile
+    constexpr int LDS_BYTES = NJ * BM * BK + (NSB < 0 ? 3 : NSB) * BN * BK + (2 * BN + BM) * 4;
     static_assert(RESIDENT * LDS_BYTES <= 160 * 1024 && (RESIDENT + 1) * LDS_BYTES > 160 * 1024, "LDS budget: exactly RESIDENT workgroups per CU (aq_plan's prefetch room)");
     auto kern = linear_aq_kernel<X_T, MM, HAS_BIAS, NJ, NSB, BM, BN>;
     static std::atomic<uint64_t> attr_devices{0};
@@ -529,9 +610,44 @@ extern "C" int sdnq_hip_linear_w8a8_fused_supported(int mm_dtype, int x_dtype, i
     return 1;
 }
 
-extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* b,
-                                          const float* sb, const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n,
-                                          sdnq_stream_t stream) {
+namespace {
+__global__ __launch_bounds__(256) void aq_slab_pack_kernel(const uint8_t* __restrict__ b, int64_t n, int nk, int64_t ldb, uint8_t* __restrict__ out, int64_t pieces) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one 16-byte piece per thread, in the order of the copy
+    if (t >= pieces) return;
+    const int l = (int)(t & 63), ks = (int)(t >> 6) & 3;
+    const int64_t q = t >> 8, g = q / nk, j = q % nk;
+    const int64_t row = g * 32 + (l & 31);
+    const v4i v = *(const v4i*)(b + (row < n ? row : n - 1) * ldb + j * 128 + ks * 32 + (l >> 5) * 16);  // rows past N: the last row (never stored by a GEMM)
+    *(v4i*)(out + t * 16) = v;
+}
+}  // namespace
+
+extern "C" int64_t sdnq_hip_aq_slab_bytes(int64_t n, int64_t k) {
+    if (n <= 0 || k <= 0 || (k % 128) != 0) return 0;
+    return ((n + 31) / 32) * 32 * k;
+}
+
+extern "C" int sdnq_hip_aq_slab_wanted(int mm_dtype, int64_t m, int64_t n, int64_t k) {
+    if (mm_dtype != SDNQ_MM_I8 || m <= 0 || n <= 0 || k <= 0 || (k % 128) != 0 || k > 1280) return 0;
+    return aq_plan(mm_dtype, m, n, k, cu_count()).geometry == 1 && aq_direct_stages() != 0 ? 1 : 0;
+}
+
+extern "C" int sdnq_hip_aq_slab_pack(const void* b, int64_t n, int64_t k, int64_t ldb, void* out, sdnq_stream_t stream) {
+    if (!b || !out) return SDNQ_ERR_NULL;
+    if (n <= 0 || k <= 0 || ldb < k) return SDNQ_ERR_SHAPE;
+    if ((k % 128) != 0 || k > 1280) return SDNQ_ERR_UNSUPPORTED;
+    if (n > 0x7fffffffll / 2) return SDNQ_ERR_SHAPE;
+    if (((uintptr_t)b % 16) || ((uintptr_t)out % 16) || (ldb % 16)) return SDNQ_ERR_ALIGN;
+    const int64_t pieces = sdnq_hip_aq_slab_bytes(n, k) / 16;
+    hipLaunchKernelGGL(aq_slab_pack_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)b, n, (int)(k / 128), ldb,
+                       (uint8_t*)out, pieces);
+    SDNQ_CHECK_LAUNCH();
+    return SDNQ_OK;
+}
+
+extern "C" int sdnq_hip_linear_w8a8_fused_slab(int mm_dtype, const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* b,
+                                               const float* sb, const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n,
+                                               const void* b_slab, sdnq_stream_t stream) {
     if (!x || !b || !sb || !out) return SDNQ_ERR_NULL;
     if (mm_dtype != SDNQ_MM_I8 && mm_dtype != SDNQ_MM_FP8) return SDNQ_ERR_DTYPE;
     if ((x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) || out_dtype != x_dtype) return SDNQ_ERR_UNSUPPORTED;
@@ -539,12 +655,19 @@ extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dty
     if (m <= 0 || n <= 0 || k <= 0 || ldx < k || (n % 8) != 0) return SDNQ_ERR_SHAPE;
     if ((k % 128) != 0 || k > 1280) return SDNQ_ERR_UNSUPPORTED;
     if (m > 0x7fffffffll / 2 || n > 0x7fffffffll || ldx * 2 * 128 > 0x7fffffffll || k * 128 > 0x7fffffffll) return SDNQ_ERR_SHAPE;
-    if (((uintptr_t)x % 16) || ((uintptr_t)b % 16) || ((uintptr_t)out % 16) || ((ldx * 2) % 16)) return SDNQ_ERR_ALIGN;
+    if (((uintptr_t)x % 16) || ((uintptr_t)b % 16) || ((uintptr_t)out % 16) || ((ldx * 2) % 16) || ((uintptr_t)b_slab % 16)) return SDNQ_ERR_ALIGN;
     AqParams p{};
     p.sb = sb; p.bias = bias; p.out = out; p.ldc = n; p.bias_dtype = bias_dtype;
     hipStream_t s = (hipStream_t)stream;
     const AqPlan pl = aq_plan(mm_dtype, m, n, k, cu_count());
-#define AQ_L(XT, MMV, HB, NJV, ...) launch_aq<XT, MMV, HB, NJV, __VA_ARGS__>(x, b, ldx, m, n, k, pl, p, s)
+    const bool direct = pl.geometry == 1 && mm_dtype == SDNQ_MM_I8 && b_slab != nullptr && aq_direct_stages() != 0;
+    const void* const w = direct ? b_slab : b;
+#define AQ_L(XT, MMV, HB, NJV, ...) launch_aq<XT, MMV, HB, NJV, __VA_ARGS__>(x, w, ldx, m, n, k, pl, p, s)
+    // geometry 1 on int8 with the slab copy: the direct form, its register stages as the negative ring depth
+#define AQ_D(XT, HB, NJV) AQ_L(XT, SDNQ_MM_I8, HB, NJV, -AQ_DIRECT_STAGES, 32, 256)
+#define AQ_DB(XT, HB) (k <= 640 ? AQ_D(XT, HB, 5) : AQ_D(XT, HB, 10))
+#define AQ_DX(XT) (bias ? AQ_DB(XT, true) : AQ_DB(XT, false))
+    if (direct) return x_dtype == SDNQ_BF16 ? AQ_DX(SDNQ_BF16) : AQ_DX(SDNQ_F16);
 #define AQ_G(XT, MMV, HB, NJV) (pl.geometry == 1 ? AQ_L(XT, MMV, HB, NJV, 3, 32, 256) : AQ_L(XT, MMV, HB, NJV, 4, 64, 128))
 #define AQ_NJ(XT, MMV, HB) (k <= 640 ? AQ_G(XT, MMV, HB, 5) : AQ_G(XT, MMV, HB, 10))
 #define AQ_B(XT, MMV) (bias ? AQ_NJ(XT, MMV, true) : AQ_NJ(XT, MMV, false))
@@ -561,7 +684,16 @@ extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dty
 #undef AQ_B
 #undef AQ_NJ
 #undef AQ_G
+#undef AQ_DX
+#undef AQ_DB
+#undef AQ_D
 #undef AQ_L
+}
+
+extern "C" int sdnq_hip_linear_w8a8_fused(int mm_dtype, const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* b,
+                                          const float* sb, const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n,
+                                          sdnq_stream_t stream) {
+    return sdnq_hip_linear_w8a8_fused_slab(mm_dtype, x, x_dtype, m, k, ldx, b, sb, bias, bias_dtype, out, out_dtype, n, nullptr, stream);
 }
 
 // lab: phase stamps of the one-launch Linear (device buffer of 1024 x 8 uint64, or null to stop).  A C++ symbol internal to the library
@@ -571,6 +703,10 @@ void sdnq_internal_aq_trace(unsigned long long* device_buf) { g_aq_trace.store(d
 // tests / labs: force the tile geometry of the one-launch Linear (-1 by shape, 0 = 64 x 128, 1 = 32 x 256, 2 = 64 x 128 on two ring
 // slots, 3 = 128 x 128; any other value = 1, as before the tall forms); internal like the trace hook
 void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry <= 3 ? geometry : 1), std::memory_order_relaxed); }
+
+// tests / labs: the form geometry 1 runs in on int8 where the caller passes the slab copy (-1 the default, 0 the LDS ring, any other value
+// the direct form); internal like the hooks above
+void sdnq_internal_aq_direct(int form) { g_aq_direct.store(form < 0 ? -1 : aq_direct_norm(form), std::memory_order_relaxed); }
 
 // tests: what the launcher would choose for (mm_dtype, m, n, k) on a part with `cus` CUs:
 // out = {geometry, BM, BN, tiles_m, tiles_n, group_m, prefetch room}

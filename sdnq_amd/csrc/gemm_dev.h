@@ -33,6 +33,7 @@ int sdnq_internal_scaled_mm_ks(const void* a, const void* b, const float* sa, co
 void sdnq_internal_ks_trace(unsigned long long* device_buf);
 void sdnq_internal_aq_trace(unsigned long long* device_buf);
 void sdnq_internal_aq_geometry(int geometry);
+void sdnq_internal_aq_direct(int form);
 void sdnq_internal_aq_plan(int mm_dtype, long long m, long long n, long long k, int cus, long long* out);
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------------

@@ -47,6 +47,10 @@ FUSED_DEQUANT_GEMM_MAX_K = int(os.environ.get("SDNQ_HIP_FUSED_DEQUANT_GEMM_MAX_K
 # Round 5: the plain w8a8 Linear as ONE launch where it is built and wins (sdnq_hip_linear_w8a8_fused, csrc/gemm_aq.hip); the library's
 # own switch (SDNQ_HIP_FUSED_ROWQUANT=0) makes `..._supported` answer no, this one skips the question
 FUSED_ROWQUANT = os.environ.get("SDNQ_HIP_FUSED_ROWQUANT", "1").lower() not in {"0", "false", "no"}
+# The one-launch Linear's 32 x 256 tile reads its weights from a fragment-ordered copy of the cached int8 operand (ops.aq_slab_pack,
+# _aq_slab below): K x N bytes more per layer that runs that tile (the SDXL UNet: 192 layers x 1.6 MB = 315 MB beside 2.2 GB of weights).
+# 0: no copies, the tile streams the stored operand through its LDS ring.
+FUSED_ROWQUANT_SLABCOPY = os.environ.get("SDNQ_HIP_FUSED_ROWQUANT_SLABCOPY", "1").lower() not in {"0", "false", "no"}
 # Round 6 (north_star N1): in the memory-lean mode (SDNQ_HIP_CACHE_WEIGHTS=0) the few-row layers on 4-bit weights do not re-quantize their
 # weight per call any more: the GEMM reads the STORED codes and expands them through per-(row, 64 columns) tables built once
 # (sdnq_hip_scaled_mm_w4, csrc/gemm_w4.hip; 0.25 B per weight resident instead of the cached mode's 1.0).  Bit-identical.
@@ -265,7 +269,7 @@ def _rowquant_cached(input: torch.Tensor, k: int, mm: int, had: int, want_rowsum
 
 class _State:
     """Per-module cache of kernel-ready tensors, keyed on the identity of the module's parameters."""
-    __slots__ = ("key", "qw", "mm", "mm_weight", "mm_scale", "mm_zp", "mm_wcs", "svd_up", "svd_down", "svd_down_t", "wd", "bias", "pf", "lut")
+    __slots__ = ("key", "qw", "mm", "mm_weight", "mm_slab", "mm_scale", "mm_zp", "mm_wcs", "svd_up", "svd_down", "svd_down_t", "wd", "bias", "pf", "lut")
 
 
 class _LaunchUnit:
@@ -428,7 +432,7 @@ def _state(mod) -> _State:
     st.qw = dq.quant_weight(mod.weight, mod.scale, getattr(mod, "zero_point", None), getattr(mod, "svd_up", None),
                             getattr(mod, "svd_down", None))
     st.mm = None
-    st.mm_weight = st.mm_scale = st.mm_zp = st.mm_wcs = None
+    st.mm_weight = st.mm_slab = st.mm_scale = st.mm_zp = st.mm_wcs = None
     st.svd_up, st.svd_down = st.qw.keep[3], st.qw.keep[4]  # physical [N,R], [R,K]
     st.svd_down_t = None
     st.wd = None
@@ -653,11 +657,25 @@ def _prepare_mm_weights(mod, st: _State, mm: int, asymmetric: bool = False, for_
                 zp = torch.add(zp, ws, alpha=128) if zp is not None else ws * 128
                 if st.qw.scale_dtype != torch.float32:  # the reference's add runs on 16-bit tensors: float32 op-math, one rounding
                     zp = zp.to(st.qw.scale_dtype).float()
+    st.mm_slab = None  # (the copy of an operand that is being replaced)
     if CACHE_WEIGHTS:
         st.mm, st.mm_weight, st.mm_scale, st.mm_zp, st.mm_wcs = key, wq, ws, zp, None
     elif dq.re_quantize_for_matmul and not asymmetric:
         st.mm, st.mm_weight, st.mm_scale, st.mm_zp, st.mm_wcs = key, None, ws, None, None  # row scales only
     return wq, ws, zp
+
+
+def _aq_slab(st: _State, mm: int, wq: torch.Tensor, m: int, n: int, k: int):
+    """The fragment-ordered copy of the layer's cached int8 matmul operand for a one-launch Linear call on m rows, or None: built once,
+    at the first call outside a stream capture for which the library runs the tile that reads it (ops.aq_slab_wanted), kept beside
+    st.mm_weight and dropped with it.  Never for an operand that is not cached (the per-call mode, SDNQ_HIP_CACHE_WEIGHTS=0)."""
+    if not FUSED_ROWQUANT_SLABCOPY or mm != ops.MM_I8 or st.mm_weight is not wq:
+        return None
+    slab = st.mm_slab
+    if slab is None and ops.aq_slab_wanted(mm, m, n, k, wq.device) and not torch.cuda.is_current_stream_capturing():
+        if wq.dim() == 2 and wq.stride(1) == 1 and wq.stride(0) % 16 == 0 and wq.data_ptr() % 16 == 0:
+            slab = st.mm_slab = ops.aq_slab_pack(wq)
+    return slab
 
 
 class ProjectionGroup:
@@ -924,29 +942,37 @@ def _quantized_matmul_forward(self, input: torch.Tensor, mm: int, small_batch_br
     had = dq.hadamard_group_size if dq.use_hadamard else 0
     has_svd = st.svd_up is not None
     bias = _attr(self, "bias")
+    plain = not has_svd and zp is None and (had == 0 or k <= 5120)
+    use_cache = cache_input and CACHE_ACTIVATIONS > 0
+    x2 = slab = None
+    one_launch = False
+    if (plain and FUSED_ROWQUANT and had == 0 and input.is_cuda
+            and (not use_cache or (UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER))):
+        # nobody else consumes this layer's quantized activation (its input is its own: to_out, to_q of the cross attention, proj_in /
+        # proj_out, ...): where the one-launch route is built and expected to win, the GEMM row-quantizes its own activation rows in
+        # LDS -- no row-quantization launch, no quantized copy in HBM, one allocation, safe under graph capture (no scratch buffer).
+        # Decided in front of the prefetch hand-off: where the launch reads the slab copy of the weight, that is what the launches in
+        # front of it must warm (a prefetch of the stored operand would leave the bytes this launch reads cold)
+        x2 = input if input.dim() == 2 else input.reshape(-1, k)
+        if x2.stride(-1) != 1 or (x2.stride(0) * x2.element_size()) % 16:
+            x2 = x2.contiguous()
+        one_launch = ops.linear_w8a8_fused_supported(mm, x2, n, input.dtype)
+        if one_launch:
+            slab = _aq_slab(st, mm, wq, x2.shape[0], n, k)
     pf_on = PREFETCH_NEXT and st.mm_weight is wq and input.is_cuda
     if pf_on:  # (a cached operand: the per-call mode's scratch copies are not prefetched)
-        _pf_launch(st, (wq,))
+        _pf_launch(st, (wq,) if slab is None else (slab,))
     # what a plan may carry later: this layer, called through its own forward on its own input (no conv caller, no group), its matmul operand cached
     plannable = cache_input and small_batch_branch and group is None and st.mm_weight is wq
-    if not has_svd and zp is None and (had == 0 or k <= 5120):
+    if plain:
         # plain w8a8 layer: on a cache miss the row quantization and the GEMM go through ONE binding call (an eager model is
         # bound by the host-side cost per layer); the quantized activation still lands in the cache for sibling layers
-        use_cache = cache_input and CACHE_ACTIVATIONS > 0
-        if (FUSED_ROWQUANT and had == 0 and input.is_cuda
-                and (not use_cache or (UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER))):
-            # nobody else consumes this layer's quantized activation (its input is its own: to_out, to_q of the cross attention, proj_in /
-            # proj_out, ...): where the one-launch route is built and expected to win, the GEMM row-quantizes its own activation rows in
-            # LDS -- no row-quantization launch, no quantized copy in HBM, one allocation, safe under graph capture (no scratch buffer)
-            x2 = input if input.dim() == 2 else input.reshape(-1, k)
-            if x2.stride(-1) != 1 or (x2.stride(0) * x2.element_size()) % 16:
-                x2 = x2.contiguous()
-            if ops.linear_w8a8_fused_supported(mm, x2, n, input.dtype):
-                y = ops.linear_w8a8_fused(mm, x2, wq, ws, bias, input.dtype)
-                if FAST_PLANS and plannable and "_sdnq_plan_declined" not in self.__dict__:
-                    _install_plan(self, mm=mm, n=n, k=k, wq=wq, ws=ws, bias=bias, had=0, allow_fused=True,
-                                  allow_ws=use_cache and UNSHARED_FAST_PATH, unit=st.pf.c if pf_on else None)
-                return y if input.dim() == 2 else y.view(*input.shape[:-1], n)
+        if one_launch:
+            y = ops.linear_w8a8_fused(mm, x2, wq, ws, bias, input.dtype, slab)
+            if FAST_PLANS and plannable and "_sdnq_plan_declined" not in self.__dict__:
+                _install_plan(self, mm=mm, n=n, k=k, wq=wq, ws=ws, bias=bias, had=0, allow_fused=True,
+                              allow_ws=use_cache and UNSHARED_FAST_PATH, unit=st.pf.c if pf_on else None, wslab=slab)
+            return y if input.dim() == 2 else y.view(*input.shape[:-1], n)
         if (use_cache and UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER and input.is_cuda
                 and not torch.cuda.is_current_stream_capturing()):
             # nobody ever used the quantized copy this layer parked (see _ActivationCache._retire): no key, no look-up, the quantized
@@ -1165,7 +1191,7 @@ def _fp16_matmul_forward(self, input: torch.Tensor, small_batch_branch: bool = T
             w16, ws = ops.rowquant_f16(ops.dequant(st.qw, torch.float32, 0, use_svd=False).reshape(n, -1))
         else:
             w16, ws = ops.unpack_mm_f16(st.qw), st.qw.keep[1]
-        st.mm, st.mm_weight, st.mm_scale, st.mm_zp, st.mm_wcs = key, w16, ws.reshape(-1), None, None
+        st.mm, st.mm_weight, st.mm_slab, st.mm_scale, st.mm_zp, st.mm_wcs = key, w16, None, ws.reshape(-1), None, None
     x2 = input.reshape(-1, k)
     if x2.stride(-1) != 1 or (x2.stride(0) * x2.element_size()) % 16:
         x2 = x2.contiguous()

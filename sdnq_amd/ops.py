@@ -500,8 +500,40 @@ def reset_fused_calls():
         fp.reset_counters()
 
 
-def linear_w8a8_fused(mm: int, x2d: torch.Tensor, b_phys: torch.Tensor, sb: torch.Tensor, bias, out_dtype: torch.dtype) -> torch.Tensor:
-    """The plain w8a8 Linear as one launch (no quantized copy of the activation is produced); bit-identical to linear_w8a8."""
+def aq_slab_bytes(n: int, k: int) -> int:
+    """Bytes of the fragment-ordered copy of an [n][k] int8 weight (sdnq_hip_aq_slab_bytes; 0 where none is defined)."""
+    return int(_lib.load().sdnq_hip_aq_slab_bytes(n, k))
+
+
+_slab_wanted = {}
+
+
+def aq_slab_wanted(mm: int, m: int, n: int, k: int, device) -> bool:
+    """True where the one-launch Linear on (m, n, k) would read the slab copy of its weight (sdnq_hip_aq_slab_wanted; memoized per device)."""
+    key = (mm, m, n, k, device.index)
+    r = _slab_wanted.get(key)
+    if r is None:
+        with torch.cuda.device(device):
+            r = _slab_wanted[key] = bool(_lib.load().sdnq_hip_aq_slab_wanted(mm, m, n, k))
+    return r
+
+
+def aq_slab_pack(b_phys: torch.Tensor) -> torch.Tensor:
+    """The fragment-ordered copy of an int8 weight [N][K] (row stride >= K) for the one-launch Linear's 32 x 256 tile: a new int8 tensor
+    of aq_slab_bytes(N, K) bytes, written on the current stream (sdnq_hip_aq_slab_pack)."""
+    _require_cuda(b_phys)
+    n, k = b_phys.shape
+    nbytes = aq_slab_bytes(n, k)
+    if nbytes == 0 or b_phys.stride(1) != 1 or b_phys.element_size() != 1:
+        raise _lib.SdnqHipError(f"aq_slab_pack: no slab copy for a weight of shape {tuple(b_phys.shape)}, strides {b_phys.stride()}, {b_phys.dtype}")
+    out = torch.empty(nbytes, device=b_phys.device, dtype=torch.int8)
+    check(_lib.load().sdnq_hip_aq_slab_pack(b_phys.data_ptr(), n, k, b_phys.stride(0), out.data_ptr(), _stream(b_phys)), "aq_slab_pack")
+    return out
+
+
+def linear_w8a8_fused(mm: int, x2d: torch.Tensor, b_phys: torch.Tensor, sb: torch.Tensor, bias, out_dtype: torch.dtype, slab=None) -> torch.Tensor:
+    """The plain w8a8 Linear as one launch (no quantized copy of the activation is produced); bit-identical to linear_w8a8.
+    `slab`: aq_slab_pack(b_phys), or None -- where the launch runs the 32 x 256 tile its waves read their weights from it."""
     _require_cuda(x2d, b_phys, sb, bias)
     m, k = x2d.shape
     n = b_phys.shape[0]
@@ -509,6 +541,11 @@ def linear_w8a8_fused(mm: int, x2d: torch.Tensor, b_phys: torch.Tensor, sb: torc
     if bias is not None:
         bias = bias.contiguous()
     fused_calls[0] += 1
+    if slab is not None:
+        check(_lib.load().sdnq_hip_linear_w8a8_fused_slab(mm, x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), b_phys.data_ptr(), sb.data_ptr(),
+                                                          _ptr(bias), 0 if bias is None else float_code(bias.dtype), out.data_ptr(), float_code(out_dtype),
+                                                          n, slab.data_ptr(), _stream(x2d)), "linear_w8a8_fused_slab")
+        return out
     check(_lib.load().sdnq_hip_linear_w8a8_fused(mm, x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), b_phys.data_ptr(), sb.data_ptr(),
                                                  _ptr(bias), 0 if bias is None else float_code(bias.dtype), out.data_ptr(), float_code(out_dtype),
                                                  n, _stream(x2d)), "linear_w8a8_fused")

@@ -1,5 +1,7 @@
 """Lab of the one-launch w8a8 Linear (csrc/gemm_aq.hip) against the two-launch route: graph-replayed pairs on cold / warm operands and the
-phase stamps of the fused kernel.  usage: python tools/aq_lab.py [MxNxK ...]"""
+phase stamps of the fused kernel.  usage: python tools/aq_lab.py [--forms 0,1] [MxNxK ...]
+--forms: the forms of the 32 x 256 tile to run one after the other (sdnq_internal_aq_direct: 0 the LDS ring, 1 the direct form on the
+slab copy of the weight; default: -1, whatever the library ships).  Every fused call is handed the slab copy; the ring form ignores it."""
 import ctypes
 import sys
 
@@ -10,7 +12,15 @@ from sdnq_amd import _lib, ops  # noqa: E402
 
 dev = torch.device("cuda:0")
 lib = _lib.load()
-shapes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:]] or [(1024, 1280, 1280), (1024, 1280, 640), (4096, 640, 640), (1024, 640, 1280), (2048, 1280, 1280), (1024, 3840, 1280)]
+args = sys.argv[1:]
+forms = [-1]
+if "--forms" in args:
+    i = args.index("--forms")
+    forms = [int(v) for v in args[i + 1].split(",")]
+    del args[i:i + 2]
+aq_direct = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z23sdnq_internal_aq_directi")
+aq_direct.argtypes, aq_direct.restype = [ctypes.c_int], None
+shapes = [tuple(int(v) for v in a.split("x")) for a in args] or [(1024, 1280, 1280), (1024, 1280, 640), (4096, 640, 640), (1024, 640, 1280), (2048, 1280, 1280), (1024, 3840, 1280)]
 
 
 def timed(fn, pool, reps=5):
@@ -38,10 +48,14 @@ def timed(fn, pool, reps=5):
     return best
 
 
-for (m, n, k) in shapes:
+for (m, n, k), form in ((sh, f) for sh in shapes for f in forms):
+    aq_direct(form)
+    if len(forms) > 1:
+        print(f"-- form {form}", flush=True)
     for pool_n, tag in ((1, "re-read"), (64, "distinct operands")):
         xs_ = [torch.randn(m, k, device=dev).to(torch.bfloat16) for _ in range(pool_n)]
         bs = [torch.randint(-128, 128, (n, k), dtype=torch.int8, device=dev) for _ in range(pool_n)]
+        slabs = [ops.aq_slab_pack(w) if ops.aq_slab_bytes(n, k) else None for w in bs]
         sb = torch.rand(n, device=dev) * 0.02 + 1e-4
         bias = torch.randn(n, device=dev).to(torch.bfloat16)
         reps = max(pool_n, 32)
@@ -49,7 +63,7 @@ for (m, n, k) in shapes:
         two = timed(lambda i: ops.linear_w8a8(ops.MM_I8, xs_[i % pool_n], bs[i % pool_n], sb, bias, torch.bfloat16), idx)
         sup = lib.sdnq_hip_linear_w8a8_fused_supported(0, 1, 1, m, n, k)
         try:
-            one = timed(lambda i: ops.linear_w8a8_fused(ops.MM_I8, xs_[i % pool_n], bs[i % pool_n], sb, bias, torch.bfloat16), idx)
+            one = timed(lambda i: ops.linear_w8a8_fused(ops.MM_I8, xs_[i % pool_n], bs[i % pool_n], sb, bias, torch.bfloat16, slabs[i % pool_n]), idx)
         except Exception as e:  # noqa: BLE001
             one = float("nan")
             print("  fused route refused:", e)
@@ -64,9 +78,10 @@ for (m, n, k) in shapes:
         aq_trace(buf.data_ptr())
         x = torch.randn(m, k, device=dev).to(torch.bfloat16)
         b = torch.randint(-128, 128, (n, k), dtype=torch.int8, device=dev)
+        slab = ops.aq_slab_pack(b) if ops.aq_slab_bytes(n, k) else None
         for _ in range(3):
             buf.zero_()
-            ops.linear_w8a8_fused(ops.MM_I8, x, b, sb, bias, torch.bfloat16)
+            ops.linear_w8a8_fused(ops.MM_I8, x, b, sb, bias, torch.bfloat16, slab)
             torch.cuda.synchronize()
         aq_trace(None)
         t = buf.view(1024, 8).cpu()
