@@ -534,6 +534,22 @@ int sdnq_hip_linear_w8a8_fused_slab(int mm_dtype, const void* x, int x_dtype, in
                                     const float* sb, const void* bias, int bias_dtype, void* out, int out_dtype, int64_t n,
                                     const void* b_slab, sdnq_stream_t stream);
 
+/* The one-launch Linear for SEVERAL int8 layers that read one activation (the linked to_q / to_k / to_v of a self-attention block; the
+ * reference runs one row quantization and one Triton scaled-mm per layer): one launch, no row-quantization launch and no quantized copy of
+ * the activation.  n_members layers of n_member output channels each; b_slabs / sbs / biases are HOST arrays of n_members device pointers:
+ * every layer's slab copy (sdnq_hip_aq_slab_pack), its [n_member] scales and its [n_member] bias of bias_dtype (biases NULL: no layer has
+ * one).  Output as sdnq_hip_scaled_mm_grouped: ONE buffer of M * n_members * n_member elements of x's dtype, layer i the contiguous
+ * [M][n_member] matrix at element offset M * n_member * i.  Every element has the bits sdnq_hip_linear_w8a8_fused gives that layer alone.
+ * sdnq_hip_linear_w8a8_fused_grouped_supported: 1 where this is built and every tile of the group is resident at once -- int8, bf16 / f16
+ * in = out, K % 128 == 0 and 640 < K <= 1280, n_member % 256 == 0, at most 8 layers, ceil(M / 32) * n_members * n_member / 256 tiles on at
+ * most two per CU; other groups return SDNQ_ERR_UNSUPPORTED and keep sdnq_hip_rowquant + sdnq_hip_scaled_mm_grouped
+ * (SDNQ_HIP_FUSED_ROWQUANT=0 or SDNQ_HIP_FUSED_ROWQUANT_GROUPED=0 turns it off). */
+int sdnq_hip_linear_w8a8_fused_grouped(int mm_dtype, const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, const void* const* b_slabs,
+                                       const float* const* sbs, const void* const* biases, int bias_dtype, int64_t n_members, int64_t n_member,
+                                       void* out, int out_dtype, sdnq_stream_t stream);
+int sdnq_hip_linear_w8a8_fused_grouped_supported(int mm_dtype, int x_dtype, int out_dtype, int64_t m, int64_t n_member, int64_t n_members,
+                                                 int64_t k);
+
 /* ---- the whole quantized-matmul forward of one layer behind ONE call -------------------------------------------------
  * int8_matmul / fp8_matmul / uint8_matmul (layers/linear/linear_int8.py:75-97, linear_fp8.py:58-78, linear_uint8.py:80-102) for every
  * layer form: row quantization of the activation (Hadamard-rotated when the layer is, asymmetric for the uint8 matmul), the low-rank

@@ -35,6 +35,7 @@ void sdnq_internal_aq_trace(unsigned long long* device_buf);
 void sdnq_internal_aq_geometry(int geometry);
 void sdnq_internal_aq_direct(int form);
 void sdnq_internal_aq_plan(int mm_dtype, long long m, long long n, long long k, int cus, long long* out);
+void sdnq_internal_aq_plan_grouped(long long m, long long n_member, long long n_members, long long k, int cus, long long* out);
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------------
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

@@ -48,7 +48,8 @@ FUSED_DEQUANT_GEMM_MAX_K = int(os.environ.get("SDNQ_HIP_FUSED_DEQUANT_GEMM_MAX_K
 # own switch (SDNQ_HIP_FUSED_ROWQUANT=0) makes `..._supported` answer no, this one skips the question
 FUSED_ROWQUANT = os.environ.get("SDNQ_HIP_FUSED_ROWQUANT", "1").lower() not in {"0", "false", "no"}
 # The one-launch Linear's 32 x 256 tile reads its weights from a fragment-ordered copy of the cached int8 operand (ops.aq_slab_pack,
-# _aq_slab below): K x N bytes more per layer that runs that tile (the SDXL UNet: 192 layers x 1.6 MB = 315 MB beside 2.2 GB of weights).
+# _aq_slab below): K x N bytes more per layer that runs that tile (the SDXL UNet: 192 layers x 1.6 MB = 315 MB beside 2.2 GB of weights,
+# and 180 x 1.6 MB = 295 MB for the linked q / k / v members, whose group runs as one launch of that tile: ProjectionGroup._slabs).
 # 0: no copies, the tile streams the stored operand through its LDS ring.
 FUSED_ROWQUANT_SLABCOPY = os.environ.get("SDNQ_HIP_FUSED_ROWQUANT_SLABCOPY", "1").lower() not in {"0", "false", "no"}
 # Round 6 (north_star N1): in the memory-lean mode (SDNQ_HIP_CACHE_WEIGHTS=0) the few-row layers on 4-bit weights do not re-quantize their
@@ -707,6 +708,7 @@ class ProjectionGroup:
         self.fallback = None  # smaller groups (lists of members) to form when THIS grouping turns out wrong (loader.link_projections)
         self.pf = None            # _LaunchUnit of the grouped launch (weight prefetch across layers)
         self.pf_tensors = ()      # the members' weight operands, as the unit table was built from them
+        self.states = ()          # ... and the members' states (their slab copies live there: _slabs)
         with _groups_lock:
             _groups.append(weakref.ref(self))
 
@@ -799,7 +801,29 @@ class ProjectionGroup:
         except ops._lib.SdnqHipError:
             return False
         self.pf_tensors = tuple(wq for (wq, _, _) in parts)
+        self.states = states
         return True
+
+    def _slabs(self, mm: int, x2: torch.Tensor):
+        """The members' slab copies where the group runs as ONE launch on the 16-bit activation x2 (ops.linear_w8a8_fused_grouped: no row
+        quantization launch, no quantized copy), else None: the row quantizer and the grouped GEMM.  A copy is built by _aq_slab's rule --
+        once, outside a stream capture, kept beside st.mm_weight and dropped with it (_prepare_mm_weights) -- and read from the member's
+        state on every call, so a replaced operand or copy is never served from here."""
+        if not (FUSED_ROWQUANT and FUSED_ROWQUANT_SLABCOPY) or mm != ops.MM_I8 or self.gemm is None or len(set(self.gemm.widths)) != 1:
+            return None
+        if not ops.linear_w8a8_fused_grouped_supported(mm, x2, self.gemm.widths[0], len(self.mods), x2.dtype):
+            return None
+        slabs = []
+        for st, wq in zip(self.states, self.pf_tensors):
+            if st.mm_weight is not wq:
+                return None  # (an operand that is not cached, or not the one the unit table points at)
+            slab = st.mm_slab
+            if slab is None:
+                if (torch.cuda.is_current_stream_capturing() or wq.dim() != 2 or wq.stride(1) != 1 or wq.stride(0) % 16 or wq.data_ptr() % 16):
+                    return None
+                slab = st.mm_slab = ops.aq_slab_pack(wq)
+            slabs.append(slab)
+        return tuple(slabs)
 
     def _float_operands(self, input: torch.Tensor) -> bool:
         """Unit table for the fused dequantize GEMM of the members (float mode), if every member is a signed-int8 row-wise layer."""
@@ -866,10 +890,23 @@ class ProjectionGroup:
             return y
         if not self._begin_compute() or not self._operands(mm):
             return None
-        x2, xq, xs, _, _ = _rowquant_cached(input, input.shape[-1], mm, 0, False, False, None)
-        if PREFETCH_NEXT:
-            _pf_launch(self, self.pf_tensors)
-        outs = ops.scaled_mm_grouped(mm, xq, xs, self.gemm, input.dtype)
+        slabs = None
+        if FUSED_ROWQUANT and input.is_cuda:
+            # the linked q / k / v of a self-attention block: where every tile of the group is resident at once, ONE launch row-quantizes
+            # the activation in LDS and multiplies it by every member's weights (no ops.rowquant, nothing parked in the activation cache)
+            x2 = input if input.dim() == 2 else input.reshape(-1, input.shape[-1])
+            if x2.stride(-1) != 1 or (x2.stride(0) * x2.element_size()) % 16:
+                x2 = x2.contiguous()
+            slabs = self._slabs(mm, x2)
+        if slabs is not None:
+            if PREFETCH_NEXT:
+                _pf_launch(self, slabs)  # (what this launch reads is what the launches in front of it must warm)
+            outs = ops.linear_w8a8_fused_grouped(mm, x2, [(s, ws, b) for s, (_, ws, b) in zip(slabs, self.gemm.keep)], input.dtype)
+        else:
+            x2, xq, xs, _, _ = _rowquant_cached(input, input.shape[-1], mm, 0, False, False, None)
+            if PREFETCH_NEXT:
+                _pf_launch(self, self.pf_tensors)
+            outs = ops.scaled_mm_grouped(mm, xq, xs, self.gemm, input.dtype)
         self.last = (input, key, stream, outs, set(range(len(self.mods))))
         if FAST_PLANS and self._c is not None and "_sdnq_plan" not in mod.__dict__:
             # from now on a member that finds its output waiting takes it without entering this module (csrc/fastpath.cpp: plan_call)

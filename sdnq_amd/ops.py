@@ -552,6 +552,51 @@ def linear_w8a8_fused(mm: int, x2d: torch.Tensor, b_phys: torch.Tensor, sb: torc
     return out
 
 
+_fused_grouped_ok = {}
+
+
+def linear_w8a8_fused_grouped_supported(mm: int, x2d: torch.Tensor, n_member: int, n_members: int, out_dtype: torch.dtype) -> bool:
+    """True where the grouped one-launch Linear (sdnq_hip_linear_w8a8_fused_grouped) takes n_members layers of n_member channels on x2d;
+    memoized per (dtype, M, widths, K, device) like linear_w8a8_fused_supported."""
+    if x2d.dtype not in (torch.bfloat16, torch.float16) or out_dtype != x2d.dtype or not x2d.is_cuda or x2d.stride(0) * 128 >= (1 << 31):
+        return False
+    key = (mm, x2d.dtype, x2d.shape[0], n_member, n_members, x2d.shape[1], x2d.device.index)
+    r = _fused_grouped_ok.get(key)
+    if r is None:
+        with torch.cuda.device(x2d.device):
+            r = _fused_grouped_ok[key] = bool(_lib.load().sdnq_hip_linear_w8a8_fused_grouped_supported(
+                mm, float_code(x2d.dtype), float_code(out_dtype), x2d.shape[0], n_member, n_members, x2d.shape[1]))
+    return r
+
+
+def linear_w8a8_fused_grouped(mm: int, x2d: torch.Tensor, members, out_dtype: torch.dtype):
+    """One launch for layers that read the same activation x2d [M, K], no row-quantization launch in front of it.  `members`:
+    [(slab, ws [N] f32, bias [N] | None)] with slab = aq_slab_pack of the layer's [N, K] int8 operand, one N for all.  Returns one
+    contiguous [M, N] tensor per layer (views of ONE allocation, as scaled_mm_grouped), each bit-identical to linear_w8a8_fused on
+    that layer alone."""
+    m, k = x2d.shape
+    g = len(members)
+    n = int(members[0][1].numel())
+    has_bias = members[0][2] is not None
+    keep = []
+    for (slab, ws, bias) in members:
+        _require_cuda(x2d, slab, ws, bias)
+        if ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() != n or slab.numel() != aq_slab_bytes(n, k) or not slab.is_contiguous():
+            raise _lib.SdnqHipError("linear_w8a8_fused_grouped: every layer needs contiguous float32 scales [N] and the slab copy of an [N, K] operand, one N")
+        if (bias is not None) != has_bias or (has_bias and (bias.numel() != n or bias.dtype != members[0][2].dtype)):
+            raise _lib.SdnqHipError("linear_w8a8_fused_grouped: either every layer has a bias [N] of one dtype or none has")
+        keep.append(None if bias is None else bias.contiguous())
+    ptrs = ctypes.c_void_p * g
+    slabs, sbs = ptrs(*[s.data_ptr() for (s, _, _) in members]), ptrs(*[w.data_ptr() for (_, w, _) in members])
+    biases = ptrs(*[b.data_ptr() for b in keep]) if has_bias else None
+    out = torch.empty((m * g * n,), device=x2d.device, dtype=out_dtype)
+    fused_calls[0] += 1
+    check(_lib.load().sdnq_hip_linear_w8a8_fused_grouped(mm, x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), slabs, sbs, biases,
+                                                         float_code(keep[0].dtype) if has_bias else 0, g, n, out.data_ptr(), float_code(out_dtype),
+                                                         _stream(x2d)), "linear_w8a8_fused_grouped")
+    return [out[m * n * i:m * n * (i + 1)].view(m, n) for i in range(g)]
+
+
 def scaled_mm_nchw(mm: int, a: torch.Tensor, b_phys: torch.Tensor, sa: torch.Tensor, sb: torch.Tensor, bias, out_dtype: torch.dtype,
                    batch: int, pixels: int) -> torch.Tensor:
     """Conv flavour of scaled_mm: rows m = (b, pixel); returns the channel-major image [batch, N, pixels] (the reference's

@@ -1,5 +1,5 @@
 """Lab of the one-launch w8a8 Linear (csrc/gemm_aq.hip) against the two-launch route: graph-replayed pairs on cold / warm operands and the
-phase stamps of the fused kernel.  usage: python tools/aq_lab.py [--forms 0,1] [MxNxK ...]
+phase stamps of the fused kernel.  usage: python tools/aq_lab.py [--forms 0,1] [MxNxK ...] | --grouped [MxGxNxK ...]
 --forms: the forms of the 32 x 256 tile to run one after the other (sdnq_internal_aq_direct: 0 the LDS ring, 1 the direct form on the
 slab copy of the weight; default: -1, whatever the library ships).  Every fused call is handed the slab copy; the ring form ignores it."""
 import ctypes
@@ -20,7 +20,7 @@ if "--forms" in args:
     del args[i:i + 2]
 aq_direct = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z23sdnq_internal_aq_directi")
 aq_direct.argtypes, aq_direct.restype = [ctypes.c_int], None
-shapes = [tuple(int(v) for v in a.split("x")) for a in args] or [(1024, 1280, 1280), (1024, 1280, 640), (4096, 640, 640), (1024, 640, 1280), (2048, 1280, 1280), (1024, 3840, 1280)]
+shapes = [tuple(int(v) for v in a.split("x")) for a in args if "--grouped" not in args] or [(1024, 1280, 1280), (1024, 1280, 640), (4096, 640, 640), (1024, 640, 1280), (2048, 1280, 1280), (1024, 3840, 1280)]
 
 
 def timed(fn, pool, reps=5):
@@ -48,6 +48,54 @@ def timed(fn, pool, reps=5):
     return best
 
 
+def phases(run):
+    """Mean phase stamps of the one-launch kernel over the workgroups of the launch `run` makes (memtime ticks)."""
+    buf = torch.zeros(1024 * 8, dtype=torch.int64, device=dev)
+    aq_trace = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z22sdnq_internal_aq_tracePy")
+    aq_trace.argtypes = [ctypes.c_void_p]
+    aq_trace.restype = None
+    aq_trace(buf.data_ptr())
+    for _ in range(3):
+        buf.zero_()
+        run()
+        torch.cuda.synchronize()
+    aq_trace(None)
+    t = buf.view(1024, 8).cpu()
+    t = t[t[:, 0] > 0]
+    d = (t[:, 1:7] - t[:, 0:6]).double()
+    names = ["entry->issued", "issued->quantized", "K loop", "drain+sync", "epilogue math", "stores"]
+    print("   phases (memtime ticks, mean over", t.shape[0], "workgroups):", ", ".join(f"{nm} {v:.0f}" for nm, v in zip(names, d.mean(0).tolist())),
+          "| total", f"{(t[:, 6] - t[:, 0]).double().mean():.0f}", flush=True)
+
+
+if "--grouped" in args:
+    # the linked q / k / v problem, M x (G x N) x K: the grouped one-launch form (sdnq_hip_linear_w8a8_fused_grouped; the arm is the library's:
+    # a -DSDNQ_AQ_GROUPED_LAB build picks it by SDNQ_HIP_FUSED_ROWQUANT_GROUPED_ARM) against ops.rowquant + ops.scaled_mm_grouped.
+    # usage: python tools/aq_lab.py --grouped [MxGxNxK ...]
+    args.remove("--grouped")
+    for m, g, n, k in ([tuple(int(v) for v in a.split("x")) for a in args] or [(1024, 3, 1280, 1280)]):
+        for pool_n, tag in ((1, "re-read"), (24, "distinct operands")):
+            xs_ = [torch.randn(m, k, device=dev).to(torch.bfloat16) for _ in range(pool_n)]
+            ws = [[torch.randint(-128, 128, (n, k), dtype=torch.int8, device=dev) for _ in range(g)] for _ in range(pool_n)]
+            sb = torch.rand(n, device=dev) * 0.02 + 1e-4
+            bias = torch.randn(n, device=dev).to(torch.bfloat16)
+            groups = [ops.GemmGroup([(w, sb, bias) for w in wl]) for wl in ws]
+            members = [[(ops.aq_slab_pack(w), sb, bias) for w in wl] for wl in ws]
+            idx = list(range(max(pool_n, 32)))
+
+            def two_launches(i):
+                xq, xs, _, _ = ops.rowquant(xs_[i % pool_n], ops.MM_I8)
+                return ops.scaled_mm_grouped(ops.MM_I8, xq, xs, groups[i % pool_n], torch.bfloat16)
+
+            two = timed(two_launches, idx)
+            one = timed(lambda i: ops.linear_w8a8_fused_grouped(ops.MM_I8, xs_[i % pool_n], members[i % pool_n], torch.bfloat16), idx)
+            print(f"{m}x({g}x{n})x{k} {tag:18s}: rowquant + grouped GEMM {two:7.2f} us | one grouped launch {one:7.2f} us", flush=True)
+        a, b = two_launches(0), ops.linear_w8a8_fused_grouped(ops.MM_I8, xs_[0], members[0], torch.bfloat16)
+        torch.cuda.synchronize()
+        print("   same bits:", all(torch.equal(u.view(torch.int16), v.view(torch.int16)) for u, v in zip(a, b)), flush=True)
+        phases(lambda: ops.linear_w8a8_fused_grouped(ops.MM_I8, xs_[0], members[0], torch.bfloat16))
+    sys.exit(0)
+
 for (m, n, k), form in ((sh, f) for sh in shapes for f in forms):
     aq_direct(form)
     if len(forms) > 1:
@@ -71,24 +119,9 @@ for (m, n, k), form in ((sh, f) for sh in shapes for f in forms):
     # phase stamps (shader clock, 100 MHz memtime ticks -> reported in ticks): entry, loads+ring issued, quantized, K loop done, synced, staged, stored
     # (the 32 x 256 tile drains its first two weight stages before "quantized", and its "K loop" has no barrier: thread 0's own loop)
     try:
-        buf = torch.zeros(1024 * 8, dtype=torch.int64, device=dev)
-        aq_trace = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z22sdnq_internal_aq_tracePy")
-        aq_trace.argtypes = [ctypes.c_void_p]
-        aq_trace.restype = None
-        aq_trace(buf.data_ptr())
         x = torch.randn(m, k, device=dev).to(torch.bfloat16)
         b = torch.randint(-128, 128, (n, k), dtype=torch.int8, device=dev)
         slab = ops.aq_slab_pack(b) if ops.aq_slab_bytes(n, k) else None
-        for _ in range(3):
-            buf.zero_()
-            ops.linear_w8a8_fused(ops.MM_I8, x, b, sb, bias, torch.bfloat16, slab)
-            torch.cuda.synchronize()
-        aq_trace(None)
-        t = buf.view(1024, 8).cpu()
-        t = t[t[:, 0] > 0]
-        d = (t[:, 1:7] - t[:, 0:6]).double()
-        names = ["entry->issued", "issued->quantized", "K loop", "drain+sync", "epilogue math", "stores"]
-        print("   phases (memtime ticks, mean over", t.shape[0], "workgroups):", ", ".join(f"{nm} {v:.0f}" for nm, v in zip(names, d.mean(0).tolist())),
-              "| total", f"{(t[:, 6] - t[:, 0]).double().mean():.0f}", flush=True)
+        phases(lambda: ops.linear_w8a8_fused(ops.MM_I8, x, b, sb, bias, torch.bfloat16, slab))
     except Exception as e:  # noqa: BLE001
         print("   trace failed:", e)
