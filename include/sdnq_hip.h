@@ -1015,6 +1015,35 @@ int64_t sdnq_hip_dora_bwd_workspace_bytes(int64_t m, int64_t n);
 int sdnq_hip_dora_bwd(const void* dy, int64_t lddy, const void* y, int64_t ldy, const void* bias, const float* c, int dtype, int64_t m,
                       int64_t n, void* g, float* q, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* ---- merging a low-rank adapter into the stored codes of a Linear weight --------------------------------------------------------------------
+ * sdnq_hip_merge_lowrank: codes -> codes in one launch; replaces dequantize + addmm + quantize (PEFT's merge_and_unload on a quantized
+ * layer), which moves a float [N][K] matrix about five times.  Nothing of size N x K in float is written.
+ *     e[n][k] = fmaf(scale, sum_r f32(up[n][r]) * f32(down[r][k]), w32[n][k])      all float32; w32 and the rank sum as sdnq_hip_dora_normsq
+ *     e       = row_scale[n] * e                                                  one multiply, where row_scale != NULL (DoRA's c)
+ *   and then exactly sdnq_hip_quantize_weight on a float32 source e with the group size of w and qmin / qmax: s = amax / qmax, or
+ *   s = (max - min) / (qmax - qmin) with zp = min (- s * qmin where qmin != 0); q = e / s or (e - zp) / s; integers round half to even, are
+ *   clamped, the NaN of an all-zero group gives code 0, signed packed codes are stored as value - qmin; the float kinds go through the same
+ *   encoders; the packers place the bits as the reference's do (unmasked base elements included).  The result equals
+ *   sdnq_hip_quantize_weight(e) bit for bit: min / max do not depend on the order of their operands.  The same bits on every call; no atomics,
+ *   no workspace, capturable.
+ * w: the stored weight of a Linear layer as sdnq_hip_dora_normsq takes it; SVD factors in the descriptor are allowed and IGNORED (the codes
+ *   are the residual; the factors stay as they are).  A 16-bit scale_dtype rounds w32 as sdnq_hip_dequant does.
+ * out: a descriptor with the format fields of w (n, k, group_size: SDNQ_ERR_SHAPE; storage, kind, bits, exponent, mantissa, native_float:
+ *   SDNQ_ERR_DTYPE) over OTHER memory: out->weight receives the codes (16-byte aligned), out->scale float32 [N][G], out->zero_point float32
+ *   [N][G] for the unsigned kinds (NULL there: SDNQ_ERR_NULL; ignored otherwise).  An output that overlaps an input or another output:
+ *   SDNQ_ERR_SHAPE, nothing launched.
+ * up [n][rank], down [rank][k] contiguous of `dtype` = SDNQ_BF16 / SDNQ_F16 (else SDNQ_ERR_DTYPE, with or without factors); up == down ==
+ *   NULL with row_scale set is a pure row rescale; one of the two NULL, or all three NULL: SDNQ_ERR_NULL.
+ * Built for group sizes 16, 32, 64, 128, 256 (one sweep over K: a group is finished inside one 256-column chunk, by lane shuffles up to 64,
+ *   through LDS above) and row-wise weights (group_size == k: two sweeps, the second recomputes e with the same operations).  Any other
+ *   group size, SDNQ_KIND_CODEBOOK and positions > 1: SDNQ_ERR_UNSUPPORTED before any launch -- the caller composes sdnq_hip_dequant, a
+ *   matrix product and sdnq_hip_quantize_weight / _codebook.
+ * k % 16 == 0, n % 8 == 0, rank % 8 == 0, 8 <= rank <= 256, qmax > qmin (SDNQ_ERR_SHAPE); up, down and out->weight 16-byte, row_scale and
+ *   the output scales 4-byte aligned (SDNQ_ERR_ALIGN); the descriptor's own faults as sdnq_hip_dequant_t reports them.  Everything is
+ *   validated before the launch. */
+int sdnq_hip_merge_lowrank(const SdnqWeight* w, const SdnqWeight* out, const void* up, const void* down, int dtype, int rank,
+                           float scale, const float* row_scale, float qmin, float qmax, sdnq_stream_t stream);
+
 /* ---- trainable low-rank adapters on frozen quantized Conv1d / Conv2d layers ----------------------------------------------------------------
  * PEFT's conv adapter: lora_A is a conv with the layer's kernel, stride, padding and dilation from C_in to `rank` channels, lora_B a 1 x 1
  * conv from `rank` to C_out.  With U = im2col(x) [B OH OW][C kh kw] (sdnq_hip_im2col) the down projection is U . down^T and the gradient of

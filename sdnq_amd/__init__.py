@@ -15,7 +15,7 @@ from .capture import CapturedModel, capture
 from . import torch_ops  # registers the sdnq_hip::* operators with torch.library
 from .loader import accelerate, apply_sdnq_options_to_model, fuse_projections, link_layers, link_projections, load_sdnq_model, post_process_model, save_sdnq_model
 from .training import enable_input_grad
-from .lora import add_lora, load_lora_state_dict, lora_state_dict, remove_lora
+from .lora import add_lora, load_lora_state_dict, lora_state_dict, merge_lora, merge_lora_state_dict, remove_lora
 from .quantizer import (QuantizationMethod, SDNQConfig, apply_sdnq_to_module, sdnq_post_load_quant, sdnq_quantize_layer,
                         sdnq_quantize_layer_weight, sdnq_quantize_layer_weight_dynamic)
 
@@ -34,5 +34,5 @@ __all__ = [
     "CapturedModel", "QuantizationMethod", "SDNQConfig", "SDNQDequantizer", "SDNQLayer", "SDNQLinear", "accelerate", "capture", "fuse_projections", "link_layers", "link_projections",
     "apply_sdnq_options_to_model", "apply_sdnq_to_module", "load_sdnq_model", "save_sdnq_model", "post_process_model", "dtype_dict", "enable_input_grad", "fp8_scaled_mm_func", "get_forward_func",
     "get_sdnq_wrapper_class", "int_scaled_mm_func", "invalidate", "sdnq_post_load_quant", "sdnq_quantize_layer",
-    "sdnq_quantize_layer_weight", "sdnq_quantize_layer_weight_dynamic", "add_lora", "remove_lora", "lora_state_dict", "load_lora_state_dict",
+    "sdnq_quantize_layer_weight", "sdnq_quantize_layer_weight_dynamic", "add_lora", "remove_lora", "lora_state_dict", "load_lora_state_dict", "merge_lora", "merge_lora_state_dict",
 ]

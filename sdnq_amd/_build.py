@@ -59,6 +59,8 @@ UNITS = (
     ("conv_lowrank", "", None),
     # DoRA's norm kernel takes the weight descriptor as one by-value struct, as dequant_t does: no preload
     ("dora", "", None),
+    # the merge kernel takes two descriptors and the pack table by value, as quantize does: no preload
+    ("merge", "", None),
     # attention.hip, attention_var.hip (the forward kernels): keep the MFMA accumulators in VGPRs (the softmax rescales / reads them
     # with VALU every block; in AGPR form the compiler moved 80 registers per 32-key block through v_accvgpr_read/write)
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),

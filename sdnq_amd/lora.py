@@ -88,10 +88,20 @@ optimizer step returns the bits of the inference call.  normsq is recomputed on 
 parameters through raw pointers without bumping ``_version``.  The wrapper runs the same three kernels under ``torch.no_grad()`` / ``eval()``.
 Measured (tools/dora_bench.py, profiles/dora_bench.jsonl): see README.md.
 
+``merge_lora(model)`` folds the adapters into the STORED CODES of their layers (PEFT's ``merge_and_unload``) and takes them off, and
+``merge_lora_state_dict(model, sd, scale)`` applies a PEFT-keyed LoRA file to a quantized model that carries no adapters -- what UIs do on
+every LoRA switch.  Both go through ``_merge_layer``: ``ops.merge_lowrank`` reads the codes once and writes the re-quantized codes, scales
+and zero points of c * (W + s * up @ down) in one launch (csrc/merge.hip: e in registers as the norm kernel forms it, then the quantizer's
+arithmetic; nothing of size N x K in float exists), bit for bit what ``ops.quantize_weight`` gives on the float32 matrix e.  SVD layers keep
+their factors (the codes are the residual); Hadamard layers merge ``ops.hadamard(down)`` (the codes are those of the rotated weight; one
+more rounding of down to the layer dtype); what the kernel is not built for -- group sizes other than 16 .. 256 and row-wise, codebooks,
+ranks above 256 -- takes ``ops.dequant`` + ``torch.addmm`` + ``ops.quantize_weight`` / ``quantize_codebook``.  LOSSY (the codes are
+re-quantized: up to half a step of the new scales) and there is no unmerge; a per-layer error report, merging conv adapters and merging
+DoRA onto layers with SVD factors are not built (listed in ``.skipped``, adapters left on).
+
 Not built, each raising or listed with its sentence: adapters on grouped and 3-D convs, on transposed-conv and embedding layers and on float32
 layers, on convs with string padding or a padding mode other than zeros; dropout on conv adapters; DoRA on conv adapters, caching the norm of
-frozen adapters; per-layer ranks, rsLoRA; merging the adapter into the
-stored codes; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque whole-layer operator: the values of adapter
+frozen adapters; per-layer ranks, rsLoRA; ``torch.compile`` of the wrapper (a compiled model runs it inside the opaque whole-layer operator: the values of adapter
 inference, no gradients) and double backward; the C++ fast plans calling the adapter (the wrapper calls the base forward, which keeps its
 plan); a batched (single-launch) NCHW add of the conv adapter's up projection (one ops.lowrank_add launch per image).
 """
@@ -247,14 +257,15 @@ class QuantizedLinearLoRA(torch.autograd.Function):
 
 
 # ---- DoRA (add_lora(..., use_dora=True)) ------------------------------------------------------------------------------------------------
-def _layer_normsq(layer, down, up) -> torch.Tensor:
+def _layer_normsq(layer, down, up, scale=None) -> torch.Tensor:
     """normsq [N] float32 of a Linear layer: sum_k (W[n][k] + lora_scale * (up . down)[n][k])^2 -- down / up in the layer dtype, or both None
     for || W[n,:] ||^2.  A plain layer: ops.dora_normsq on the stored codes.  A layer with SVD factors or a Hadamard rotation: ops.dequant
-    into the "decoded" slot of sdnq_amd.scratch and ops.dora_normsq_dense on it (one more pass over the weight)."""
+    into the "decoded" slot of sdnq_amd.scratch and ops.dora_normsq_dense on it (one more pass over the weight).  scale: instead of the
+    layer's lora_scale (merge_lora_state_dict: a layer without an adapter)."""
     qw = linear._state(layer).qw
     dq = layer.sdnq_dequantizer
     had = dq.hadamard_group_size if dq.use_hadamard else 0
-    scale = layer.lora_scale if up is not None else 1.0  # (without factors the scale multiplies nothing)
+    scale = (layer.lora_scale if scale is None else scale) if up is not None else 1.0  # (without factors the scale multiplies nothing)
     if not qw.desc.svd_up and not had:
         return ops.dora_normsq(qw, up, down, scale)
     dt = dq.result_dtype
@@ -711,23 +722,25 @@ def _lora_modules(model: torch.nn.Module):
             yield name, module
 
 
+def _take_off(module) -> bool:
+    """One layer's part of `remove_lora`: the forward back, the attributes deleted, the compile plan refreshed.  False: no adapter there."""
+    wrapped = getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None
+    if not wrapped and "lora_down" not in module.__dict__.get("_parameters", {}):
+        return False
+    if wrapped:
+        module.forward_func = module.forward_func._sdnq_lora_previous
+        _refresh_compile_plan(module)
+    for attr in ("lora_down", "lora_up", "lora_scale", "lora_dropout", "lora_magnitude", "lora_dora"):
+        if hasattr(module, attr):
+            delattr(module, attr)
+    return True
+
+
 def remove_lora(model: torch.nn.Module) -> int:
     """Take the adapters off: every layer gets back the very forward it had before `add_lora` and loses lora_down, lora_up,
     lora_scale and lora_dropout (a DoRA layer lora_magnitude and lora_dora as well).  A layer whose forward was re-pointed after
     `add_lora` (see there) keeps the forward it has now and loses the attributes.  Returns the number of layers changed."""
-    count = 0
-    for module in list(model.modules()):
-        wrapped = getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None
-        if not wrapped and "lora_down" not in module.__dict__.get("_parameters", {}):
-            continue
-        if wrapped:
-            module.forward_func = module.forward_func._sdnq_lora_previous
-            _refresh_compile_plan(module)
-        for attr in ("lora_down", "lora_up", "lora_scale", "lora_dropout", "lora_magnitude", "lora_dora"):
-            if hasattr(module, attr):
-                delattr(module, attr)
-        count += 1
-    return count
+    return sum(_take_off(module) for module in list(model.modules()))
 
 
 _PEFT_PREFIX = "base_model.model."
@@ -746,12 +759,8 @@ def lora_state_dict(model: torch.nn.Module) -> dict:
     return sd
 
 
-def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
-    """Copy `sd` (the keys of `lora_state_dict`; a leading ``base_model.model.`` and an adapter name as in ``lora_A.default.weight`` are
-    accepted) into the adapters `add_lora` put on `model`.  Every layer with an adapter must find both its keys and every key its layer,
-    with the shapes of the registered parameters: KeyError / ValueError otherwise.  A DoRA layer needs its magnitude as well, as
-    ``<module>.lora_magnitude_vector.weight``, PEFT's ``lora_magnitude_vector.<adapter>.weight`` or the bare ``lora_magnitude_vector.<adapter>``;
-    a magnitude key for a layer without DoRA is a KeyError, as any unknown key.  Returns the number of layers loaded."""
+def _split_keys(sd: dict, who: str) -> dict:
+    """{module name: {"A": lora_A, "B": lora_B, "M": magnitude}} of a PEFT-keyed state dict (the key forms of `load_lora_state_dict`)."""
     import re
     found = {}
     for key, value in sd.items():
@@ -760,10 +769,20 @@ def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
         if m is None:  # DoRA's magnitude: .weight, .<adapter>.weight, or the bare .<adapter> of older PEFT files
             mm = re.fullmatch(r"(.*)\.lora_magnitude_vector(?:\.weight|\.[^.]+\.weight|\.[^.]+)", bare)
             if mm is None:
-                raise KeyError(f"load_lora_state_dict: {key!r} is not a <module>.lora_A.weight / <module>.lora_B.weight key")
+                raise KeyError(f"{who}: {key!r} is not a <module>.lora_A.weight / <module>.lora_B.weight key")
             found.setdefault(mm.group(1), {})["M"] = value
             continue
         found.setdefault(m.group(1), {})[m.group(2)] = value
+    return found
+
+
+def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
+    """Copy `sd` (the keys of `lora_state_dict`; a leading ``base_model.model.`` and an adapter name as in ``lora_A.default.weight`` are
+    accepted) into the adapters `add_lora` put on `model`.  Every layer with an adapter must find both its keys and every key its layer,
+    with the shapes of the registered parameters: KeyError / ValueError otherwise.  A DoRA layer needs its magnitude as well, as
+    ``<module>.lora_magnitude_vector.weight``, PEFT's ``lora_magnitude_vector.<adapter>.weight`` or the bare ``lora_magnitude_vector.<adapter>``;
+    a magnitude key for a layer without DoRA is a KeyError, as any unknown key.  Returns the number of layers loaded."""
+    found = _split_keys(sd, "load_lora_state_dict")
     mods = dict(_lora_modules(model))
     missing = [n for n in found if n not in mods]
     if missing:
@@ -788,3 +807,205 @@ def load_lora_state_dict(model: torch.nn.Module, sd: dict) -> int:
                 p.copy_(v)
         count += 1
     return count
+
+
+# ---- merging an adapter into the stored codes (merge_lora, merge_lora_state_dict) --------------------------------------------------------
+_MERGE_FORCE_COMPOSITION = False  # tests: send layers the fused kernel serves through the composition route
+_MERGE_FIELDS = ("weight", "scale", "zero_point")
+
+
+class MergeResult(int):
+    """What `merge_lora()` / `merge_lora_state_dict()` return: an int (the number of layers whose codes were rewritten) that also carries
+    `.merged` -- their qualified names -- and `.skipped` -- [(qualified module name, reason)] of the layers left as they were."""
+
+    def __new__(cls, merged, skipped):
+        r = super().__new__(cls, len(merged))
+        r.merged, r.skipped = list(merged), list(skipped)
+        return r
+
+
+def merge_unsupported_reason(module, dora: bool = False) -> str | None:
+    """None when an adapter on `module` (an SDNQ layer) can be merged into its codes; otherwise the sentence that says why not.  dora: the
+    adapter carries a DoRA magnitude."""
+    from .common import linear_types
+    dq = module.sdnq_dequantizer
+    cls = getattr(dq, "layer_class_name", None)
+    if cls not in linear_types:
+        return f"{cls}: merging is built for quantized Linear layers (merging conv adapters is not built)"
+    fwd = getattr(module, "forward_func", None)
+    if getattr(fwd, "_sdnq_lora_base", None) is None:  # no adapter on it: what add_lora would say about the layer
+        why = lora_unsupported_reason(module)
+        if why is not None:
+            return why
+    if dora and getattr(module, "svd_up", None) is not None:
+        return ("DoRA on a layer with SVD factors: merging it is not built (the row scale c would have to reach svd_up as well as the "
+                "codes)")
+    return None
+
+
+def _like(old: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """`values` (the logical shape of `old`) in a new tensor with the shape, stride and dtype of `old`."""
+    new = torch.empty_strided(old.size(), old.stride(), dtype=old.dtype, device=old.device)
+    if values.dtype != old.dtype and not values.dtype.is_floating_point and values.element_size() == old.element_size():
+        values = values.view(old.dtype)  # the same code bits under the layer's integer / float8 spelling
+    new.copy_(values)
+    return new
+
+
+def _merge_layer(module, down: torch.Tensor, up: torch.Tensor | None, scale: float, c: torch.Tensor | None) -> str:
+    """Rewrite the stored codes, scale and zero point of the Linear `module` as the quantization of c[:, None] * (W + scale * up @ down): W
+    the float32 value of the stored codes (for a layer with SVD factors the residual -- the factors stay; for a Hadamard layer the rotated
+    weight -- `down` is rotated along K first, ops.hadamard: one more rounding of down to the layer dtype).  down [R, K] / up [N, R]
+    contiguous in the layer dtype, R % 8 == 0, or both None with c; c [N] float32 or None.  Returns the route, "fused"
+    (ops.merge_lowrank: one launch) or "composed" (ops.dequant to float32, torch.addmm, ops.quantize_weight / quantize_codebook: what the
+    kernel reports unsupported -- other group sizes, codebooks -- and ranks above 256).  The quantizer works in float32 and the results
+    are cast to the dtypes the module stores afterwards, as the loader does.  The new tensors are installed as NEW parameter objects with
+    the shape, stride and dtype of the old ones, all at the end: a failure before leaves the layer as it was.  The layer's kernel state,
+    fast-path plan, projection group, slab copy and 4-bit tables rebuild on the changed parameter identity (linear._state)."""
+    dq = module.sdnq_dequantizer
+    qw = linear._state(module).qw
+    n, k = qw.n, qw.k
+    had = dq.hadamard_group_size if dq.use_hadamard else 0
+    with torch.no_grad():
+        if had and down is not None:
+            down = ops.hadamard(down, had)
+        rank = 0 if up is None else up.shape[1]
+        codebook = bool(getattr(dq, "use_codebook", False))
+        if ops.merge_lowrank_supported(qw) and rank <= 256 and not _MERGE_FORCE_COMPOSITION:
+            route = "fused"
+            codes, sc, zp = ops.merge_lowrank(qw, up, down, scale, c, weights_dtype=dq.weights_dtype)
+        else:
+            route = "composed"
+            e = ops.dequant(qw, torch.float32, 0, use_svd=False)
+            if up is not None:
+                e = torch.addmm(e, up.float(), down.float(), alpha=float(scale))
+            if c is not None:
+                e = c[:, None] * e
+            if codebook:
+                codes, sc = ops.quantize_codebook(e, dq.weights_dtype, qw.group_size)
+                zp = None
+            else:
+                codes, sc, zp = ops.quantize_weight(e, dq.weights_dtype, qw.group_size)
+        old = {name: _attr(module, name) for name in _MERGE_FIELDS}
+        w_old = old["weight"]
+        if dq.weight_is_transposed:  # logical [K, N] over the physical [N][K] bytes
+            w_new = _like(w_old, codes.reshape(n, k).t())
+        else:
+            w_new = _like(w_old, codes.reshape(w_old.shape))
+        new = {"weight": w_new, "scale": _like(old["scale"], sc.reshape(old["scale"].shape).to(old["scale"].dtype))}
+        if old["zero_point"] is not None:
+            new["zero_point"] = _like(old["zero_point"], zp.reshape(old["zero_point"].shape).to(old["zero_point"].dtype))
+    for name, t in new.items():  # nothing above touched the module
+        if name in module._parameters:
+            module._parameters[name] = torch.nn.Parameter(t, requires_grad=False)
+        elif name in module._buffers:
+            module._buffers[name] = t
+        else:
+            setattr(module, name, t)
+    return route
+
+
+def _warn_skipped(who: str, skipped) -> None:
+    if skipped:
+        import warnings
+        warnings.warn(f"sdnq_amd.{who}: {len(skipped)} layer(s) were not merged: "
+                      + "; ".join(f"{n} ({w})" for n, w in skipped[:8]) + (" ..." if len(skipped) > 8 else ""), stacklevel=3)
+
+
+def merge_lora(model: torch.nn.Module, targets=None) -> MergeResult:
+    """Fold the adapters `add_lora` put on `model` into the stored codes of their layers (PEFT's ``merge_and_unload``) and take them off:
+    afterwards the layer is a plain quantized layer again -- no low-rank launches, no norm launch -- whose weight is the re-quantization
+    of W + lora_scale * up @ down (DoRA: of c[:, None] * that, c = lora_magnitude / || W + lora_scale * up @ down ||), and
+    ``save_sdnq_model`` writes it as a plain quantized checkpoint.  `targets` selects layers as in `add_lora`.  The factors are taken in
+    the layer dtype, as the forward casts them; dropout is ignored (``eval()`` semantics).  Per layer: `_merge_layer`, then what
+    `remove_lora` does.  LOSSY: the codes are re-quantized (an error of up to half a step of the NEW scales on top of the adapter's
+    effect) and there is no unmerge; keep ``lora_state_dict(model)`` if the adapter is to be used again.  Conv adapters and DoRA on layers
+    with SVD factors are not merged: they are listed in ``.skipped`` with one sentence each and in ONE ``warnings.warn``, and keep their
+    adapters.  A per-layer error report is not built."""
+    pick = _selected(targets)
+    merged, skipped = [], []
+    for name, module in list(_lora_modules(model)):
+        if not pick(name):
+            continue
+        dora = bool(getattr(module, "lora_dora", False))
+        why = merge_unsupported_reason(module, dora)
+        if why is not None:
+            skipped.append((name or type(module).__name__, why))
+            continue
+        dt = module.sdnq_dequantizer.result_dtype
+        with torch.no_grad():
+            down = _attr(module, "lora_down").detach().to(dt).contiguous()
+            up = _attr(module, "lora_up").detach().to(dt).contiguous()
+            c = None
+            if dora:
+                c = (_attr(module, "lora_magnitude").detach().float() / torch.sqrt(_layer_normsq(module, down, up))).contiguous()
+        _merge_layer(module, down, up, float(module.lora_scale), c)
+        _take_off(module)
+        merged.append(name or type(module).__name__)
+    _warn_skipped("merge_lora", skipped)
+    return MergeResult(merged, skipped)
+
+
+def pad_rank(down: torch.Tensor, up: torch.Tensor):
+    """(down [R', K], up [N, R']) with R' the next multiple of 8 (at least 8): zero rows of down, zero columns of up -- the same product."""
+    r = down.shape[0]
+    r8 = max(8, -(-r // 8) * 8)
+    if r8 == r:
+        return down.contiguous(), up.contiguous()
+    d = down.new_zeros((r8, down.shape[1]))
+    u = up.new_zeros((up.shape[0], r8))
+    d[:r] = down
+    u[:, :r] = up
+    return d, u
+
+
+def merge_lora_state_dict(model: torch.nn.Module, sd: dict, scale: float = 1.0) -> MergeResult:
+    """Apply a PEFT-keyed LoRA file to a quantized `model` that carries NO adapters: every ``<module>.lora_A.weight`` [r, K] /
+    ``<module>.lora_B.weight`` [N, r] pair of `sd` (the key forms of `load_lora_state_dict`) is folded into the codes of its layer as
+    W + scale * B @ A -- the caller computes ``scale = alpha / r`` (alpha is not in the file).  The rank is read from the tensors; one that
+    is no multiple of 8 is padded with zero rows / columns (`pad_rank`).  A ``lora_magnitude_vector`` key makes the layer's merge DoRA's.
+    The factors are cast to the layer dtype.  KeyError: a key that names no quantized layer of `model`, or a layer with one factor only;
+    ValueError: a factor of the wrong shape, or a layer that carries an adapter (``merge_lora`` merges those).  Everything is checked
+    before the first layer changes.  Conv layers, float32 layers, layers that do not run on the MI355X forwards and DoRA on layers with
+    SVD factors are listed in ``.skipped`` (ONE warning) and left alone.  Lossy, no unmerge: see `merge_lora`."""
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"merge_lora_state_dict: scale must be finite (got {scale})")
+    found = _split_keys(sd, "merge_lora_state_dict")
+    mods = {n: m for n, m in model.named_modules() if getattr(m, "sdnq_dequantizer", None) is not None}
+    missing = [n for n in found if n not in mods]
+    if missing:
+        raise KeyError(f"merge_lora_state_dict: {missing[:4]} name no quantized layer of the model")
+    work, skipped = [], []
+    for name, got in found.items():
+        module = mods[name]
+        if not {"A", "B"} <= set(got):
+            raise KeyError(f"merge_lora_state_dict: {name} needs both lora_A.weight and lora_B.weight (got {sorted(got)})")
+        if getattr(getattr(module, "forward_func", None), "_sdnq_lora_base", None) is not None:
+            raise ValueError(f"merge_lora_state_dict: {name} carries an adapter (merge_lora(model) merges the adapters add_lora put on; "
+                             "remove_lora(model) takes them off)")
+        why = merge_unsupported_reason(module, "M" in got)
+        if why is not None:
+            skipped.append((name, why))
+            continue
+        dq = module.sdnq_dequantizer
+        n, k = int(dq.out_features), int(dq.in_features)
+        a, b = got["A"], got["B"]
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != k or b.shape[0] != n or a.shape[0] != b.shape[1] or a.shape[0] < 1:
+            raise ValueError(f"merge_lora_state_dict: {name} needs lora_A [r, {k}] and lora_B [{n}, r] (got {tuple(a.shape)}, {tuple(b.shape)})")
+        if "M" in got and tuple(got["M"].shape) != (n,):
+            raise ValueError(f"merge_lora_state_dict: {name}.lora_magnitude_vector has shape {tuple(got['M'].shape)}, the layer {n} rows")
+        work.append((name, module, a, b, got.get("M")))
+    merged = []
+    for name, module, a, b, mag in work:
+        dt = module.sdnq_dequantizer.result_dtype
+        dev = module.weight.device
+        with torch.no_grad():
+            down, up = pad_rank(a.detach().to(device=dev, dtype=dt), b.detach().to(device=dev, dtype=dt))
+            c = None
+            if mag is not None:
+                c = (mag.detach().to(device=dev, dtype=torch.float32) / torch.sqrt(_layer_normsq(module, down, up, scale))).contiguous()
+        _merge_layer(module, down, up, scale, c)
+        merged.append(name)
+    _warn_skipped("merge_lora_state_dict", skipped)
+    return MergeResult(merged, skipped)

@@ -1316,6 +1316,96 @@ def dora_normsq_dense(wd: torch.Tensor, up: torch.Tensor | None = None, down: to
     return out
 
 
+def _code_buffer(storage: int, bits: int, n: int, k: int, dev) -> torch.Tensor:
+    """The flat buffer the quantizer kernels write the codes of an [N, K] weight into."""
+    if storage == _lib.ST_PACKED_U8:
+        return torch.empty((n * k // 8 * bits,), device=dev, dtype=torch.uint8)
+    if storage == _lib.ST_PACKED_I16:
+        return torch.empty((n * k // 16 * bits,), device=dev, dtype=torch.int16)
+    return torch.empty((n, k), device=dev, dtype=torch.uint8 if storage == _lib.ST_RAW8 else torch.int16)
+
+
+def _code_view(raw: torch.Tensor, weights_dtype: str) -> torch.Tensor:
+    """`raw` shaped and typed as ``quantize_weight`` returns the codes of `weights_dtype`."""
+    from . import packed as _packed
+    ent = dtype_dict[weights_dtype]
+    bits = ent["num_bits"]
+    if ent["is_packed"] and bits not in (8, 16):
+        _g, words, _wb = _packed._GEOM[bits]
+        return raw if words == 1 else raw.view(-1, words)
+    if ent["is_packed"]:  # custom float8 / float16 codes (pack_float returns uint8 / uint16)
+        return raw.view(torch.uint16) if bits == 16 else raw
+    return raw.view(ent["torch_dtype"]) if ent["torch_dtype"].itemsize == raw.element_size() else raw
+
+
+def _format_fields(storage, kind, bits, ebits, mbits, native) -> tuple:
+    """What tells two storage formats apart: a codebook's codes are unsigned integers, and integers have no exponent / mantissa split."""
+    kind = _lib.KIND_UINT if kind == _lib.KIND_CODEBOOK else kind
+    if kind in (_lib.KIND_INT, _lib.KIND_UINT):
+        return storage, kind, bits
+    return storage, kind, bits, ebits, mbits, native
+
+
+def _format_name(d) -> str:
+    """The key of ``dtype_dict`` whose storage fields are those of the descriptor `d` (a codebook's: its unsigned integer codes)."""
+    want = _format_fields(d.storage, d.kind, d.bits, d.exponent, d.mantissa, d.native_float)
+    for name in dtype_dict:
+        try:
+            if _format_fields(*_storage_kind(name)) == want:
+                return name
+        except (_lib.SdnqHipError, KeyError):
+            continue
+    raise _lib.SdnqHipError(f"no weights_dtype has the storage fields {want}")
+
+
+def merge_lowrank_supported(qw: QuantWeight) -> bool:
+    """True where sdnq_hip_merge_lowrank is built for the format of `qw` (else it returns SDNQ_ERR_UNSUPPORTED): no codebook, a Linear
+    weight, a group size of 16, 32, 64, 128 or 256 or one scale per row."""
+    d = qw.desc
+    return d.kind != _lib.KIND_CODEBOOK and d.positions <= 1 and (qw.group_size in (16, 32, 64, 128, 256) or qw.group_size == qw.k)
+
+
+def merge_lowrank(qw: QuantWeight, up: torch.Tensor | None, down: torch.Tensor | None, scale: float = 1.0,
+                  row_scale: torch.Tensor | None = None, weights_dtype: str | None = None):
+    """sdnq_hip_merge_lowrank: (codes, scale [N, G] float32, zero_point [N, G] float32 | None) of the re-quantized
+    ``row_scale[:, None] * (w32 + scale * up @ down)`` from the stored codes of `qw` in ONE launch -- every element
+    e = fma(scale, acc, w32) in float32 (``dora_normsq``'s definitions; SVD factors of `qw` are ignored: the codes are the residual), then
+    the arithmetic and the storage of ``quantize_weight`` with the group size of `qw`: the outputs have the shapes and dtypes
+    ``quantize_weight`` returns and are its bits on the float32 matrix e.  up [N, R] / down [R, K] contiguous bfloat16 / float16, or both
+    None with `row_scale` [N] float32 for a pure row rescale.  `weights_dtype` names the format of `qw` (the key of ``dtype_dict``, whose
+    min / max are the clamp; None: found from the descriptor's fields).  ``merge_lowrank_supported(qw)`` says beforehand what the kernel is
+    built for; it raises SdnqHipError with status SDNQ_ERR_UNSUPPORTED for what the kernel is not built for (group
+    sizes other than 16 .. 256 powers of two and row-wise, codebooks, conv weights): callers compose ``dequant`` + ``quantize_weight``."""
+    r, code = _dora_factors("merge_lowrank", qw.n, qw.k, up, down)
+    if up is None and row_scale is None:
+        raise _lib.SdnqHipError("merge_lowrank: nothing to merge (up, down and row_scale are all None)")
+    d0 = qw.desc
+    if weights_dtype is None:
+        weights_dtype = _format_name(d0)
+    ent = dtype_dict[weights_dtype]
+    storage, kind, bits, ebits, mbits, native = _storage_kind(weights_dtype)
+    if _format_fields(storage, kind, bits, ebits, mbits, native) != _format_fields(d0.storage, d0.kind, d0.bits, d0.exponent, d0.mantissa,
+                                                                                   d0.native_float):
+        raise _lib.SdnqHipError(f"merge_lowrank: weights_dtype {weights_dtype} is not the format of qw")
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or tuple(row_scale.shape) != (qw.n,) or not row_scale.is_contiguous():
+            raise _lib.SdnqHipError(f"merge_lowrank: row_scale must be a contiguous float32 [N] = [{qw.n}] (got {row_scale.dtype} "
+                                    f"{tuple(row_scale.shape)})")
+    dev = qw.keep[0].device
+    _require_cuda(qw.keep[0], up, down, row_scale)
+    g = qw.k // qw.group_size
+    raw = _code_buffer(storage, bits, qw.n, qw.k, dev)
+    sc = torch.empty((qw.n, g), device=dev, dtype=torch.float32)
+    zp = torch.empty((qw.n, g), device=dev, dtype=torch.float32) if ent["is_unsigned"] else None
+    d = SdnqWeight(weight=raw.data_ptr(), scale=sc.data_ptr(), zero_point=_ptr(zp), svd_up=None, svd_down=None, n=qw.n, k=qw.k,
+                   group_size=qw.group_size, svd_rank=0, svd_dtype=0, storage=d0.storage, kind=d0.kind, bits=d0.bits, exponent=d0.exponent,
+                   mantissa=d0.mantissa, native_float=d0.native_float, positions=d0.positions)
+    check(_lib.load().sdnq_hip_merge_lowrank(ctypes.byref(d0), ctypes.byref(d), _ptr(up), _ptr(down), BF16 if code is None else code, r,
+                                             float(scale), _ptr(row_scale), float(ent["min"]), float(ent["max"]), _stream(raw)),
+          "merge_lowrank")
+    return _code_view(raw, weights_dtype), sc, zp
+
+
 def _dora_vectors(what: str, n: int, dt: torch.dtype, c: torch.Tensor, bias) -> None:
     if c.dtype != torch.float32 or tuple(c.shape) != (n,) or not c.is_contiguous() or c.data_ptr() % 16:
         raise _lib.SdnqHipError(f"{what}: c must be a contiguous, 16-byte aligned float32 vector [N = {n}] (got {c.dtype}, {tuple(c.shape)})")
@@ -1685,8 +1775,6 @@ def quantize_weight(weight2d: torch.Tensor, weights_dtype: str, group_size: int,
     HIP replacement of quantize_weight + pack_int / pack_float (quant_utils.py:28-56, packed_int/__init__.py:77-80,
     packed_float.py:27-82); `group_size` == K for row-wise.  positions = P > 1: conv weight flattened to [N, C_in * P],
     group_size counts channels, scales are [N, (C_in / group_size) * P]."""
-    from .common import dtype_dict
-    from . import packed as _packed
     _require_cuda(weight2d)
     if weight2d.dtype not in _FLOAT_CODE:
         raise _lib.SdnqHipError(f"quantize_weight: unsupported source dtype {weight2d.dtype}")
@@ -1696,14 +1784,7 @@ def quantize_weight(weight2d: torch.Tensor, weights_dtype: str, group_size: int,
     storage, kind, bits, ebits, mbits, native = _storage_kind(weights_dtype)
     g = (k // positions) // group_size * positions
     dev = w.device
-    if storage == _lib.ST_PACKED_U8:
-        raw = torch.empty((n * k // 8 * bits,), device=dev, dtype=torch.uint8)
-    elif storage == _lib.ST_PACKED_I16:
-        raw = torch.empty((n * k // 16 * bits,), device=dev, dtype=torch.int16)
-    elif storage == _lib.ST_RAW8:
-        raw = torch.empty((n, k), device=dev, dtype=torch.uint8)
-    else:
-        raw = torch.empty((n, k), device=dev, dtype=torch.int16)
+    raw = _code_buffer(storage, bits, n, k, dev)
     scale = torch.empty((n, g), device=dev, dtype=torch.float32)
     zp = torch.empty((n, g), device=dev, dtype=torch.float32) if ent["is_unsigned"] else None
     d = SdnqWeight(weight=raw.data_ptr(), scale=scale.data_ptr(), zero_point=_ptr(zp), svd_up=None, svd_down=None, n=n, k=k,
@@ -1711,14 +1792,7 @@ def quantize_weight(weight2d: torch.Tensor, weights_dtype: str, group_size: int,
                    mantissa=mbits, native_float=native, positions=positions)
     check(_lib.load().sdnq_hip_quantize_weight(w.data_ptr(), float_code(w.dtype), w.stride(0), ctypes.byref(d), float(ent["min"]),
                                                float(ent["max"]), _stream(w)), "quantize_weight")
-    if ent["is_packed"] and bits not in (8, 16):
-        _g, words, _wb = _packed._GEOM[bits]
-        codes = raw if words == 1 else raw.view(-1, words)
-    elif ent["is_packed"]:  # custom float8 / float16 codes (pack_float returns uint8 / uint16)
-        codes = raw.view(torch.uint16) if bits == 16 else raw
-    else:
-        codes = raw.view(ent["torch_dtype"]) if ent["torch_dtype"].itemsize == raw.element_size() else raw
-    return codes, scale, zp
+    return _code_view(raw, weights_dtype), scale, zp
 
 
 def _adamw_tail(p: torch.Tensor, lr, betas, step, weight_decay, clip, grad_scale, sr_param, sr_state, seed, offset):
