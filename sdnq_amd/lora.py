@@ -35,7 +35,7 @@ An element is dropped iff its 16 random bits are below T = min(65535, max(1, rou
 probability is T / 65536, within 2^-17 of p (at least 2^-16).  The survivors are not rescaled in the operand; 1 / (1 - p) goes into the
 float32 scale the kernels take anyway, scale_d = float32(scale * 65536 / (65536 - T)) (``dropout_scale``).  Each forward call reads
 (initial_seed, offset) from torch's device generator and advances the offset by 4, as ``sdnq_amd.optim`` does for its stochastic stores;
-the backward keeps (seed, offset, T) as three Python ints beside what it saves anyway.  ``torch.cuda.manual_seed`` reproduces a run, and
+the backward keeps (T, seed, offset) as three Python ints beside what it saves anyway.  ``torch.cuda.manual_seed`` reproduces a run, and
 ``torch.utils.checkpoint`` (which restores the generator state for its recomputation) replays the same mask.  While a stream is being
 captured an active dropout raises (the offset is drawn on the host: a replay would repeat one mask); ``dropout=0`` and ``eval()`` capture
 as before.  ``eval()`` and ``dropout=0`` run exactly the calls above without the mask: the same entry points and bits as before.
@@ -124,11 +124,11 @@ def _workspace(dev: torch.device, nbytes: int):
 
 
 def _factor_grad(a: torch.Tensor, b: torch.Tensor, scale: float, out_t: bool, out_dtype: torch.dtype, drop=None) -> torch.Tensor:
-    """scale * a^T . b; drop = (seed, offset, T): a under its dropout mask."""
+    """scale * a^T . b; drop: None or the triple of _draw_dropout -- a under its dropout mask."""
     ws = _workspace(a.device, ops.lowrank_grad_workspace_bytes(a.shape[0], a.shape[1], b.shape[1])) if a.shape[0] else None
     if drop is None:
         return ops.lowrank_grad(a, b, scale, out_t=out_t, out_dtype=out_dtype, workspace=ws)
-    return ops.lowrank_grad_dropout(a, b, scale, drop[2], drop[0], drop[1], out_t=out_t, out_dtype=out_dtype, workspace=ws)
+    return ops.lowrank_grad_dropout(a, b, scale, *drop, out_t=out_t, out_dtype=out_dtype, workspace=ws)
 
 
 def _check_call(layer, input: torch.Tensor) -> torch.dtype:
@@ -153,8 +153,9 @@ def dropout_scale(scale: float, threshold: int) -> float:
 
 
 def _draw_dropout(layer, dev: torch.device):
-    """None when dropout is off for this call; otherwise (seed, offset, T) -- (initial_seed, offset) of torch's device generator, whose
-    offset advances by 4 (torch keeps it a multiple of 4), as SDNQOptimizer.step draws for its stochastic stores."""
+    """None when dropout is off for this call; otherwise ops._Dropout(T, seed, offset), the triple in the order every entry point takes it
+    -- (initial_seed, offset) of torch's device generator, whose offset advances by 4 (torch keeps it a multiple of 4), as
+    SDNQOptimizer.step draws for its stochastic stores."""
     p = float(getattr(layer, "lora_dropout", 0.0))
     if p <= 0.0 or not layer.training:
         return None
@@ -164,23 +165,23 @@ def _draw_dropout(layer, dev: torch.device):
     gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
     seed, offset = int(gen.initial_seed()), int(gen.get_offset())
     gen.set_offset(offset + 4)
-    return seed, offset, dropout_threshold(p)
+    return ops._Dropout(dropout_threshold(p), seed, offset)
 
 
 def _scale(layer, drop) -> float:
-    return layer.lora_scale if drop is None else dropout_scale(layer.lora_scale, drop[2])
+    return layer.lora_scale if drop is None else dropout_scale(layer.lora_scale, drop.threshold)
 
 
 def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor, drop=None, dora=None):
     """(y, x2d, t): the three steps of the forward with gradients off.  down / up: the factors in the layer dtype.  drop: None or the
-    (seed, offset, T) of _draw_dropout -- then t comes from the masked x and the scale carries 1 / (1 - p).  dora: None or (c [N] float32,
+    triple of _draw_dropout -- then t comes from the masked x and the scale carries 1 / (1 - p).  dora: None or (c [N] float32,
     bias in the layer dtype | None) -- then the add is ops.lowrank_add_dora."""
     y = base(layer, input)
     x2d = training._rows(input)
     n = up.shape[0]
     if x2d.shape[0] == 0:
         return y, x2d, x2d.new_empty((0, down.shape[0]))
-    t = ops.lowrank_down(x2d, down) if drop is None else ops.lowrank_down_dropout(x2d, down, drop[2], drop[0], drop[1])
+    t = ops.lowrank_down(x2d, down) if drop is None else ops.lowrank_down_dropout(x2d, down, *drop)
     try:
         y2d = y.view(-1, n)
     except RuntimeError:
@@ -198,61 +199,90 @@ def _run(layer, base, input: torch.Tensor, down: torch.Tensor, up: torch.Tensor,
     return y, x2d, t
 
 
+def _zero_grads(grad_output: torch.Tensor, input_shape, need_x: bool, *params):
+    """The gradients of a call without rows: (zeros of `input_shape` in grad_output's dtype, or None without `need_x`; then for each of
+    `params` -- a factor or c where its gradient is needed, None where not -- zeros like it, or None)."""
+    return (grad_output.new_zeros(input_shape) if need_x else None, *(None if p is None else torch.zeros_like(p) for p in params))
+
+
+def _project_grad(g2d: torch.Tensor, up2d: torch.Tensor) -> torch.Tensor:
+    """g_t [M][rank] = g2d . up2d, up2d [N][rank] cast to the dtype of g2d: ops.lowrank_down on its transpose."""
+    return ops.lowrank_down(g2d, up2d.to(g2d.dtype).t().contiguous())
+
+
+def _linear_forward(ctx, layer, base, input, down, up, bias, c=None):
+    """The forward of QuantizedLinearLoRA (c None) and of QuantizedLinearDoRA (c [N] float32).  Saves x2d, t, down, up -- and with c: c,
+    the OUTPUT y and the bias (None without one).  Without c nothing of DoRA is touched: plain LoRA's entry points and saved tensors."""
+    dt = _check_call(layer, input)
+    ctx.drop = drop = _draw_dropout(layer, input.device)
+    with torch.no_grad():
+        if c is not None:
+            c = c.detach().contiguous()
+        y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), drop, None if c is None else (c, _dora_bias(bias, dt)))
+    ctx.layer, ctx.input_shape = layer, input.shape
+    ctx.bias_dtype = None if bias is None else bias.dtype
+    ctx.save_for_backward(x2d, t, down, up, *(() if c is None else (c, y, bias)))
+    return y
+
+
+def _linear_backward(ctx, grad_output, need_x, need_down, need_up, need_c, need_bias):
+    """(grad_input, grad_down, grad_up, grad_c, grad_bias), None where not needed: the backward chain of the module docstring, once for
+    both Linear Functions.  A forward that saved c (DoRA) first turns dY into g = round(dY * c) (ops.dora_bwd, with q for grad_c only
+    where the magnitude needs a gradient) and runs the chain on g; grad_bias comes from the unscaled dY either way."""
+    layer = ctx.layer
+    x2d, t, down, up, *dora = ctx.saved_tensors
+    training._check_grad_output(layer, grad_output, "Linear")
+    dy2d = training._rows(grad_output)
+    drop = ctx.drop
+    dt, scale = dy2d.dtype, _scale(layer, drop)
+    grad_c = grad_bias = None
+    m, n = dy2d.shape
+    if m == 0:
+        grad_input, grad_down, grad_up, grad_c = _zero_grads(grad_output, ctx.input_shape, need_x, down if need_down else None,
+                                                              up if need_up else None, dora[0] if need_c else None)
+    else:
+        grad_input = grad_down = grad_up = None
+        g2d = dy2d
+        if dora:
+            c, y, bias = dora
+            ws = _workspace(dy2d.device, ops.dora_bwd_workspace_bytes(m, n)) if need_c else None
+            g2d, q = ops.dora_bwd(dy2d, training._rows(y) if need_c else None, _dora_bias(bias, dt), c, want_q=need_c, workspace=ws)
+            if need_c:
+                grad_c = torch.where(c != 0, q / c, torch.zeros_like(q))
+        g_t = None
+        if need_x or need_down:
+            g_t = _project_grad(g2d, up)
+        if need_x:
+            gi2d = training._linear_base_grad(layer, g2d)
+            if drop is None:
+                ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
+            else:
+                ops.lowrank_add_dropout(g_t, down.to(dt).t().contiguous(), gi2d, scale, *drop)
+            grad_input = gi2d.view(ctx.input_shape)
+        if need_up:
+            grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
+        if need_down:
+            grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype, drop)
+    if need_bias:
+        grad_bias = dy2d.sum(0).to(ctx.bias_dtype)
+    return grad_input, grad_down, grad_up, grad_c, grad_bias
+
+
 class QuantizedLinearLoRA(torch.autograd.Function):
     """y = layer(input) + scale * (input . down^T) . up^T with a graph: gradients for the input, the two factors and the bias; the
     weight, scale, zero point and SVD factors of the layer are frozen and get none.  Saves the module, the flattened input and t -- and,
-    with dropout active, the three ints (seed, offset, T) from which the backward's kernels recompute the mask.  Not differentiable
+    with dropout active, the three ints (T, seed, offset) from which the backward's kernels recompute the mask.  Not differentiable
     twice."""
 
     @staticmethod
     def forward(ctx, layer, base, input, down, up, bias=None):
-        dt = _check_call(layer, input)
-        ctx.drop = drop = _draw_dropout(layer, input.device)
-        with torch.no_grad():
-            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), drop)
-        ctx.layer, ctx.input_shape = layer, input.shape
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        ctx.save_for_backward(x2d, t, down, up)
-        return y
+        return _linear_forward(ctx, layer, base, input, down, up, bias)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        layer = ctx.layer
-        dq = layer.sdnq_dequantizer
-        x2d, t, down, up = ctx.saved_tensors
-        if grad_output.dtype != dq.result_dtype:
-            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
-                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
-        if not grad_output.is_cuda:
-            raise _lib.SdnqHipError("gradients through a quantized Linear with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
-        g2d = training._rows(grad_output)
-        drop = ctx.drop
-        dt, scale = g2d.dtype, _scale(layer, drop)
         _, _, need_x, need_down, need_up, need_bias = ctx.needs_input_grad
-        grad_input = grad_down = grad_up = grad_bias = None
-        if g2d.shape[0] == 0:
-            if need_x:
-                grad_input = grad_output.new_zeros(ctx.input_shape)
-            grad_down = torch.zeros_like(down) if need_down else None
-            grad_up = torch.zeros_like(up) if need_up else None
-        else:
-            g_t = None
-            if need_x or need_down:
-                g_t = ops.lowrank_down(g2d, up.to(dt).t().contiguous())
-            if need_x:
-                gi2d = training._linear_base_grad(layer, g2d)
-                if drop is None:
-                    ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
-                else:
-                    ops.lowrank_add_dropout(g_t, down.to(dt).t().contiguous(), gi2d, scale, drop[2], drop[0], drop[1])
-                grad_input = gi2d.view(ctx.input_shape)
-            if need_up:
-                grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
-            if need_down:
-                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype, drop)
-        if need_bias:
-            grad_bias = g2d.sum(0).to(ctx.bias_dtype)
+        grad_input, grad_down, grad_up, _, grad_bias = _linear_backward(ctx, grad_output, need_x, need_down, need_up, False, need_bias)
         return None, None, grad_input, grad_down, grad_up, grad_bias
 
 
@@ -296,86 +326,18 @@ class QuantizedLinearDoRA(torch.autograd.Function):
     backward recovers c . u = y - b from the saved output (the op that consumes y usually saves the same tensor), so
         g      = round(dY * c),  q[n] = sum_i dY[i][n] (y[i][n] - b[n])        ops.dora_bwd, one pass
         grad_c = q / c where c != 0, else 0                                    (a magnitude entry that is exactly zero gets gradient 0)
-        g_t, grad_input, grad_up, grad_down: QuantizedLinearLoRA's chain on g (dropout variants included)
+        g_t, grad_input, grad_up, grad_down: the chain QuantizedLinearLoRA runs, on g (_linear_backward; dropout variants included)
         grad_bias = dY.sum(0)                                                  the unscaled dY
     Not differentiable twice."""
 
     @staticmethod
     def forward(ctx, layer, base, input, down, up, c, bias=None):
-        dt = _check_call(layer, input)
-        ctx.drop = drop = _draw_dropout(layer, input.device)
-        with torch.no_grad():
-            c32 = c.detach().contiguous()
-            y, x2d, t = _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), drop, (c32, _dora_bias(bias, dt)))
-        ctx.layer, ctx.input_shape = layer, input.shape
-        ctx.bias_dtype = None if bias is None else bias.dtype
-        ctx.has_bias = bias is not None
-        ctx.save_for_backward(x2d, t, down, up, c32, y, *(() if bias is None else (bias,)))
-        return y
+        return _linear_forward(ctx, layer, base, input, down, up, bias, c)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
-        layer = ctx.layer
-        dq = layer.sdnq_dequantizer
-        x2d, t, down, up, c, y = ctx.saved_tensors[:6]
-        bias = ctx.saved_tensors[6] if ctx.has_bias else None
-        if grad_output.dtype != dq.result_dtype:
-            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
-                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
-        if not grad_output.is_cuda:
-            raise _lib.SdnqHipError("gradients through a quantized Linear with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
-        dy2d = training._rows(grad_output)
-        drop = ctx.drop
-        dt, scale = dy2d.dtype, _scale(layer, drop)
-        _, _, need_x, need_down, need_up, need_c, need_bias = ctx.needs_input_grad
-        grad_input = grad_down = grad_up = grad_c = grad_bias = None
-        m, n = dy2d.shape
-        if m == 0:
-            if need_x:
-                grad_input = grad_output.new_zeros(ctx.input_shape)
-            grad_down = torch.zeros_like(down) if need_down else None
-            grad_up = torch.zeros_like(up) if need_up else None
-            grad_c = torch.zeros_like(c) if need_c else None
-        else:
-            ws = _workspace(dy2d.device, ops.dora_bwd_workspace_bytes(m, n)) if need_c else None
-            g2d, q = ops.dora_bwd(dy2d, training._rows(y) if need_c else None, _dora_bias(bias, dt), c, want_q=need_c, workspace=ws)
-            if need_c:
-                grad_c = torch.where(c != 0, q / c, torch.zeros_like(q))
-            g_t = None
-            if need_x or need_down:
-                g_t = ops.lowrank_down(g2d, up.to(dt).t().contiguous())
-            if need_x:
-                gi2d = training._linear_base_grad(layer, g2d)
-                if drop is None:
-                    ops.lowrank_add(g_t, down.to(dt).t().contiguous(), gi2d, scale)
-                else:
-                    ops.lowrank_add_dropout(g_t, down.to(dt).t().contiguous(), gi2d, scale, drop[2], drop[0], drop[1])
-                grad_input = gi2d.view(ctx.input_shape)
-            if need_up:
-                grad_up = _factor_grad(g2d, t, scale, False, up.dtype)
-            if need_down:
-                grad_down = _factor_grad(x2d, g_t, scale, True, down.dtype, drop)
-        if need_bias:
-            grad_bias = dy2d.sum(0).to(ctx.bias_dtype)
-        return None, None, grad_input, grad_down, grad_up, grad_c, grad_bias
-
-
-def _with_dora(base, previous):
-    grad_on = torch.is_grad_enabled
-
-    def forward(self, input):
-        down, up, mag = _attr(self, "lora_down"), _attr(self, "lora_up"), _attr(self, "lora_magnitude")
-        dt = _check_call(self, input)
-        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad or mag.requires_grad):
-            return QuantizedLinearDoRA.apply(self, base, input, down, up, _dora_c(self, down, up, dt), _attr(self, "bias"))
-        with torch.no_grad():
-            c = _dora_c(self, down, up, dt).contiguous()
-            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(self, input.device),
-                        (c, _dora_bias(_attr(self, "bias"), dt)))[0]
-    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_dora"
-    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
-    return forward
+        return (None, None, *_linear_backward(ctx, grad_output, *ctx.needs_input_grad[2:]))
 
 
 # ---- the same on frozen quantized Conv1d / Conv2d layers (add_lora(..., convs=True)) ----------------------------------------------------
@@ -485,30 +447,24 @@ class QuantizedConvLoRA(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         layer = ctx.layer
-        dq = layer.sdnq_dequantizer
         x4, t, down, up = ctx.saved_tensors
-        if grad_output.dtype != dq.result_dtype:
-            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized conv whose compute dtype is "
-                                      f"{dq.result_dtype}: the backward products run in the layer's dtype")
-        if not grad_output.is_cuda:
-            raise _lib.SdnqHipError("gradients through a quantized conv with an adapter need grad_output on a gfx950 device (got a CPU tensor)")
+        training._check_grad_output(layer, grad_output, "conv")
         kernel, stride, padding, dilation, nd = ctx.geometry
         dt, scale = grad_output.dtype, layer.lora_scale
         _, _, need_x, need_down, need_up, need_bias = ctx.needs_input_grad
-        grad_input = grad_down = grad_up = grad_bias = None
+        grad_bias = None
         if grad_output.numel() == 0 or 0 in ctx.input_shape:
-            if need_x:
-                grad_input = grad_output.new_zeros(ctx.input_shape)
-            grad_down = torch.zeros_like(down) if need_down else None
-            grad_up = torch.zeros_like(up) if need_up else None
+            grad_input, grad_down, grad_up = _zero_grads(grad_output, ctx.input_shape, need_x, down if need_down else None,
+                                                         up if need_up else None)
         else:
+            grad_input = grad_down = grad_up = None
             dy4 = (grad_output.unsqueeze(2) if nd == 1 else grad_output).contiguous()
             b, n, ho, wo = dy4.shape
             rank = down.shape[0]
             dy2d = dy4.permute(0, 2, 3, 1).contiguous().view(b * ho * wo, n)
             g_t = None
             if need_x or need_down:
-                g_t = ops.lowrank_down(dy2d, up.to(dt).reshape(n, rank).t().contiguous())
+                g_t = _project_grad(dy2d, up.reshape(n, rank))
             if need_x:
                 shape4 = tuple(x4.shape)
                 route, gi = training._conv_base_grad(layer, dy4, shape4, kernel, stride, padding, dilation, dy2d)
@@ -523,35 +479,62 @@ class QuantizedConvLoRA(torch.autograd.Function):
         return None, None, grad_input, grad_down, grad_up, grad_bias
 
 
-def _with_conv_lora(base, previous):
-    grad_on = torch.is_grad_enabled
+# ---- the forwards add_lora installs ------------------------------------------------------------------------------------------------------
+def _wrapper(suffix: str, with_graph, without_graph, names=("lora_down", "lora_up")):
+    """wrap(base, previous) -> the forward_func of a layer with an adapter.  Per call: `with_graph(layer, base, input, *parameters)` -- an
+    autograd Function -- when gradients are on and the input or one of the layer's parameters `names` requires one, else
+    `without_graph(...)` under torch.no_grad(): the same kernels without a Function.  The forward is stamped with the name of `base` plus
+    `suffix` and with what remove_lora and add_lora read: _sdnq_lora_base, the inference forward it calls, and _sdnq_lora_previous, the
+    forward_func it replaced."""
+    def wrap(base, previous):
+        grad_on = torch.is_grad_enabled
 
-    def forward(self, input):
-        down, up = _attr(self, "lora_down"), _attr(self, "lora_up")
-        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad):
-            return QuantizedConvLoRA.apply(self, base, input, down, up, _attr(self, "bias"))
-        geometry = training._conv_geometry(self)
-        dt = _conv_check_call(self, input, geometry[4])
-        with torch.no_grad():
-            return _conv_run(self, base, input, down.detach().to(dt), up.detach().to(dt), geometry)[0]
-    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_lora"
-    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
-    return forward
+        def forward(self, input):
+            params = [_attr(self, name) for name in names]
+            if grad_on() and (input.requires_grad or any(p.requires_grad for p in params)):
+                return with_graph(self, base, input, *params)
+            with torch.no_grad():
+                return without_graph(self, base, input, *params)
+        forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + suffix
+        forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
+        return forward
+    return wrap
 
 
-def _with_lora(base, previous):
-    grad_on = torch.is_grad_enabled
+def _lora_graph(layer, base, input, down, up):
+    return QuantizedLinearLoRA.apply(layer, base, input, down, up, _attr(layer, "bias"))
 
-    def forward(self, input):
-        down, up = _attr(self, "lora_down"), _attr(self, "lora_up")
-        if grad_on() and (input.requires_grad or down.requires_grad or up.requires_grad):
-            return QuantizedLinearLoRA.apply(self, base, input, down, up, _attr(self, "bias"))
-        dt = _check_call(self, input)
-        with torch.no_grad():
-            return _run(self, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(self, input.device))[0]
-    forward.__name__ = forward.__qualname__ = getattr(base, "__name__", "forward") + "_with_lora"
-    forward._sdnq_lora_base, forward._sdnq_lora_previous = base, previous
-    return forward
+
+def _lora_plain(layer, base, input, down, up):
+    dt = _check_call(layer, input)
+    return _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(layer, input.device))[0]
+
+
+def _dora_graph(layer, base, input, down, up, magnitude):
+    dt = _check_call(layer, input)
+    return QuantizedLinearDoRA.apply(layer, base, input, down, up, _dora_c(layer, down, up, dt), _attr(layer, "bias"))
+
+
+def _dora_plain(layer, base, input, down, up, magnitude):
+    dt = _check_call(layer, input)
+    c = _dora_c(layer, down, up, dt).contiguous()
+    return _run(layer, base, input, down.detach().to(dt), up.detach().to(dt), _draw_dropout(layer, input.device),
+                (c, _dora_bias(_attr(layer, "bias"), dt)))[0]
+
+
+def _conv_graph(layer, base, input, down, up):
+    return QuantizedConvLoRA.apply(layer, base, input, down, up, _attr(layer, "bias"))
+
+
+def _conv_plain(layer, base, input, down, up):
+    geometry = training._conv_geometry(layer)
+    dt = _conv_check_call(layer, input, geometry[4])
+    return _conv_run(layer, base, input, down.detach().to(dt), up.detach().to(dt), geometry)[0]
+
+
+_with_lora = _wrapper("_with_lora", _lora_graph, _lora_plain)
+_with_dora = _wrapper("_with_dora", _dora_graph, _dora_plain, ("lora_down", "lora_up", "lora_magnitude"))
+_with_conv_lora = _wrapper("_with_lora", _conv_graph, _conv_plain)
 
 
 def _refresh_compile_plan(module) -> None:
@@ -709,10 +692,7 @@ def add_lora(model: torch.nn.Module, rank: int = 16, alpha: float | None = None,
             module.lora_dora = True
             params.append(module.lora_magnitude)
         added += 1
-    if skipped:
-        import warnings
-        warnings.warn(f"sdnq_amd.add_lora: {len(skipped)} SDNQ layer(s) got no adapter: "
-                      + "; ".join(f"{n} ({w})" for n, w in skipped[:8]) + (" ..." if len(skipped) > 8 else ""), stacklevel=2)
+    _warn_skipped("add_lora", "SDNQ layer(s) got no adapter", skipped)
     return LoRAResult(added, skipped, params)
 
 
@@ -905,11 +885,26 @@ def _merge_layer(module, down: torch.Tensor, up: torch.Tensor | None, scale: flo
     return route
 
 
-def _warn_skipped(who: str, skipped) -> None:
+def _warn_skipped(who: str, what: str, skipped) -> None:
+    """ONE warning for the layers a public function `who` left alone, attributed to its caller (so `who` calls this itself): their
+    number, `what` became of them, and the first eight with their reasons."""
     if skipped:
         import warnings
-        warnings.warn(f"sdnq_amd.{who}: {len(skipped)} layer(s) were not merged: "
+        warnings.warn(f"sdnq_amd.{who}: {len(skipped)} {what}: "
                       + "; ".join(f"{n} ({w})" for n, w in skipped[:8]) + (" ..." if len(skipped) > 8 else ""), stacklevel=3)
+
+
+def _merge_operands(module, down: torch.Tensor, up: torch.Tensor, magnitude, scale=None):
+    """(down [R', K], up [N, R'], c [N] float32 | None) as _merge_layer takes them: the factors in the layer dtype on the layer's device,
+    contiguous, the rank padded to a multiple of 8 (`pad_rank`), and with a DoRA `magnitude` c = magnitude / || W + scale * up @ down ||
+    (scale None: the layer's lora_scale), the norm from the very factors that are merged."""
+    dt, dev = module.sdnq_dequantizer.result_dtype, module.weight.device
+    with torch.no_grad():
+        down, up = pad_rank(down.detach().to(device=dev, dtype=dt), up.detach().to(device=dev, dtype=dt))
+        c = None
+        if magnitude is not None:
+            c = (magnitude.detach().to(device=dev, dtype=torch.float32) / torch.sqrt(_layer_normsq(module, down, up, scale))).contiguous()
+    return down, up, c
 
 
 def merge_lora(model: torch.nn.Module, targets=None) -> MergeResult:
@@ -932,17 +927,12 @@ def merge_lora(model: torch.nn.Module, targets=None) -> MergeResult:
         if why is not None:
             skipped.append((name or type(module).__name__, why))
             continue
-        dt = module.sdnq_dequantizer.result_dtype
-        with torch.no_grad():
-            down = _attr(module, "lora_down").detach().to(dt).contiguous()
-            up = _attr(module, "lora_up").detach().to(dt).contiguous()
-            c = None
-            if dora:
-                c = (_attr(module, "lora_magnitude").detach().float() / torch.sqrt(_layer_normsq(module, down, up))).contiguous()
+        down, up, c = _merge_operands(module, _attr(module, "lora_down"), _attr(module, "lora_up"),
+                                      _attr(module, "lora_magnitude") if dora else None)
         _merge_layer(module, down, up, float(module.lora_scale), c)
         _take_off(module)
         merged.append(name or type(module).__name__)
-    _warn_skipped("merge_lora", skipped)
+    _warn_skipped("merge_lora", "layer(s) were not merged", skipped)
     return MergeResult(merged, skipped)
 
 
@@ -998,14 +988,8 @@ def merge_lora_state_dict(model: torch.nn.Module, sd: dict, scale: float = 1.0) 
         work.append((name, module, a, b, got.get("M")))
     merged = []
     for name, module, a, b, mag in work:
-        dt = module.sdnq_dequantizer.result_dtype
-        dev = module.weight.device
-        with torch.no_grad():
-            down, up = pad_rank(a.detach().to(device=dev, dtype=dt), b.detach().to(device=dev, dtype=dt))
-            c = None
-            if mag is not None:
-                c = (mag.detach().to(device=dev, dtype=torch.float32) / torch.sqrt(_layer_normsq(module, down, up, scale))).contiguous()
+        down, up, c = _merge_operands(module, a, b, mag, scale)
         _merge_layer(module, down, up, scale, c)
         merged.append(name)
-    _warn_skipped("merge_lora_state_dict", skipped)
+    _warn_skipped("merge_lora_state_dict", "layer(s) were not merged", skipped)
     return MergeResult(merged, skipped)

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import typing
 from dataclasses import dataclass
 
 import torch
@@ -1118,8 +1119,9 @@ def _lowrank_check(what: str, rank: int, **tensors) -> None:
                                     f"{t.storage_offset()}, row stride {t.stride(0)} elements)")
 
 
-def _lowrank_add(what: str, t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float, drop=None) -> torch.Tensor:
-    """lowrank_add (drop None) and lowrank_add_dropout (drop = (threshold, seed, offset)): the same checks under the caller's name."""
+def _lowrank_add(what: str, t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: float, drop=None, dora=None) -> torch.Tensor:
+    """lowrank_add (drop and dora None), lowrank_add_dropout (drop = (threshold, seed, offset)) and lowrank_add_dora (dora = (c, bias | None)):
+    the same checks under the caller's name.  drop and dora are exclusive, as in the library's launcher."""
     if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
         raise _lib.SdnqHipError(f"{what}: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
     (m, r), (n, r2) = t.shape, up.shape
@@ -1130,13 +1132,19 @@ def _lowrank_add(what: str, t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, 
         raise _lib.SdnqHipError(f"{what}: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
     if not t.is_contiguous() or not up.is_contiguous():
         raise _lib.SdnqHipError(f"{what}: t and up must be contiguous")
+    if drop is not None and dora is not None:
+        raise _lib.SdnqHipError(f"{what}: the dropout mask and DoRA's epilogue are exclusive (no such kernel)")
     if drop is not None:
         drop = _dropout_args(what, *drop)
-    _require_cuda(t, up, y)
+    if dora is not None:
+        _dora_vectors(what, n, y.dtype, *dora)
+    _require_cuda(t, up, y, *(dora or ()))
     if m == 0:
         return y
     head = (t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y))
-    if drop is None:
+    if dora is not None:
+        check(_lib.load().sdnq_hip_lowrank_add_dora(*head, dora[0].data_ptr(), _ptr(dora[1]), _stream(y)), what)
+    elif drop is None:
         check(_lib.load().sdnq_hip_lowrank_add(*head, _stream(y)), what)
     else:
         check(_lib.load().sdnq_hip_lowrank_add_dropout(*head, *drop, _stream(y)), what)
@@ -1219,6 +1227,13 @@ def lowrank_grad(a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out_t: bo
 
 
 # ---- LoRA dropout: the three adapter kernels with the mask recomputed inside (include/sdnq_hip.h has the counter convention) -----------------
+class _Dropout(typing.NamedTuple):
+    """The dropout triple of one adapter call, in the order the library (and every ``lowrank_*_dropout`` here) takes it: splat it."""
+    threshold: int
+    seed: int
+    offset: int
+
+
 def _dropout_args(what: str, threshold: int, seed: int, offset: int) -> tuple:
     """(threshold, seed, offset) as the library takes them: an element is dropped iff its 16 random bits are < threshold."""
     threshold, seed, offset = int(threshold), int(seed), int(offset)
@@ -1417,24 +1432,7 @@ def lowrank_add_dora(t: torch.Tensor, up: torch.Tensor, y: torch.Tensor, scale: 
     """sdnq_hip_lowrank_add_dora: ``lowrank_add`` with DoRA's epilogue IN PLACE on y [M, N] = the base output z (bias included):
     y = round(fma(c * scale, t @ up^T, fma(c - 1, z - bias, z))), c [N] float32, bias [N] of y's dtype or None.  With c == 1 the bits of
     ``lowrank_add``.  Returns y."""
-    what = "lowrank_add_dora"
-    if t.ndim != 2 or up.ndim != 2 or y.ndim != 2:
-        raise _lib.SdnqHipError(f"{what}: t, up and y must be 2-D (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
-    (m, r), (n, r2) = t.shape, up.shape
-    _lowrank_check(what, r, t=t, up=up, y=y)
-    if r2 != r or tuple(y.shape) != (m, n):
-        raise _lib.SdnqHipError(f"{what}: t [M, R], up [N, R], y [M, N] (got {tuple(t.shape)}, {tuple(up.shape)}, {tuple(y.shape)})")
-    if n % 8:
-        raise _lib.SdnqHipError(f"{what}: n % 8 == 0 (got n = {n}): y moves in 16-byte pieces")
-    if not t.is_contiguous() or not up.is_contiguous():
-        raise _lib.SdnqHipError(f"{what}: t and up must be contiguous")
-    _dora_vectors(what, n, y.dtype, c, bias)
-    _require_cuda(t, up, y, c, bias)
-    if m == 0:
-        return y
-    check(_lib.load().sdnq_hip_lowrank_add_dora(t.data_ptr(), up.data_ptr(), float_code(y.dtype), r, float(scale), y.data_ptr(), m, n, _ld(y),
-                                                c.data_ptr(), _ptr(bias), _stream(y)), what)
-    return y
+    return _lowrank_add("lowrank_add_dora", t, up, y, scale, dora=(c, bias))
 
 
 def dora_bwd_workspace_bytes(m: int, n: int) -> int:

@@ -249,6 +249,17 @@ def _linear_base_grad(layer, g2d: torch.Tensor) -> torch.Tensor:
     return ops.linear_float(g2d, _weight_t_operand(layer, linear._state(layer).qw, g2d.dtype, g2d.device), None)
 
 
+def _check_grad_output(layer, grad_output: torch.Tensor, kind: str) -> None:
+    """What every backward through a frozen quantized layer -- the input-gradient Functions here, the adapters of sdnq_amd.lora -- asks of
+    grad_output: the layer's compute dtype (the backward products run in it), on the device.  kind: "Linear" or "conv", for the message."""
+    dt = layer.sdnq_dequantizer.result_dtype
+    if grad_output.dtype != dt:
+        raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized {kind} whose compute dtype is {dt}: the "
+                                  "backward products run in the layer's dtype")
+    if not grad_output.is_cuda:
+        raise _lib.SdnqHipError(f"gradients through a quantized {kind} need grad_output on a gfx950 device (got a CPU tensor)")
+
+
 class QuantizedLinearInputGrad(torch.autograd.Function):
     """y = layer(input) with a graph: grad_input = dY . W, where W is the weight the layer's forward multiplies by (SVD product added,
     Hadamard rotation undone).  grad_bias = dY.sum(0) when the bias requires grad; the weight, scale, zero point and SVD factors are
@@ -268,12 +279,7 @@ class QuantizedLinearInputGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         layer = ctx.layer
-        dq = layer.sdnq_dequantizer
-        if grad_output.dtype != dq.result_dtype:
-            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized Linear whose compute dtype is "
-                                      f"{dq.result_dtype}: the backward GEMM runs in the layer's dtype")
-        if not grad_output.is_cuda:
-            raise _lib.SdnqHipError("input gradients through a quantized Linear need grad_output on a gfx950 device (got a CPU tensor)")
+        _check_grad_output(layer, grad_output, "Linear")
         g2d = _rows(grad_output)
         grad_input = grad_bias = None
         if ctx.needs_input_grad[1]:
@@ -485,12 +491,7 @@ class QuantizedConvInputGrad(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_output):
         layer = ctx.layer
-        dq = layer.sdnq_dequantizer
-        if grad_output.dtype != dq.result_dtype:
-            raise NotImplementedError(f"grad_output of dtype {grad_output.dtype} through a quantized conv whose compute dtype is "
-                                      f"{dq.result_dtype}: the backward GEMM runs in the layer's dtype")
-        if not grad_output.is_cuda:
-            raise _lib.SdnqHipError("input gradients through a quantized conv need grad_output on a gfx950 device (got a CPU tensor)")
+        _check_grad_output(layer, grad_output, "conv")
         kernel, stride, padding, dilation, nd = _conv_geometry(layer)
         shape = tuple(ctx.input_shape)
         if len(shape) != nd + 2:

@@ -113,6 +113,23 @@ def test_ops_checks_name_what_is_wrong():
     assert ops._ld(one) == 24 and ops._ld(y[:, :16]) == 24
 
 
+def test_the_dropout_triple_has_the_order_of_the_entry_points_and_is_never_indexed():
+    """One order for (threshold, seed, offset) from the draw to the library: the fields of ops._Dropout are the trailing dropout parameters
+    of the three wrappers, in their order, and sdnq_amd/lora.py passes the triple on whole or splats it -- no subscript of a name `drop`."""
+    import ast
+    import inspect
+    fields = ops._Dropout._fields
+    assert fields == ("threshold", "seed", "offset")
+    for fn in (ops.lowrank_add_dropout, ops.lowrank_grad_dropout, ops.lowrank_down_dropout):
+        assert tuple(p for p in inspect.signature(fn).parameters if p in fields) == fields, fn.__name__
+    with open(lora.__file__) as f:
+        tree = ast.parse(f.read())
+    indexed = [node.lineno for node in ast.walk(tree)
+               if isinstance(node, ast.Subscript) and isinstance(node.value, ast.Name) and node.value.id == "drop"]
+    assert indexed == [], indexed
+    assert lora._scale(type("Layer", (), {"lora_scale": 2.0})(), ops._Dropout(16384, 7, 4)) == lora.dropout_scale(2.0, 16384)
+
+
 class Toy(torch.nn.Module):
     def __init__(self, dtype=torch.bfloat16):
         super().__init__()
