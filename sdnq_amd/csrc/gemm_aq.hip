@@ -42,12 +42,12 @@ namespace {
 //   1: 32 x 256, 3 ring slots : waves 1 x 8; a wave quantizes 4 rows in one pass (half the ingest and the arithmetic in front of the K loop,
 //                               half the redundancy across a row block); 32-KB weight stages, 40 + 96 KB of LDS at K = 1280; every wave
 //                               moves and drains its own weight rows, no barrier in the K loop (the slab form: BN / 32 == NW)
-// and two "tall" forms for K <= 640 (five stages held) where the 64 x 128 tiles of a problem outnumber the CUs:
+// and the "tall" form for K <= 640 (five stages held) where the 64 x 128 tiles of a problem outnumber the CUs:
 //   2: 64 x 128, 2 ring slots : the tile of geometry 0 on a thin ring: 40 KB image + 32 KB ring, so TWO workgroups share a CU (the second
 //                               one hides the first one's stage waits, as in the two-launch GEMM's 3 slots x 2 workgroups) and
 //                               2 x CUs tiles are resident at once
-//   3: 128 x 128, 3 ring slots: waves 2 x 4 with TWO 32 x 32 accumulators each (rows 64 wm .. + 64); a wave quantizes 16 rows in four
-//                               passes; 80 KB image + 48 KB ring, one workgroup per CU, half the tiles
+// Every tile is one 32 x 32 accumulator per wave.  A 128 x 128 tile with two per wave (one workgroup per CU, half the tiles) was built
+// for the tall problems and lost: 19 799 against 13 070 ticks per workgroup (profiles/linear_aq_k640_tall.txt).
 constexpr int BK = 128, NW = 8, NT = NW * 64;
 
 // The form geometry 1 runs in on int8 where the caller passes the slab copy of the weight (sdnq_hip_linear_w8a8_fused_slab): the direct
@@ -64,10 +64,6 @@ struct AqParams {
     const uint8_t* pf_ptr[4];  // weight prefetch hosted by this launch (sdnq_hip_prefetch_hint)
     int pf_lines[4];
     unsigned long long* trace;  // lab: per-workgroup phase stamps (8 per workgroup), or null
-#ifdef SDNQ_AQ_LAB
-    int lab;  // lab build (timing only, results invalid): 1 no loop DMAs, 2 no fragment reads, 4 no MFMAs, 8 no barrier, 16 no quantization arithmetic
-              // (the slab form of the 32 x 256 tile has no loop barrier and counts on every DMA: bits 1 and 8 do nothing there)
-#endif
 };
 
 // The members of a GROUPED launch (layers that read one activation: sdnq_hip_linear_w8a8_fused_grouped), by value in the kernel arguments.
@@ -139,7 +135,7 @@ constexpr int64_t AQ_TALL_MAX_K = 640;
 //   geometry 1 (32 x 256, 3 ring slots) where the front of the 64 x 128 tile -- ingest + quantization of 64 rows x K, repeated by every
 //   column tile -- outweighs its K loop: int8, K of more than 5 stages, N a multiple of 256 (no column tile half empty), and one round:
 //   at most one tile per CU.
-//   a tall geometry (2 or 3: int8, K of at most 5 stages) where one round of 64 x 128 tiles, one per CU, does NOT cover the problem but
+//   the tall geometry (2: int8, K of at most 5 stages) where one round of 64 x 128 tiles, one per CU, does NOT cover the problem but
 //   one round of the tall form does: at most `resident` tiles per CU.
 //   Everything else keeps geometry 0 (64 x 128, 4 ring slots).
 // A forced tall geometry on a problem it has no instantiation for (fp8, K > 640) falls back to the shape rule.
@@ -147,19 +143,17 @@ struct AqPlan { int geometry, bm, bn, tiles_m, tiles_n, group_m, resident; int64
 inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
     static const int geo_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GEOMETRY", -1);  // tuning aid
     static const int gm_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);     // tuning aid (1 = n fastest)
-    static const int gm_tall_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M_TALL", 8);  // the same for geometries 2 and 3
-    // the tall form the shape rule picks: 2 (3 lost in the step; the variable is how that was measured)
-    static const int tall = env_int("SDNQ_HIP_FUSED_ROWQUANT_TALL_GEOMETRY", 2) == 3 ? 3 : 2;
+    static const int gm_tall_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M_TALL", 8);  // the same for geometry 2
     struct Geo { int bm, bn, resident; };
-    static constexpr Geo GEOS[4] = {{64, 128, 1}, {32, 256, 1}, {64, 128, 2}, {128, 128, 1}};
+    static constexpr Geo GEOS[3] = {{64, 128, 1}, {32, 256, 1}, {64, 128, 2}};
     const bool tall_ok = mm_dtype == SDNQ_MM_I8 && k <= AQ_TALL_MAX_K;
     auto tiles_of = [&](int g) { return ((m + GEOS[g].bm - 1) / GEOS[g].bm) * ((n + GEOS[g].bn - 1) / GEOS[g].bn); };
     int geo = g_aq_geometry.load(std::memory_order_relaxed);
     if (geo < 0) geo = geo_env;
-    if (geo > 3 || (geo >= 2 && !tall_ok)) geo = -1;
+    if (geo > 2 || (geo == 2 && !tall_ok)) geo = -1;
     if (geo < 0) {
         if (mm_dtype == SDNQ_MM_I8 && k > 640 && (n % 256) == 0 && ((m + 31) / 32) * (n / 256) <= cus) geo = 1;
-        else if (tall_ok && tiles_of(0) > cus && tiles_of(tall) <= (int64_t)GEOS[tall].resident * cus) geo = tall;
+        else if (tall_ok && tiles_of(0) > cus && tiles_of(2) <= (int64_t)GEOS[2].resident * cus) geo = 2;
         else geo = 0;
     }
     AqPlan pl;
@@ -171,7 +165,7 @@ inline AqPlan aq_plan(int mm_dtype, int64_t m, int64_t n, int64_t k, int cus) {
     pl.tiles_n = (int)((n + pl.bn - 1) / pl.bn);
     // the walk groups 8 row blocks in every geometry.  32 x 256 at 1024 x 1280 x 1280: a group is 40 tiles = the 20 of two XCDs, each
     // 8 row blocks x 2.5 weight blocks; in the step 8 blocks ran 7.02 ms, 16 (the same ROWS as 8 of 64) 7.08, 2 / 4 / 6 7.04
-    const int gm_e = geo >= 2 ? gm_tall_env : gm_env;
+    const int gm_e = geo == 2 ? gm_tall_env : gm_env;
     const int gm = gm_e < 1 ? 1 : gm_e;
     pl.group_m = gm > pl.tiles_m ? pl.tiles_m : gm;
     pl.prefetch_room = (int64_t)pl.resident * cus - (int64_t)pl.tiles_m * pl.tiles_n;  // workgroup slots (LDS) the tiles leave free
@@ -191,9 +185,6 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
     const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, group_m = pl.group_m;
     const int64_t tiles = (int64_t)tiles_m * tiles_n;
     p.trace = g_aq_trace.load(std::memory_order_relaxed);
-#ifdef SDNQ_AQ_LAB
-    p.lab = (int)env_int("SDNQ_HIP_AQ_LAB", 0);
-#endif
     const int pf_wgs = sdnq_internal_take_prefetch(pl.prefetch_room, NT, p.pf_ptr, p.pf_lines);
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles + pf_wgs)), dim3(NT), LDS_BYTES, s, (const uint16_t*)x, (const uint8_t*)w, (int)ldx, (int)k, (int)m,
                        (int)n, (int)k, tiles_m, tiles_n, group_m, p);
@@ -202,24 +193,13 @@ int launch_aq(const void* x, const void* w, int64_t ldx, int64_t m, int64_t n, i
 }
 
 // ---- grouped launch: layers that read ONE activation (the linked q / k / v of a self-attention block) in one launch of the direct form ----
-// Two tiles were built for it (profiles/linear_aq_qkv_grouped.txt):
-//   arm 0: 32 x 256, TWO workgroups per CU -- the direct form keeps no ring in LDS (40 KB image + vectors at K = 1280) and 117 registers
-//          per lane, so a second tile is resident beside the first and its ingest, quantization and stores run under the first one's K loop;
-//          1024 x (3 x 1280) is 480 tiles = one round on 240 CUs.  No flags or waits between workgroups: the hardware interleaves them.
-//   arm 1: 64 x 256, one per CU -- half the tiles and half the weight traffic (a fragment feeds two MFMAs), twice the rows to quantize
-//          per wave and nothing resident beside it.
-// Arm 0 won in the step (-0.07 ... -0.11 ms against -0.03) and alone (12.7 against 13.0 us; the two launches: 15.2).  The library ships
-// AQ_GROUPED_ARM; a build with -DSDNQ_AQ_GROUPED_LAB holds both and SDNQ_HIP_FUSED_ROWQUANT_GROUPED_ARM picks.  Same bits as the row
-// quantizer + grouped GEMM and as every member's own launch: tests/test_gemm_aq_grouped.py.
-constexpr int AQ_GROUPED_ARM = 0;
-inline int aq_grouped_arm() {
-#ifdef SDNQ_AQ_GROUPED_LAB
-    static const int arm = env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUPED_ARM", AQ_GROUPED_ARM) == 1 ? 1 : 0;
-    return arm;
-#else
-    return AQ_GROUPED_ARM;
-#endif
-}
+// Its tile is 32 x 256 with TWO workgroups per CU -- the direct form keeps no ring in LDS (40 KB image + vectors at K = 1280) and 117
+// registers per lane, so a second tile is resident beside the first and its ingest, quantization and stores run under the first one's
+// K loop; 1024 x (3 x 1280) is 480 tiles = one round on 240 CUs.  No flags or waits between workgroups: the hardware interleaves them.
+// A 64 x 256 tile, one per CU (half the tiles and the weight traffic, twice the rows to quantize per wave, nothing resident beside it),
+// was built and lost: -0.03 against -0.07 ... -0.11 ms in the step (profiles/linear_aq_qkv_grouped.txt).  Same bits
+// as the row quantizer + grouped GEMM and as every member's own launch: tests/test_gemm_aq_grouped.py.
+constexpr int AQ_GROUPED_BM = 32, AQ_GROUPED_BN = 256, AQ_GROUPED_RESIDENT = 2, AQ_GROUPED_NJ = 10;
 
 // The rule of the grouped launch in one place (tests/test_gemm_aq_plan_grouped.py holds its table): int8 members of one width that is a
 // multiple of the 256-column block, K of six to ten stages, and every tile of every member resident at once.  `ok` = 0: the group keeps
@@ -227,15 +207,10 @@ inline int aq_grouped_arm() {
 struct AqGroupPlan { int ok, bm, bn, tiles_m, tiles_n, group_m, resident; int64_t prefetch_room; };
 inline AqGroupPlan aq_plan_grouped(int mm_dtype, int64_t m, int64_t n_member, int64_t n_members, int64_t k, int cus) {
     static const int gm_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUP_M", 8);             // the walk of aq_plan
-    // hosted prefetch workgroups share a CU with a tile here (two workgroups per CU): with the 2 * CUs - tiles slots handed out the step
-    // ran 0.007 and 0.09 ms SLOWER than with none in two sessions (profiles/linear_aq_qkv_grouped.txt), so the launch gets no prefetch
-    // room; 1 hands the slots out (tuning aid: how that was measured)
-    static const int pf_env = (int)env_int("SDNQ_HIP_FUSED_ROWQUANT_GROUPED_PREFETCH", 0);
-    const int arm = aq_grouped_arm();
     AqGroupPlan pl{};
-    pl.bm = arm == 1 ? 64 : 32;
-    pl.bn = 256;
-    pl.resident = arm == 1 ? 1 : 2;
+    pl.bm = AQ_GROUPED_BM;
+    pl.bn = AQ_GROUPED_BN;
+    pl.resident = AQ_GROUPED_RESIDENT;
     if (mm_dtype != SDNQ_MM_I8 || m <= 0 || n_member <= 0 || (n_member % 256) != 0 || n_members < 1 || n_members > AQ_GROUP_MAX || (k % 128) != 0 ||
         k <= AQ_TALL_MAX_K || k > 1280 || cus <= 0)
         return pl;
@@ -246,28 +221,28 @@ inline AqGroupPlan aq_plan_grouped(int mm_dtype, int64_t m, int64_t n_member, in
     pl.tiles_n = (int)tiles_n;
     const int gm = gm_env < 1 ? 1 : gm_env;
     pl.group_m = gm > pl.tiles_m ? pl.tiles_m : gm;
-    pl.prefetch_room = pf_env ? (int64_t)pl.resident * cus - tiles_m * tiles_n : 0;  // workgroup slots the tiles leave free
+    // hosted prefetch workgroups would share a CU with a tile here (two workgroups per CU): with the 2 * CUs - tiles slots handed out the
+    // step ran 0.007 and 0.09 ms SLOWER than with none in two sessions (profiles/linear_aq_qkv_grouped.txt): no prefetch room
+    pl.prefetch_room = 0;
     return pl;
 }
 
-template <int X_T, bool HAS_BIAS, int NJ, int BM, int BN, int RESIDENT>
+template <int X_T, bool HAS_BIAS>
 int launch_aq_grouped(const void* x, int64_t ldx, int64_t m, int64_t n_member, int64_t k, const AqGroupPlan& pl, AqParams p, const AqGroup& g, hipStream_t s) {
+    constexpr int BM = AQ_GROUPED_BM, BN = AQ_GROUPED_BN, RESIDENT = AQ_GROUPED_RESIDENT, NJ = AQ_GROUPED_NJ;
     // what the tile uses -- the code image and the vectors; no ring --, raised to the smallest size of which RESIDENT + 1 do not fit a CU:
-    // the count of co-resident workgroups (tiles and hosted prefetch workgroups alike) is then RESIDENT whatever the register allocation
-    // (at 117 registers per lane two 8-wave workgroups is also all the register file holds)
+    // the count of co-resident workgroups is then RESIDENT whatever the register allocation (at 117 registers per lane two 8-wave
+    // workgroups is also all the register file holds)
     constexpr int USED = NJ * BM * BK + (2 * BN + BM) * 4, FLOOR = (160 * 1024 / (RESIDENT + 1) / 1024 + 1) * 1024;
     constexpr int LDS_BYTES = USED > FLOOR ? USED : FLOOR;
-    static_assert(RESIDENT * LDS_BYTES <= 160 * 1024 && (RESIDENT + 1) * LDS_BYTES > 160 * 1024, "LDS budget: exactly RESIDENT workgroups per CU (aq_plan_grouped's prefetch room)");
+    static_assert(RESIDENT * LDS_BYTES <= 160 * 1024 && (RESIDENT + 1) * LDS_BYTES > 160 * 1024, "LDS budget: exactly RESIDENT workgroups per CU");
     auto kern = linear_aq_grouped_kernel<X_T, SDNQ_MM_I8, HAS_BIAS, NJ, -AQ_DIRECT_STAGES, BM, BN>;
     static std::atomic<uint64_t> attr_devices{0};
     if (LDS_BYTES > 64 * 1024 && !allow_dynamic_lds((const void*)kern, LDS_BYTES, attr_devices)) return SDNQ_ERR_LAUNCH;
-    if (!pl.ok || pl.bm != BM || pl.bn != BN || pl.resident != RESIDENT) return SDNQ_ERR_LAUNCH;
+    if (!pl.ok) return SDNQ_ERR_LAUNCH;
     const int64_t tiles = (int64_t)pl.tiles_m * pl.tiles_n;
     p.trace = g_aq_trace.load(std::memory_order_relaxed);
-#ifdef SDNQ_AQ_LAB
-    p.lab = (int)env_int("SDNQ_HIP_AQ_LAB", 0);
-#endif
-    const int pf_wgs = sdnq_internal_take_prefetch(pl.prefetch_room, NT, p.pf_ptr, p.pf_lines);
+    const int pf_wgs = sdnq_internal_take_prefetch(pl.prefetch_room, NT, p.pf_ptr, p.pf_lines);  // (no room: consumes a pending hint)
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles + pf_wgs)), dim3(NT), LDS_BYTES, s, (const uint16_t*)x, (int)ldx, (int)m, (int)n_member, (int)k, pl.tiles_m,
                        pl.tiles_n, pl.group_m, p, g);
     SDNQ_CHECK_LAUNCH();
@@ -360,11 +335,10 @@ extern "C" int sdnq_hip_linear_w8a8_fused_slab(int mm_dtype, const void* x, int 
 #define AQ_NJ(XT, MMV, HB) (k <= 640 ? AQ_G(XT, MMV, HB, 5) : AQ_G(XT, MMV, HB, 10))
 #define AQ_B(XT, MMV) (bias ? AQ_NJ(XT, MMV, true) : AQ_NJ(XT, MMV, false))
 #define AQ_X(MMV) (x_dtype == SDNQ_BF16 ? AQ_B(SDNQ_BF16, MMV) : AQ_B(SDNQ_F16, MMV))
-    // the tall geometries: int8, five stages (aq_plan hands them out for nothing else)
+    // the tall geometry: int8, five stages (aq_plan hands it out for nothing else)
 #define AQ_TB(XT, ...) (bias ? AQ_L(XT, SDNQ_MM_I8, true, 5, __VA_ARGS__) : AQ_L(XT, SDNQ_MM_I8, false, 5, __VA_ARGS__))
 #define AQ_T(...) (x_dtype == SDNQ_BF16 ? AQ_TB(SDNQ_BF16, __VA_ARGS__) : AQ_TB(SDNQ_F16, __VA_ARGS__))
     if (pl.geometry == 2) return AQ_T(2, 64, 128, 2);
-    if (pl.geometry == 3) return AQ_T(3, 128, 128, 1);
     return mm_dtype == SDNQ_MM_I8 ? AQ_X(SDNQ_MM_I8) : AQ_X(SDNQ_MM_FP8);
 #undef AQ_T
 #undef AQ_TB
@@ -418,14 +392,9 @@ extern "C" int sdnq_hip_linear_w8a8_fused_grouped(int mm_dtype, const void* x, i
     AqParams p{};
     p.out = out; p.ldc = n_member; p.bias_dtype = bias_dtype;
     hipStream_t s = (hipStream_t)stream;
-#define AQ_GL(XT, HB, BMV, RES) launch_aq_grouped<XT, HB, 10, BMV, 256, RES>(x, ldx, m, n_member, k, pl, p, g, s)
-#define AQ_GB(XT, BMV, RES) (biases ? AQ_GL(XT, true, BMV, RES) : AQ_GL(XT, false, BMV, RES))
-#define AQ_GX(BMV, RES) (x_dtype == SDNQ_BF16 ? AQ_GB(SDNQ_BF16, BMV, RES) : AQ_GB(SDNQ_F16, BMV, RES))
-#ifdef SDNQ_AQ_GROUPED_LAB
-    if (pl.bm == 64) return AQ_GX(64, 1);
-#endif
-    return AQ_GX(32, 2);
-#undef AQ_GX
+#define AQ_GL(XT, HB) launch_aq_grouped<XT, HB>(x, ldx, m, n_member, k, pl, p, g, s)
+#define AQ_GB(XT) (biases ? AQ_GL(XT, true) : AQ_GL(XT, false))
+    return x_dtype == SDNQ_BF16 ? AQ_GB(SDNQ_BF16) : AQ_GB(SDNQ_F16);
 #undef AQ_GB
 #undef AQ_GL
 }
@@ -435,8 +404,8 @@ extern "C" int sdnq_hip_linear_w8a8_fused_grouped(int mm_dtype, const void* x, i
 void sdnq_internal_aq_trace(unsigned long long* device_buf) { g_aq_trace.store(device_buf, std::memory_order_relaxed); }
 
 // tests / labs: force the tile geometry of the one-launch Linear (-1 by shape, 0 = 64 x 128, 1 = 32 x 256, 2 = 64 x 128 on two ring
-// slots, 3 = 128 x 128; any other value = 1, as before the tall forms); internal like the trace hook
-void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry <= 3 ? geometry : 1), std::memory_order_relaxed); }
+// slots; any other value = 1, as before the tall form); internal like the trace hook
+void sdnq_internal_aq_geometry(int geometry) { g_aq_geometry.store(geometry < 0 ? -1 : (geometry <= 2 ? geometry : 1), std::memory_order_relaxed); }
 
 // tests / labs: the form geometry 1 runs in on int8 where the caller passes the slab copy (-1 the default, 0 the LDS ring, any other value
 // the direct form); internal like the hooks above

@@ -22,12 +22,11 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
 #endif
     const AqParams& p = p_;
     typedef AqMma<MM> MT;
-    constexpr int NACC = (BM / 32) * (BN / 32) / NW;  // 32x32 accumulators of a wave: consecutive row blocks of one column block
-    static_assert(BM % 32 == 0 && BN % 32 == 0 && NACC * NW == (BM / 32) * (BN / 32) && NACC >= 1 && NACC <= 2, "one or two 32x32 accumulators per wave");
+    static_assert(BM % 32 == 0 && BN % 32 == 0 && (BM / 32) * (BN / 32) == NW, "one 32x32 accumulator per wave");
     constexpr int A_STAGE = BM * BK, B_STAGE = BN * BK;
     constexpr int PS = BM / (4 * NW);   // quantization passes of a wave: 4 rows (one per quarter wave) each
     constexpr int PPW = BN / (8 * NW);  // 1-KB ring pieces (8 weight rows) of a stage that one wave moves
-    static_assert(PS >= 1 && PS <= 4 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
+    static_assert(PS >= 1 && PS <= 2 && PS * 4 * NW == BM && PPW >= 1 && PPW * 8 * NW == BN && BN <= NT, "geometry");
     // SLAB: every wave owns a private 32-column block (waves 1 x NW: geometry 1).  No weight byte is read by two waves, so a wave moves its
     // OWN 32 weight rows (pieces PPW w .. PPW w + PPW - 1 of every stage), takes each landed stage from its ring slot into registers,
     // refills the slot with stage j + NSB at once, and needs no barrier between the one that publishes the codes and the epilogue.
@@ -179,9 +178,6 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
                 constexpr int later = NJ - 1 - decltype(jc)::value;  // stages issued behind stage j so far
                 if (decltype(jc)::value == j) wait_vmcnt<PPW * (later < NSB - 1 ? later : NSB - 1)>();
             });
-#ifdef SDNQ_AQ_LAB
-            if (!(p.lab & 2))
-#endif
             static_for_up<KS>([&](auto ksc) { dst[decltype(ksc)::value] = MT::load(ldsB + (j % NSB) * B_STAGE, wave * 32 + (lane & 31), decltype(ksc)::value, lane >> 5); });
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -237,17 +233,6 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         // one test per pass, not per chunk: every row of the wave on the lean path (scale finite and ordinary -- anything but an all-zero
         // / inf / nan row), else the general path for all four rows (same codes: quant8 takes the same lean branch lane by lane)
         const bool all_fast = __builtin_amdgcn_ballot_w64(!rd.fast) == 0;
-#ifdef SDNQ_AQ_LAB
-        if (p.lab & 16) {
-            if constexpr (SLAB) {
-                if (ps == PS - 1) {
-#pragma unroll
-                    for (int j = 0; j < DF; ++j) drainB(j, fbr[j]);
-                }
-            }
-            continue;
-        }
-#endif
         if (all_fast) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -281,27 +266,24 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     SDNQ_PHASE_STAMP(p.trace, 2);
 
     // ---- K loop: weight stages through the ring, activation fragments from the resident image ----------------------------------------
-    typename MT::acc_t acc[NACC];
+    // A wave holds ONE 32 x 32 accumulator.  Its zeroing here and the epilogue below stand in a loop of one trip over the wave's blocks:
+    // written without the loop statement, the 64 x 128 kernels come out with a branch and a register allocated differently
+    // (tools/compare_kernels.py), and this kernel's code is kept as measured.
+    typename MT::acc_t acc;
 #pragma unroll
-    for (int a = 0; a < NACC; ++a)
+    for (int blk = 0; blk < 1; ++blk)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[a][e] = 0;
-    const int wm = (wave / (BN / 32)) * NACC, wn = wave % (BN / 32);  // first 32-row block, 32-column block of the wave
+        for (int e = 0; e < 16; ++e) acc[e] = 0;
+    const int wm = wave / (BN / 32), wn = wave % (BN / 32);  // 32-row block, 32-column block of the wave
     const int frow = lane & 31, fgrp = lane >> 5;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's codes and scales are in LDS before the first barrier lets anyone read them
-#ifdef SDNQ_AQ_LAB
-    const int lab = __builtin_amdgcn_readfirstlane(p.lab);
-#else
-    constexpr int lab = 0;  // (run-time switches inside the K loop cost it 35 %: a lab build only)
-#endif
-    typename MT::frag_t fa[2][NACC][KS];
+    typename MT::frag_t fa[2][KS];
     if constexpr (DIRECT) {
         // Direct form: the slab loop below with the weight fragments already in registers.  Sub-step ks of stage kt multiplies
         // fbd[kt % RD][ks] as soon as that load has landed, and the register is reloaded with the same sub-step of stage kt + RD.
         auto read_a = [&](auto setc, auto ksc, int st) {
             constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
-#pragma unroll
-            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+            fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
         };
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -312,12 +294,9 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
                 __builtin_amdgcn_sched_barrier(0);
                 static_for_up<KS>([&](auto ksc) {
                     constexpr int ks = decltype(ksc)::value;
-                    if (!(lab & 4)) {
-#pragma unroll
-                        for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fbd[slot][ks], fa[sx][a][ks]);
-                    }
+                    MT::mma(acc, fbd[slot][ks], fa[sx][ks]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (kt + 1 < NJ) { if (!(lab & 2)) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1); }
+                    if constexpr (kt + 1 < NJ) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1);
                     if constexpr (kt + RD < NJ) issueD(std::integral_constant<int, slot>{}, ksc, kt + RD);
                     __builtin_amdgcn_sched_barrier(0);
                 });
@@ -331,8 +310,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         // fragments stay software-pipelined one stage deep over two register sets (the stage count is a template constant: unrolled).
         auto read_a = [&](auto setc, auto ksc, int st) {
             constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
-#pragma unroll
-            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+            fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
         };
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -344,12 +322,9 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
                 __builtin_amdgcn_sched_barrier(0);
                 static_for_up<KS>([&](auto ksc) {
                     constexpr int ks = decltype(ksc)::value;
-                    if (!(lab & 4)) {
-#pragma unroll
-                        for (int a = 0; a < NACC; ++a) MT::mma(acc[a], kt < DF ? fbr[kt < DF ? kt : 0][ks] : fbs[ks], fa[sx][a][ks]);
-                    }
+                    MT::mma(acc, kt < DF ? fbr[kt < DF ? kt : 0][ks] : fbs[ks], fa[sx][ks]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (kt + 1 < NJ) { if (!(lab & 2)) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1); }
+                    if constexpr (kt + 1 < NJ) read_a(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             }
@@ -362,8 +337,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
         typename MT::frag_t fb[2][KS];
         auto read_stage = [&](auto setc, auto ksc, int st, int slot) {
             constexpr int sx = decltype(setc)::value, ks = decltype(ksc)::value;
-#pragma unroll
-            for (int a = 0; a < NACC; ++a) fa[sx][a][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, (wm + a) * 32 + frow, ks, fgrp);
+            fa[sx][ks] = MT::load(ldsA + (st < nk ? st : 0) * A_STAGE, wm * 32 + frow, ks, fgrp);
             fb[sx][ks] = MT::load(ldsB + slot * B_STAGE, wn * 32 + frow, ks, fgrp);
         };
         wait_vmcnt<(AHEAD - 1) * PPW>();  // stage 0 (this wave's pieces; the barrier makes it everybody's)
@@ -377,20 +351,17 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
             wait_vmcnt<(NSB - 2) * PPW>();                     // this wave's pieces of stage kt + 1 have landed
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its reads of stage kt have retired: the slot may be refilled
             __builtin_amdgcn_sched_barrier(0);
-            if (!(lab & 8)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             const int slot_free = slot_c;
             slot_c = (slot_c + 1 == NSB) ? 0 : slot_c + 1;
             // MFMA ks of stage kt, then read ks of stage kt + 1 (the last sub-step's reads retire under the next barrier's wait; KS <= 4)
             static_for_up<KS>([&](auto ksc) {
                 constexpr int ks = decltype(ksc)::value;
-                if (!(lab & 4)) {
-#pragma unroll
-                    for (int a = 0; a < NACC; ++a) MT::mma(acc[a], fb[sx][ks], fa[sx][a][ks]);
-                }
+                MT::mma(acc, fb[sx][ks], fa[sx][ks]);
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(lab & 2)) read_stage(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1, slot_c);
-                if constexpr (ks == 0) { if (!(lab & 1)) issueB(kt + NSB, slot_free); }
+                read_stage(std::integral_constant<int, sx ^ 1>{}, ksc, kt + 1, slot_c);
+                if constexpr (ks == 0) issueB(kt + NSB, slot_free);
                 __builtin_amdgcn_sched_barrier(0);
             });
         };
@@ -415,8 +386,8 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
     constexpr int OUT_ROW = BN * 2 + 16;
     static_assert(BM * OUT_ROW <= NJ * A_STAGE + NSL * B_STAGE, "output staging fits the operand area");
 #pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-        const int ml = (wm + a) * 32 + frow;
+    for (int blk = 0; blk < 1; ++blk) {  // (one block; the loop statement is kept for the reason given at the accumulator above)
+        const int ml = wm * 32 + frow;
         const float sa = s_xs[ml];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -424,7 +395,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
             float o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float vv = MT::tof(acc[a], 4 * q + e) * sa;
+                const float vv = MT::tof(acc, 4 * q + e) * sa;
                 if constexpr (HAS_BIAS) o[e] = fmaf(vv, s_sb[nl0 + e], s_bias[nl0 + e]);
                 else o[e] = vv * s_sb[nl0 + e];
             }

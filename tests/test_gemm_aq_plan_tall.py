@@ -3,8 +3,7 @@ the function is host code.
 
 The rule, written out: int8, K of at most five 128-byte stages, more tiles of 64 x 128 than CUs, but no more than the resident
 workgroup slots of the tall form -> geometry 2, the 64 x 128 tile on a 2-slot weight ring, two workgroups per CU.  Its prefetch room
-is resident slots - tiles = 2 CUs - tiles.  Geometry 3 (128 x 128, one workgroup per CU) is built and reachable through the forcing
-hook only.  Everything else answers as tests/test_gemm_aq_plan.py's table says; a few of its rows are repeated here as a guard."""
+is resident slots - tiles = 2 CUs - tiles.  Everything else answers as tests/test_gemm_aq_plan.py's table says; a few of its rows are repeated here as a guard."""
 import pytest
 
 from sdnq_amd import _lib
@@ -13,8 +12,8 @@ from tests import aq_internal as A
 MM_I8, MM_FP8 = 0, 1
 BF16 = 1
 CUS = 256
-GEO_TALL, GEO_128x128 = 2, 3
-SHAPE = {0: (64, 128), 1: (32, 256), 2: (64, 128), 3: (128, 128)}
+GEO_TALL = 2
+SHAPE = {0: (64, 128), 1: (32, 256), 2: (64, 128)}
 
 #        mm      M     N     K    cus  geometry tiles_m tiles_n group_m room
 TABLE = [
@@ -68,15 +67,16 @@ def test_supported_follows_the_plan():
 
 
 def test_forced_tall_geometries():
-    """The hook reaches both tall forms; on a problem they have no kernel for (fp8, K > 640) the shape rule answers instead."""
+    """The hook reaches the tall form; on a problem it has no kernel for (fp8, K > 640) the shape rule answers instead.  An id the hook
+    does not know (3) answers as id 1 does."""
     A.set_geometry(GEO_TALL)
     p = A.plan(MM_I8, 200, 136, 384, CUS)
     assert (p["geometry"], p["bm"], p["bn"], p["tiles_m"], p["tiles_n"], p["group_m"], p["prefetch_room"]) == (2, 64, 128, 4, 2, 4, 504)
     assert A.plan(MM_I8, 1024, 1280, 1280, CUS)["geometry"] == 1
     assert A.plan(MM_FP8, 200, 136, 384, CUS)["geometry"] == 0
-    A.set_geometry(GEO_128x128)
-    p = A.plan(MM_I8, 200, 136, 384, CUS)
-    assert (p["geometry"], p["bm"], p["bn"], p["tiles_m"], p["tiles_n"], p["group_m"], p["prefetch_room"]) == (3, 128, 128, 2, 2, 2, 252)
-    assert A.plan(MM_I8, 4096, 640, 768, CUS)["geometry"] == 0
+    A.set_geometry(A.GEO_32x256)
+    as_one = A.plan(MM_I8, 200, 136, 384, CUS)
+    A.set_geometry(3)
+    assert A.plan(MM_I8, 200, 136, 384, CUS) == as_one and as_one["geometry"] == 1
     A.set_geometry(A.GEO_64x128)
     assert A.plan(MM_I8, 4096, 640, 640, CUS)["geometry"] == 0

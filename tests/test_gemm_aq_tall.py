@@ -1,6 +1,5 @@
-"""GPU parity of the one-launch w8a8 Linear on the tall tile geometries of csrc/gemm_aq.hip (K <= 640): 2 = the 64 x 128 tile on a 2-slot
-weight ring, two workgroups per CU (what the shape rule picks at 4096 x 640 x 640), and 3 = 128 x 128 with two accumulators per wave
-(reachable through the forcing hook only).
+"""GPU parity of the one-launch w8a8 Linear on the tall tile geometry of csrc/gemm_aq.hip (K <= 640): 2 = the 64 x 128 tile on a 2-slot
+weight ring, two workgroups per CU (what the shape rule picks at 4096 x 640 x 640).
 
 Every output bit equals the two-launch route (sdnq_hip_rowquant + sdnq_hip_scaled_mm) and the CPU oracle -- equality, no tolerance.
 Shapes: M below one tile and ragged against 64- and 128-row blocks; N of one ragged column tile up to five column tiles; K of one
@@ -19,11 +18,11 @@ pytestmark = pytest.mark.gpu
 
 from sdnq_amd import _lib, ops  # noqa: E402
 
-GEO_TALL, GEO_128x128 = 2, 3
-GEOMETRIES = [GEO_TALL, GEO_128x128]
+GEO_TALL = 2
+GEOMETRIES = [GEO_TALL]
 SHAPES = [(m, n, k) for m in (33, 160, 200) for n in (8, 136, 640) for k in (128, 384, 640)]
-# more tiles than the 256-CU part holds at once: 65 x 8 = 520 tiles of 64 x 128 on 512 slots; 65 x 5 = 325 tiles of 128 x 128 on 256
-MULTI_ROUND = {GEO_TALL: (4160, 1024, 128), GEO_128x128: (8256, 640, 128)}
+# more tiles than the 256-CU part holds at once: 65 x 8 = 520 tiles of 64 x 128 on 512 slots
+MULTI_ROUND = {GEO_TALL: (4160, 1024, 128)}
 
 
 @pytest.fixture

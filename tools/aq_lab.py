@@ -69,8 +69,8 @@ def phases(run):
 
 
 if "--grouped" in args:
-    # the linked q / k / v problem, M x (G x N) x K: the grouped one-launch form (sdnq_hip_linear_w8a8_fused_grouped; the arm is the library's:
-    # a -DSDNQ_AQ_GROUPED_LAB build picks it by SDNQ_HIP_FUSED_ROWQUANT_GROUPED_ARM) against ops.rowquant + ops.scaled_mm_grouped.
+    # the linked q / k / v problem, M x (G x N) x K: the grouped one-launch form (sdnq_hip_linear_w8a8_fused_grouped: the 32 x 256 tile,
+    # two per CU) against ops.rowquant + ops.scaled_mm_grouped.
     # usage: python tools/aq_lab.py --grouped [MxGxNxK ...]
     args.remove("--grouped")
     for m, g, n, k in ([tuple(int(v) for v in a.split("x")) for a in args] or [(1024, 3, 1280, 1280)]):
