@@ -287,8 +287,10 @@ int sdnq_hip_scaled_mm_grouped(int mm_dtype, const void* a, const float* sa, con
                                sdnq_stream_t stream);
 
 /* Tuning hook (development / benchmarking only, process-wide): force the GEMM tile configuration of every following scaled
- * matmul launch (ids: sdnq_amd/csrc/gemm.hip, launch_tiles); < 0 restores the built-in shape heuristics.  Never needed for
- * correct results -- every configuration produces identical outputs. */
+ * matmul launch; < 0 restores the built-in shape heuristics.  The int8 / fp8 ids (sdnq_amd/csrc/gemm.hip, launch_tiles) are
+ * 0 256x256, 1 64x128, 2 64x64, 3 256x128, 17 128x128, 19 256x128 fine ping-pong, 20 256x256 half-tile ring, 25 256x160 and
+ * 28 the 64x80 K-split tile (int8 problems it takes); any other id runs the heuristics.  Never needed for correct results --
+ * every configuration produces identical outputs. */
 void sdnq_hip_set_tile_override(int tile_id);
 
 /* the float GEMM of sdnq_hip_linear_float over the STACKED dequantized weights of layers that consume one activation, each

@@ -35,9 +35,6 @@ constexpr int BKB = 128;  // default bytes of K per LDS stage row (a full 128-by
 
 __device__ const uint4 g_zero16 = {0u, 0u, 0u, 0u};  // source of K-tail chunks for the LDS-DMA
 
-#ifdef SDNQ_TRACE2
-__device__ unsigned g_trace2[64];
-#endif
 #ifdef SDNQ_TRACE  // development build only: per-workgroup phase timestamps (shader clock), read back by tools/trace_gemm.py
 __device__ unsigned long long g_trace[4096 * 8];
 // launch filter (tools/trace_in_step.py): only launches of this M x N x K are recorded, so that after a replay of a whole step's graph the
@@ -108,24 +105,11 @@ struct TileView {
     int64_t n_lim;         // valid channels from the tile's first one (may exceed BN)
 };
 
-// the 16-byte store of a finished output piece.  SDNQ_STORE_MODE (lab builds): 1 non-temporal, 2 write-through (sc1), 3 sc0 sc1
-// Default 1: the outputs are written once and not read again by this kernel; non-temporal stores measured -2..-9 % on the
-// output-heavy GEMMs (1024 x 10240 x 1280: 24.9 -> 22.6 us, 4096 x 5120 x 640: 31.3 -> 28.9 us) and never slower (tools/micro/gemm_lab.hip).
-#ifndef SDNQ_STORE_MODE
-#define SDNQ_STORE_MODE 1
-#endif
+// the 16-byte store of a finished output piece, non-temporal: the outputs are written once and not read again by this kernel; it
+// measured -2..-9 % on the output-heavy GEMMs (1024 x 10240 x 1280: 24.9 -> 22.6 us, 4096 x 5120 x 640: 31.3 -> 28.9 us) and never
+// slower than a plain or a write-through store (tools/micro/gemm_lab.hip).
 __device__ __forceinline__ void store16(void* dst, const uint4& v) {
-#if SDNQ_STORE_MODE == 1
     __builtin_nontemporal_store((v4i){(int)v.x, (int)v.y, (int)v.z, (int)v.w}, (v4i*)dst);
-#elif SDNQ_STORE_MODE == 2
-    const v4i w = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(w) : "memory");
-#elif SDNQ_STORE_MODE == 3
-    const v4i w = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(w) : "memory");
-#else
-    *(uint4*)dst = v;
-#endif
 }
 
 // address of output row gm, channel `c` of the tile (global channel gn0 = n0 + c)
@@ -195,18 +179,6 @@ template <> struct MmaTraits<MM_W8BF16> : FloatMma<MM_W8BF16> {};
 template <> struct MmaTraits<MM_W8F16> : FloatMma<MM_W8F16> {};
 template <> struct MmaTraits<MM_W8BF16U> : FloatMma<MM_W8BF16U> {};
 template <> struct MmaTraits<MM_W8F16U> : FloatMma<MM_W8F16U> {};
-// int8 on v_mfma_i32_16x16x64_i8: 16 x 16 output tiles (4 accumulators per lane: lane l holds n = 4 (l >> 4) + 0..3 of m = l & 15 --
-// again a run of 4 output channels of one row), 64 bytes of K per instruction.  Same LDS image and loaders; what it buys is
-// tile shapes in multiples of 16: 64 x 80 tiles cut the 1024 x 1280 outputs of the SDXL attention / feed-forward projections into
-// exactly 256 workgroups with 25 % fewer LDS-fill bytes per CU than 160 tiles of 64 x 128.
-enum { MM_I8_16 = 7 };
-template <> struct MmaTraits<MM_I8_16> {
-    typedef v4i acc_t;
-    static constexpr int MS = 16;
-    static constexpr int KB = 64;
-    static __device__ __forceinline__ void zero(acc_t& c) { c = (v4i){0, 0, 0, 0}; }
-    static __device__ __forceinline__ float tof(const acc_t& c, int i) { return (float)c[i]; }
-};
 template <int MM> constexpr bool is_w8a16 = (MM == MM_W8BF16 || MM == MM_W8F16 || MM == MM_W8BF16U || MM == MM_W8F16U);
 template <int MM> constexpr bool is_w8_bf16 = (MM == MM_W8BF16 || MM == MM_W8BF16U);
 template <int MM> constexpr bool is_w8_signed = (MM == MM_W8BF16 || MM == MM_W8F16);
@@ -306,8 +278,6 @@ template <int MM> struct FragOps {
             c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, w), __builtin_bit_cast(v8bf, x), c, 0, 0, 0);
         } else if constexpr (is_w8a16<MM>) {
             c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, w), __builtin_bit_cast(v8h, x), c, 0, 0, 0);
-        } else if constexpr (MM == MM_I8_16) {
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x, c, 0, 0, 0);
         } else if constexpr (MM == SDNQ_MM_I8) {
             c = __builtin_amdgcn_mfma_i32_32x32x32_i8(w, x, c, 0, 0, 0);
         } else if constexpr (MM == MM_BF16) {
@@ -355,23 +325,18 @@ template <> struct FragOps<SDNQ_MM_FP8> {
 //            ks run, the fragments of sub-step ks+1 (or of the next stage, right after the barrier) are already being
 //            read into the other of two fragment sets, so neither the LDS latency nor the two waves of a SIMD reading
 //            LDS in lock-step after every barrier leave the matrix pipe idle.
-//   LD_PP  : the LD_DMA ring driven PING-PONG by the two halves of an 8-wave workgroup (waves 0-3 / 4-7: wave w and wave w+4
-//            sit on the same SIMD).  Each half alternates a LOAD phase (all LDS->register fragment reads of one K stage, its
-//            share of the LDS-DMA issue for the stage NS-1 ahead, counted vmcnt) with an MFMA phase (the stage's matrix
-//            instructions back to back at raised priority), the second half running one phase behind the first, one raw
-//            s_barrier per phase: while one wave of a SIMD feeds the matrix pipe, its partner does the issue-heavy work
-//            (an LDS-DMA costs its wave ~60-180 issue cycles) that in the lock-step schedules above leaves the pipe idle.
-//   LD_8P  : the fine-grained form of the ping-pong (round 3).  A K stage is consumed in TWO phases -- phase 0: every weight
+//   LD_8P  : the LD_DMA ring driven PING-PONG by the two halves of an 8-wave workgroup (round 3; waves 0-3 / 4-7: wave w and wave
+//            w+4 sit on the same SIMD).  A K stage is consumed in TWO phases -- phase 0: every weight
 //            fragment + the first half of the wave's activation row blocks, phase 1: the second half -- and each phase is
 //            {LDS->register reads of THIS phase, then this wave's share of the LDS-DMA issue (half a stage), raw barrier,
 //            lgkmcnt(0), the phase's MFMAs back to back at raised priority, raw barrier}.  The second half of the workgroup
 //            (waves 4-7, the SIMD partners of waves 0-3) runs one barrier behind, so at any time one wave of every SIMD is
 //            in its MFMA section while its partner does the slow-issuing work (an LDS-DMA piece occupies its wave's issue
-//            port for 60-180 cycles, during which an in-order wave cannot feed the matrix pipe).  What differs from LD_PP:
-//            reads come BEFORE the DMA issue and are waited for AFTER the barrier (their latency hides under the DMA issue
-//            and the barrier instead of delaying the partner's release), the counted vmcnt sits once per stage, and the
-//            phases are half as long (8 MFMAs), so neither role starves.  Hazards (slots = intervals between barriers;
-//            group 0 reads/issues in even slots, group 1 in odd ones):
+//            port for 60-180 cycles, during which an in-order wave cannot feed the matrix pipe; in the lock-step schedules
+//            above that leaves the pipe idle).  The reads come BEFORE the DMA issue and are waited for AFTER the barrier (their
+//            latency hides under the DMA issue and the barrier instead of delaying the partner's release), the counted vmcnt
+//            sits once per stage, and the phases are short (8 MFMAs), so neither role starves.  Hazards (slots = intervals
+//            between barriers; group 0 reads/issues in even slots, group 1 in odd ones):
 //              RAW  stage j is first read in phase 2j; every wave waits for ITS pieces of stage j (vmcnt leaving the AHEAD-1
 //                   younger stages in flight) at the end of the read/issue section of phase 2j-1, in front of a barrier that
 //                   both groups pass before phase 2j's reads;
@@ -400,17 +365,17 @@ template <> struct FragOps<SDNQ_MM_FP8> {
 //              a half-tile is refilled two phases after its last read (the WAR rule of LD_8P) and needed six phases after that; every
 //              phase ends its read/issue section with vmcnt(8): all but the four youngest half-tiles have landed, which covers the
 //              reads of the next phase.  Needs K % 128 == 0 (a partial K tile would read the next row's bytes).
-//   LD_OV  : the LD_DMA ring with every stream of a K stage OVERLAPPED (round 5; the one-round tiles of the bs = 1 steps).  In LD_DMA a
+//   LD_OG  : the LD_DMA ring with every stream of a K stage OVERLAPPED (round 5; the 256x160 tile of 32x160 wave tiles).  In LD_DMA a
 //            stage is {counted vmcnt, barrier, this wave's DMA pieces, all fragment reads, lgkmcnt, the MFMAs}: the ~85 issue cycles of
 //            every LDS-DMA piece, the LDS reads (64 KB per stage of a 64x128 tile: 256 LDS cycles) and the matrix time of the two waves
 //            of a SIMD ADD UP -- 907 cycles per 24.5-KB stage = 27 B/clk/CU where the fill path alone sustains 45-59
-//            (profiles/r03_dma_shape.txt).  Here the fragments of stage kt + 1 are read (right after the barrier, into the other of two
-//            register sets) while the MFMAs of stage kt run, and the DMA pieces of the stage NS ahead are issued BETWEEN those MFMAs --
-//            one piece per matrix instruction or two, so the wave's issue port is busy with the piece while its MFMA occupies the pipe.
-//            The ring slot of stage kt is free as soon as every wave's reads of it have retired (lgkmcnt(0) in front of the barrier that
-//            opens stage kt), i.e. one stage EARLIER than in LD_DMA: NS slots carry NS stages of DMA in flight.
-//   LD_OG  : LD_OV with the fragments read one K SUB-STEP ahead instead of one stage (wave tiles of several MFMA tiles; see the loop).
-enum { LD_DMA = 0, LD_PIPE = 2, LD_PP = 3, LD_8P = 4, LD_HT = 5, LD_OV = 6, LD_OG = 7 };
+//            (profiles/r03_dma_shape.txt).  Here the fragments of the NEXT K sub-step are read (into the other of two register sets
+//            of TM + TN fragments) while the MFMAs of this one run, and the DMA pieces of the stage NS ahead are issued BETWEEN those
+//            MFMAs -- one piece per matrix instruction or two, so the wave's issue port is busy with the piece while its MFMA occupies
+//            the pipe.  The ring slot of stage kt is free as soon as every wave's reads of it have retired (lgkmcnt(0) in front of the
+//            barrier that opens the next stage), i.e. one stage EARLIER than in LD_DMA: NS slots carry NS stages of DMA in flight.
+//            See the loop for the order of a trip.
+enum { LD_DMA = 0, LD_PIPE = 2, LD_8P = 4, LD_HT = 5, LD_OG = 7 };
 constexpr int HT_BYTES = 16384, HT_SLOTS = 8;
 
 // LP: dequantize_fp32=False with BFLOAT16 scales -- the reference's eager epilogue runs on bf16 tensors (kernel_wrappers.py:132-144:
@@ -436,10 +401,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                    (int)((hk_flags >> 16) & 1u), (int)((hk_flags >> 17) & 1u), hk_mg_per_group, hk_mg_group_m, ((hk_flags >> 18) & 1u) != 0};
     typedef MmaTraits<MM> MT;
     constexpr int WAVES_M = BM / WM, WAVES_N = BN / WN, NW = WAVES_M * WAVES_N, NT = NW * 64;
-    constexpr int MS = MT::MS;                 // MFMA output tile edge: 32, or 16 for MM_I8_16
+    constexpr int MS = MT::MS;                 // MFMA output tile edge
     constexpr int TM = WM / MS, TN = WN / MS;
-    static_assert(WM % MS == 0 && WN % MS == 0, "wave tile in whole MFMA tiles");
-    static_assert(MS == 32 || (EPI <= EPI_BIAS1D && BM <= 128), "16x16 tiles: plain epilogues of the small tiles only");
+    static_assert(MS == 32 && WM % MS == 0 && WN % MS == 0, "wave tile in whole 32x32 MFMA tiles");
     constexpr int RPP = 1024 / BK;   // tile rows per 1-KiB DMA piece (8 for 128-byte rows, 16 for 64-byte rows)
     constexpr int LPR = BK / 16;     // lanes (16-byte chunks) per row
     // the weight operand of the fused dequantize GEMM holds one byte per K element where the activations hold two
@@ -485,13 +449,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
     // where each field is first used, and the tile mapping -> TileView -> descriptor chain then waits for three or four DEPENDENT
     // round trips to a cold scalar cache (~600-800 cycles each) before the first LDS-DMA can be issued.  The empty asm makes all of
     // them live in SGPRs here, so the loads go out together behind a single s_waitcnt.
-#ifndef SDNQ_NO_KERNARG_BATCH
     asm volatile("" ::"s"(hk_a), "s"(hk_b), "s"(hk_lda), "s"(hk_ldb), "s"(hk_M), "s"(hk_N), "s"(hk_K), "s"(hk_tiles_m), "s"(hk_tiles_n), "s"(hk_flags),
                  "s"(hk_mg_per_group), "s"(hk_mg_group_m));
 #ifndef SDNQ_PRELOAD_GEMM  // without preload everything is fetched here; with it the struct's fields are requested below, behind the DMAs
     asm volatile("" ::"s"(p_.sb), "s"(p_.bias), "s"(p_.out), "s"(p_.units), "s"(p_.ldc), "s"(p_.unit_n), "s"(p_.mg_tail), "s"(p_.mg_unit),
                  "s"(p_.bias_dtype), "s"(p_.seg_n), "s"(p_.out_hw), "s"(p_.sa));
-#endif
 #endif
 #ifdef SDNQ_TRACE
     const bool tr_on = g_trace_shape[0] == 0 || (g_trace_shape[0] == hk_M && g_trace_shape[1] == hk_N && g_trace_shape[2] == hk_K);
@@ -711,7 +673,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
         issue_ht(std::integral_constant<int, 2>{}, 5, 1);
     }
     TRACE(1);
-#if defined(SDNQ_PRELOAD_GEMM) && !defined(SDNQ_NO_KERNARG_BATCH)
+#ifdef SDNQ_PRELOAD_GEMM
     asm volatile("" ::"s"(p_.sb), "s"(p_.bias), "s"(p_.out), "s"(p_.ldc), "s"(p_.bias_dtype), "s"(p_.seg_n), "s"(p_.out_hw), "s"(p_.sa));
 #endif
     if (hk.grouped) {
@@ -832,60 +794,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                 if (U == 1 || kt + u < nk) mma_set(std::integral_constant<int, cur>{});
             });
         }
-    } else if constexpr (LD == LD_PP) {
-        static_assert(NW == 8, "ping-pong schedule: two halves of four waves");
-        typedef typename FragOps<MM>::frag_t frag_t;
-        constexpr int KS = BK / MT::KB;
-        frag_t fa[KS][TM];
-        typename FragOps<MM>::fragb_t fb[KS][TN];
-        const int half = __builtin_amdgcn_readfirstlane(wave >> 2);
-        // Time is cut into slots by workgroup-wide barriers.  Half 0 runs LOAD(j) in slot 2j and MFMA(j) in slot 2j+1, half 1
-        // LOAD(j) in slot 2j+1 and MFMA(j) in slot 2j+2.
-        //   RAW: stage j is first read in slot 2j; every wave waits for ITS pieces of stage j (counted vmcnt) before the barrier
-        //        that ends slot 2j-1 (half 0: end of MFMA(j-1); half 1: end of LOAD(j-1)).
-        //   WAR: the DMA for stage j+AHEAD overwrites the ring slot of stage j-1; it is issued in LOAD(j) (slots 2j / 2j+1), after
-        //        the barrier that ends slot 2j-1, by which time both halves have finished reading stage j-1 (lgkmcnt(0) before
-        //        the barrier that ends a LOAD phase).
-        wait_ahead();  // own pieces of stage 0 (stages 1..AHEAD-1 stay in flight)
-        __builtin_amdgcn_s_barrier();
-        if (half == 1) __builtin_amdgcn_s_barrier();  // the stagger: half 1 sits out slot 0
-#pragma nounroll
-        for (int kt = 0; kt < nk; ++kt) {
-            // ---- LOAD(kt)
-            issue(kt + AHEAD);
-            {
-                const uint8_t* sA = lds + slot_c * STAGE_BYTES;
-                const uint8_t* sB = sA + BM * BK;
-                slot_c = (slot_c + 1 == NS) ? 0 : slot_c + 1;
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-                    for (int i = 0; i < TN; ++i) fb[ks][i] = FragOps<MM>::template loadb<BKW>(sB, wn * WN + i * MS + frow, ks, fgrp, hk.swz);
-#pragma unroll
-                    for (int j = 0; j < TM; ++j) fa[ks][j] = FragOps<MM>::template load<BK>(sA, wm * WM + j * MS + frow, ks, fgrp, hk.swz);
-                }
-            }
-            if (half == 1) wait_ahead();  // own pieces of stage kt+1, read by half 0 in the next slot
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            // ---- MFMA(kt)
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int i = 0; i < TN; ++i)
-                    { const auto wfrag = FragOps<MM>::prep(fb[ks][i], wrow[i], wflip);
-#pragma unroll
-                for (int j = 0; j < TM; ++j) FragOps<MM>::mma(acc[i][j], wfrag, fa[ks][j]); }
-            __builtin_amdgcn_s_setprio(0);
-            if (half == 0) wait_ahead();  // own pieces of stage kt+1, read by this half right after the barrier
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (half == 0) __builtin_amdgcn_s_barrier();  // matches half 1's extra barrier at the start
     } else if constexpr (LD == LD_8P) {
         static_assert(NW == 8 && !JOINT && (TM % 2) == 0 && NS >= 3 && A_PIECES >= 1 && B_PIECES >= 1, "fine ping-pong: 8 waves, even activation blocks");
         typedef typename FragOps<MM>::frag_t frag_t;
@@ -994,70 +902,21 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                 return (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
         };
-#ifdef SDNQ_TRACE2  // development build: per-segment cycle totals of waves 0 and 4 (tools/micro/gemm_lab.hip prints them)
-        unsigned tacc[4][5] = {};
-        unsigned ts0 = (unsigned)__builtin_amdgcn_s_memtime(), ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0;
-#define TS(v) v = (unsigned)__builtin_amdgcn_s_memtime()
-#else
-#define TS(v) do { } while (0)
-#endif
-        auto phase_sync = [&](bool reads) {
+        auto phase_sync = [&]() {
             // end of the read / issue section: counted vmcnt (four half-tiles stay in flight), barrier, then this phase's own reads
             __builtin_amdgcn_sched_barrier(0);
-            TS(ts1);
             wait_vmcnt<8>();
-            TS(ts2);
             __builtin_amdgcn_s_barrier();
-            if (reads) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            TS(ts3);
             __builtin_amdgcn_s_setprio(1);
         };
-        auto phase_end = [&](auto qc) {
+        auto phase_end = [&]() {
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-            TS(ts4);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-#ifdef SDNQ_TRACE2
-            constexpr int q = decltype(qc)::value;
-            const unsigned ts5 = (unsigned)__builtin_amdgcn_s_memtime();
-            tacc[q][0] += ts1 - ts0; tacc[q][1] += ts2 - ts1; tacc[q][2] += ts3 - ts2; tacc[q][3] += ts4 - ts3; tacc[q][4] += ts5 - ts4;
-            ts0 = ts5;
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         };
-#ifdef SDNQ_LAB_LUT4
-        // TIMING-ONLY lab build (wrong results; _build.py --define SDNQ_LAB_LUT4): what a fused 4-bit loader would add to this K loop.  Every weight
-        // fragment is treated as 8 bytes of packed codes + a 16-entry byte table of its (row, group) and expanded to the 16 int8 codes
-        // of the MFMA operand with the cheapest sequence found (nibble split, two v_perm per 4 codes, bit-3 blend; the even / odd
-        // interleave is assumed away by a k-permuted activation operand): 34 vector-ALU instructions per fragment, placed in the
-        // read / issue section of the phase (where the partner wave's MFMA section can hide them).  No table build, no table traffic.
-        v4i lut_t = *(const v4i*)(lds + VEC_OFF + (lane & 15) * 16);
-        auto lut_expand = [&](fragb_t& f) {
-            if constexpr (NPC == 1) {
-                v4i o;
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const u32 x = (u32)f[d];
-                    const u32 cl = x & 0x0f0f0f0fu, chh = (x >> 4) & 0x0f0f0f0fu;
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const u32 c = h ? chh : cl;
-                        const u32 sel = c & 0x07070707u;
-                        const u32 p0 = __builtin_amdgcn_perm((u32)lut_t[1], (u32)lut_t[0], sel);
-                        const u32 p1 = __builtin_amdgcn_perm((u32)lut_t[3], (u32)lut_t[2], sel);
-                        const u32 m = ((c >> 3) & 0x01010101u) * 255u;
-                        o[2 * d + h] = (int)((p1 & m) | (p0 & ~m));
-                    }
-                }
-                f = o;
-            }
-        };
-#define LUT_EXPAND(fb) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) lut_expand(fb[ks]); } while (0)
-#else
-#define LUT_EXPAND(fb) do { } while (0)
-#endif
         wait_vmcnt<8>();  // HA0(0), HB0(0) have landed: everything phase 0 reads
         __builtin_amdgcn_s_barrier();
         if (grp == 1) __builtin_amdgcn_s_barrier();  // the stagger: group 1 sits out the first slot
@@ -1071,29 +930,27 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
             // ---- phase 0: B0 (A0 was read in the previous phase 3) -> acc[0][0..1]; refill HB1 for K tile t + 1
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) fb0[ks] = ldB(ks, PAR * HT_BYTES);
-            LUT_EXPAND(fb0);
             __builtin_amdgcn_sched_barrier(0);
             issue_ht(std::integral_constant<int, 3>{}, 6 + (PAR ^ 1), t + 1);
-            phase_sync(true);
+            phase_sync();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 { const auto wfrag = FragOps<MM>::prep(fb0[ks], wrow[0], wflip);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) FragOps<MM>::mma(acc[0][j], wfrag, fa0[ks][j]); }
-            phase_end(std::integral_constant<int, 0>{});
+            phase_end();
             // ---- phase 1: B1 -> acc[1][0..1]; refill HA1 for K tile t + 1
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) fb1[ks] = ldB(ks, (2 + PAR) * HT_BYTES);
-            LUT_EXPAND(fb1);
             __builtin_amdgcn_sched_barrier(0);
             issue_ht(std::integral_constant<int, 1>{}, 2 + (PAR ^ 1), t + 1);
-            phase_sync(true);
+            phase_sync();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 { const auto wfrag = FragOps<MM>::prep(fb1[ks], wrow[1], wflip);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) FragOps<MM>::mma(acc[1][j], wfrag, fa0[ks][j]); }
-            phase_end(std::integral_constant<int, 1>{});
+            phase_end();
             // ---- phase 2: A1 -> acc[1][2..3]; refill HA0 for K tile t + 2
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
@@ -1101,13 +958,13 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                 for (int j = 0; j < 2; ++j) fa1[ks][j] = ldA(ks, (2 + PAR) * HT_BYTES + j * 4096);
             __builtin_amdgcn_sched_barrier(0);
             issue_ht(std::integral_constant<int, 0>{}, PAR, t + 2);
-            phase_sync(true);
+            phase_sync();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 { const auto wfrag = FragOps<MM>::prep(fb1[ks], wrow[1], wflip);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) FragOps<MM>::mma(acc[1][2 + j], wfrag, fa1[ks][j]); }
-            phase_end(std::integral_constant<int, 2>{});
+            phase_end();
             // ---- phase 3: A0 of K tile t + 1 (its registers are free since phase 1; landed: it is the fifth-youngest half-tile) ->
             //      acc[0][2..3]; refill HB0 for K tile t + 2.  Reads per phase: 4 / 4 / 8 / 8 instead of 12 / 4 / 8 / 0.
 #pragma unroll
@@ -1116,13 +973,13 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                 for (int j = 0; j < 2; ++j) fa0[ks][j] = ldA(ks, (PAR ^ 1) * HT_BYTES + j * 4096);
             __builtin_amdgcn_sched_barrier(0);
             issue_ht(std::integral_constant<int, 2>{}, 4 + PAR, t + 2);
-            phase_sync(true);
+            phase_sync();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
                 { const auto wfrag = FragOps<MM>::prep(fb0[ks], wrow[0], wflip);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) FragOps<MM>::mma(acc[0][2 + j], wfrag, fa1[ks][j]); }
-            phase_end(std::integral_constant<int, 3>{});
+            phase_end();
         };
 #pragma nounroll
         for (int t = 0; t < nkt; t += 2) {
@@ -1130,125 +987,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
             if (t + 1 < nkt) ktile(std::integral_constant<int, 1>{}, t + 1);
         }
         if (grp == 0) __builtin_amdgcn_s_barrier();  // matches group 1's extra barrier at the start
-#ifdef SDNQ_TRACE2
-        if (blockIdx.x == 300 && (tid == 0 || tid == 256)) {
-            for (int q = 0; q < 4; ++q)
-                for (int e = 0; e < 5; ++e) g_trace2[(tid >> 8) * 20 + q * 5 + e] = tacc[q][e];
-        }
-#endif
-#undef TS
-#undef LUT_EXPAND
-    } else if constexpr (LD == LD_OV) {
-        static_assert(MS == 32, "overlapped ring: 32x32 MFMA tiles");
-        typedef typename FragOps<MM>::frag_t frag_t;
-        typedef typename FragOps<MM>::fragb_t fragb_t;
-        constexpr int KS = BK / MT::KB, NM = KS * TN * TM;
-        frag_t fa[2][KS][TM];
-        fragb_t fb[2][KS][TN];
-        // A 32x32 wave tile has ONE accumulator: its MFMAs form a dependent chain, and anything issued between two MFMAs on the same
-        // accumulator costs the forwarding path (+43 cycles per gap, MI355X_MICROARCH.md).  Odd K sub-steps accumulate into a second
-        // register set, summed once after the loop (int32: exact, so still bit-identical; fp32: one more addition order).
-        constexpr bool SPLIT_ACC = (TM * TN == 1) && (KS % 2 == 0) && (MM == SDNQ_MM_I8);  // (integer sums only: a second fp32 accumulator would make the result depend on the tile)
-        typename MT::acc_t acc_odd[1];
-        if constexpr (SPLIT_ACC) MT::zero(acc_odd[0]);
-        auto load_stage = [&](int slot, auto setc) {
-            constexpr int st = decltype(setc)::value;
-            const uint8_t* sA = lds + slot * STAGE_BYTES;
-            const uint8_t* sB = sA + BM * BK;
-#ifdef SDNQ_ABL_NOREAD
-            if (slot >= 0) return;
-#endif
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-                for (int i = 0; i < TN; ++i) fb[st][ks][i] = FragOps<MM>::template loadb<BKW>(sB, wn * WN + i * MS + frow, ks, fgrp, hk.swz);
-#pragma unroll
-                for (int j = 0; j < TM; ++j) fa[st][ks][j] = FragOps<MM>::template load<BK>(sA, wm * WM + j * MS + frow, ks, fgrp, hk.swz);
-            }
-        };
-        // one fragment read of a stage, numbered ks-major: r -> (ks, weight sub-tile i | activation sub-tile j)
-        constexpr int NRG = TM + TN, NRT = KS * NRG;
-#ifndef SDNQ_OV_NMR_NUM
-#define SDNQ_OV_NMR_NUM 3
-#endif
-        constexpr int NMR = (NM * SDNQ_OV_NMR_NUM) / 4 > 0 ? (NM * SDNQ_OV_NMR_NUM) / 4 : 1;
-        auto read_one = [&](const uint8_t* sA, const uint8_t* sB, auto setc, auto rc) {
-            constexpr int st = decltype(setc)::value, r = decltype(rc)::value, ks = r / NRG, e = r % NRG;
-#ifdef SDNQ_ABL_NOREAD
-            if (sA != nullptr) return;
-#endif
-            if constexpr (e < TN) fb[st][ks][e] = FragOps<MM>::template loadb<BKW>(sB, wn * WN + e * MS + frow, ks, fgrp, hk.swz);
-            else fa[st][ks][e - TN] = FragOps<MM>::template load<BK>(sA, wm * WM + (e - TN) * MS + frow, ks, fgrp, hk.swz);
-        };
-        // the MFMAs of fragment set `st`; dealt out between them: the fragment reads of the NEXT stage (ring slot `rslot`, into the other
-        // set) and the DMA pieces of logical stage `js` (into ring slot `slot`).  A wave that issued all its reads in one burst after the
-        // barrier sat in the LDS issue queue behind the other seven waves' bursts until nearly all 64-96 KB had been served and only then
-        // reached its first MFMA (reads + MFMAs measured as their SUM, tools/micro/build_abl.sh: nodma 64 us vs mmaonly 43.5)
-        auto mma_issue = [&](auto setc, int js, int slot, int rslot) {
-            constexpr int st = decltype(setc)::value;
-            const uint8_t* sA = lds + rslot * STAGE_BYTES;
-            const uint8_t* sB = sA + BM * BK;
-            static_for_up<NM>([&](auto mc) {
-                constexpr int mi = decltype(mc)::value, ks = mi / (TN * TM), i = (mi / TM) % TN, j = mi % TM;
-#ifndef SDNQ_ABL_NOMMA
-                if constexpr (SPLIT_ACC && (ks & 1)) FragOps<MM>::mma(acc_odd[0], FragOps<MM>::prep(fb[st][ks][i], wrow[i], wflip), fa[st][ks][j]);
-                else FragOps<MM>::mma(acc[i][j], FragOps<MM>::prep(fb[st][ks][i], wrow[i], wflip), fa[st][ks][j]);
-#endif
-                __builtin_amdgcn_sched_barrier(0);
-                static_for_up<NRT>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
-                    // reads are dealt over the first NMR MFMAs only: the last ones retire under the stage's remaining MFMAs, so the
-                    // lgkmcnt(0) in front of the next barrier does not wait for LDS latency
-                    if constexpr (mi < NMR && r >= (mi * NRT) / NMR && r < ((mi + 1) * NRT) / NMR) read_one(sA, sB, std::integral_constant<int, st ^ 1>{}, rc);
-                });
-                __builtin_amdgcn_sched_barrier(0);
-                static_for_up<PPW>([&](auto pc) {
-                    constexpr int pi = decltype(pc)::value;
-                    constexpr int after = ((pi + 1) * NM) / (PPW + 1) - 1 < 0 ? 0 : ((pi + 1) * NM) / (PPW + 1) - 1;
-                    if constexpr (after == mi) {
-#ifndef SDNQ_ABL_NODMA
-                        issue_range(js, slot, std::integral_constant<int, pi>{}, std::integral_constant<int, pi + 1>{});
-#endif
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                });
-            });
-        };
-        // prologue: stages 0 .. NS-2 are in flight (above); stage 0 landed -> the last free slot gets stage NS-1, stage 0 -> set 0
-        wait_ahead();
-        __builtin_amdgcn_s_barrier();
-        if (true) TRACE(2);
-        issue(AHEAD);
-        load_stage(0, std::integral_constant<int, 0>{});
-        auto half = [&](auto setc, int kt) {
-            constexpr int st = decltype(setc)::value;
-            // stage kt + 1 has landed (this wave's pieces; the barrier makes it everybody's), the NS - 2 younger stages stay in flight;
-            // this wave's reads of stage kt have retired, so after the barrier the slot of stage kt belongs to the DMA of stage kt + NS
-#ifndef SDNQ_ABL_NODMA
-            wait_ahead();
-#endif
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-#ifndef SDNQ_ABL_NOBAR
-            __builtin_amdgcn_s_barrier();
-#endif
-            __builtin_amdgcn_sched_barrier(0);
-            const int slot_free = slot_c;
-            slot_c = (slot_c + 1 == NS) ? 0 : slot_c + 1;
-            mma_issue(setc, kt + NS, slot_free, slot_c);  // (reads past the end of K: a re-fetched stage nobody multiplies)
-        };
-#pragma nounroll
-        for (int kt = 0; kt < nk; kt += 2) {
-            half(std::integral_constant<int, 0>{}, kt);
-            if (kt + 1 < nk) half(std::integral_constant<int, 1>{}, kt + 1);
-        }
-        if constexpr (SPLIT_ACC) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[0][0][e] += acc_odd[0][e];
-        }
     } else if constexpr (LD == LD_OG) {
-        // the overlapped ring for wave tiles of several MFMA tiles: fragments are read ONE K sub-step ahead (two register sets of TM + TN
-        // fragments instead of two whole stages: a 32x160 wave tile would need 192 fragment registers), everything else as LD_OV.  One loop
+        // the overlapped ring for wave tiles of several MFMA tiles: fragments are read ONE K sub-step ahead, into the other of two register
+        // sets of TM + TN fragments (a whole stage ahead, a 32x160 wave tile would need 192 fragment registers).  The reads and the DMA
+        // pieces are dealt out BETWEEN the MFMAs: a wave that issues all its reads in one burst after the barrier sits in the LDS issue
+        // queue behind the other seven waves' bursts and reaches its first MFMA only when nearly all of them have been served.  One loop
         // trip = {counted vmcnt, lgkmcnt(0), barrier} then the LAST sub-step of stage kt (its reads fetch sub-step 0 of stage kt + 1, which
         // the barrier just published) and sub-steps 0 .. KS-2 of stage kt + 1; the DMA pieces of stage kt + NS (ring slot of stage kt, free
         // since every wave's reads of it retired in front of the barrier) are dealt out over the trip's MFMAs.
@@ -1260,9 +1003,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
         fragb_t fb[2][TN];
         auto read_one = [&](const uint8_t* sA, const uint8_t* sB, auto setc, auto ksc, auto ec) {
             constexpr int st = decltype(setc)::value, ks = decltype(ksc)::value, e = decltype(ec)::value;
-#ifdef SDNQ_ABL_NOREAD
-            if (sA != nullptr) return;
-#endif
             if constexpr (e < TN) fb[st][e] = FragOps<MM>::template loadb<BKW>(sB, wn * WN + e * MS + frow, ks, fgrp, hk.swz);
             else fa[st][e - TN] = FragOps<MM>::template load<BK>(sA, wm * WM + (e - TN) * MS + frow, ks, fgrp, hk.swz);
         };
@@ -1275,9 +1015,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
             const uint8_t* sB = sA + BM * BK;
             static_for_up<NMG>([&](auto mc) {
                 constexpr int mi = decltype(mc)::value, i = mi / TM, j = mi % TM, gmi = G * NMG + mi;
-#ifndef SDNQ_ABL_NOMMA
                 FragOps<MM>::mma(acc[i][j], FragOps<MM>::prep(fb[SC][i], wrow[i], wflip), fa[SC][j]);
-#endif
                 if constexpr (FEED) {
                     __builtin_amdgcn_sched_barrier(0);
                     static_for_up<NRG>([&](auto ec) {
@@ -1290,9 +1028,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
                         constexpr int pi = decltype(pc)::value;
                         constexpr int after = ((pi + 1) * NMT) / (PPW + 1) - 1 < 0 ? 0 : ((pi + 1) * NMT) / (PPW + 1) - 1;
                         if constexpr (after == gmi) {
-#ifndef SDNQ_ABL_NODMA
                             issue_range(js, dslot, std::integral_constant<int, pi>{}, std::integral_constant<int, pi + 1>{});
-#endif
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     });
@@ -1309,14 +1045,10 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
         constexpr std::integral_constant<bool, true> feed{};
 #pragma nounroll
         for (int kt = -1; kt < nk - 1; ++kt) {
-#ifndef SDNQ_ABL_NODMA
             wait_ahead();  // stage kt + 1 has landed (this wave's pieces); NS - 2 younger stages stay in flight
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of stage kt have retired
             __builtin_amdgcn_sched_barrier(0);
-#ifndef SDNQ_ABL_NOBAR
             __builtin_amdgcn_s_barrier();
-#endif
             __builtin_amdgcn_sched_barrier(0);
             if (kt < 0) TRACE(2);
             const int rslot = slot_c;  // stage kt + 1
@@ -1767,9 +1499,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_kernel(const 
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
 #pragma unroll
-            for (int q = 0; q < (MS == 32 ? 4 : 1); ++q) {
-                // 4 consecutive channels: 32x32 tiles hold runs (reg & 3) + 8 (reg >> 2) + 4 fgrp, 16x16 tiles the one run 4 fgrp + reg
-                const int nl0 = wn * WN + i * MS + (MS == 32 ? 8 * q + 4 * fgrp : 4 * fgrp);
+            for (int q = 0; q < 4; ++q) {
+                // 4 consecutive channels: a 32x32 tile holds the runs (reg & 3) + 8 (reg >> 2) + 4 fgrp
+                const int nl0 = wn * WN + i * MS + (8 * q + 4 * fgrp);  // (the parentheses stay: summed left to right, 41 kernels come out with other listings)
                 float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -1998,31 +1730,11 @@ int launch_tiles(const GemmParams& p, hipStream_t s) {
     if (force == 2) return launch_one<MM, OUT_T, EPI, 64, 64, 32, 32, 4, LD_PIPE>(p, s);
     if (force == 3) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_PIPE, 64>(p, s);
     if constexpr (PP_OK<MM, OUT_T, EPI>) {
-        if (force == 4) return launch_one<MM, OUT_T, EPI, 256, 256, 128, 64, 4, LD_PP, 64>(p, s);
-        if (force == 5) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_PP, 64>(p, s);
-        if (force == 6) return launch_one<MM, OUT_T, EPI, 128, 256, 64, 64, 4, LD_PP, 64>(p, s);
-        if (force == 7) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 3, LD_PP, 128>(p, s);
-        if (force == 8) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 4, LD_PP, 64>(p, s);
-        if (force == 9) return launch_one<MM, OUT_T, EPI, 64, 128, 32, 32, 3, LD_PP, 128>(p, s);
-        if (force == 10) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 4, LD_PIPE, 64>(p, s);
-        if (force == 11) return launch_one<MM, OUT_T, EPI, 128, 256, 64, 64, 3, LD_PP, 64>(p, s);
-        if (force == 12) return launch_one<MM, OUT_T, EPI, 256, 160, 32, 160, 4, LD_PIPE, 64>(p, s);
-        if (force == 13) return launch_one<MM, OUT_T, EPI, 256, 160, 32, 160, 3, LD_PIPE, 64>(p, s);
-        if (force == 14) return launch_one<MM, OUT_T, EPI, 128, 320, 32, 160, 3, LD_PIPE, 64>(p, s);
-        if (force == 15) return launch_one<MM, OUT_T, EPI, 256, 160, 32, 160, 4, LD_DMA, 64>(p, s);
-        if (force == 16) return launch_one<MM, OUT_T, EPI, 128, 320, 32, 160, 4, LD_PIPE, 64>(p, s);
         if (force == 17) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 3, LD_PIPE, 128>(p, s);
-        if (force == 18) return launch_one<MM, OUT_T, EPI, 256, 256, 128, 64, 4, LD_8P, 64>(p, s);
         if (force == 19) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_8P, 128>(p, s);
         if (force == 20 && (p.K % 128) == 0 && ht_ok(p)) return launch_one<MM, OUT_T, EPI, 256, 256, 128, 64, 2, LD_HT, 128>(p, s);
         if (force == 20) return launch_one<MM, OUT_T, EPI, 256, 256, 128, 64, 4, LD_PIPE, 64>(p, s);
-        if (force == 21) return launch_one<MM, OUT_T, EPI, 64, 128, 32, 32, 3, LD_OV, 128>(p, s);
-        if (force == 22) return launch_one<MM, OUT_T, EPI, 64, 128, 32, 32, 4, LD_OV, 128>(p, s);
-        if (force == 23) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 3, LD_OV, 128>(p, s);
-        if (force == 24) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_OV, 128>(p, s);
         if (force == 25) return launch_one<MM, OUT_T, EPI, 256, 160, 32, 160, 3, LD_OG, 128>(p, s);
-        if (force == 26) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 3, LD_OG, 128>(p, s);
-        if (force == 27) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_OG, 128>(p, s);
         // 28: 64x80 tiles, eight waves in two K groups that share one 8-deep ring, int32 partial sums reduced through LDS (gemm_ks.hip, round 6);
         //     problems it does not take (fp8, grouped / linked / conv outputs, K tails) fall through to the heuristics
         if constexpr (MM == SDNQ_MM_I8) {
@@ -2030,19 +1742,6 @@ int launch_tiles(const GemmParams& p, hipStream_t s) {
             if (force == 28 && ks_ok(p))
                 return sdnq_internal_scaled_mm_ks(p.a, p.b, p.sa, p.sb, EPI == EPI_BIAS1D ? p.bias : nullptr, p.bias_dtype, p.out, OUT_T, p.M, p.N, p.K, p.lda, p.ldb, p.ldc, s);
         }
-        // (round 5, measured and NOT instantiated: 64x80 tiles on v_mfma_i32_16x16x64_i8 -- four waves of 16x80, 256 workgroups for 1024 x 1280
-        //  outputs, 25 % fewer LDS-fill bytes per CU -- on LD_DMA and on LD_OV, 3 / 4 ring slots: replayed alone 7.67-8.09 us against 7.09 at
-        //  K = 1280, in the step +0.36..+0.53 ms over the 180 launches of 1024 x 1280 x 1280, +0.11..+0.21 at K = 5120; profiles/r05_overlapped_ring_lab.txt)
-        // (round 4 lab, not instantiated: 128x160 tiles -- N = 320 in two exact columns, 256 tiles at M = 16384 -- equal the 64x128 tile on
-        //  the conv step, 64x320 tiles are slower; profiles/r04_conv_tiles_in_step.txt)
-        // (round 4, profiles/r04_ring_depth_in_step.txt: 5- and 6-deep rings for the 64x128 tile -- the one-workgroup-per-CU problems of the
-        //  SDXL step, 160 tiles on 256 CUs -- judged on the step: 1024 x 1280 x 1280 +0.11 / +0.13 ms, 4096 x 640 x 640 +0.15 / +0.16 ms,
-        //  1024 x 1280 x 5120 +-0.00: more bytes in flight did not shorten that loop -- its 720 cycles per stage are the SUM of DMA issue,
-        //  fragment reads and MFMAs of a lock-step stage (round 5, DESIGN.md section 6: the fill path alone sustains 47 B/clk/CU), not a service
-        //  rate -- and the deeper prologue only delays the first MFMA.  Not instantiated in the library.)
-        // (64x80 tiles on v_mfma_i32_16x16x64_i8 -- MM_I8_16, instantiated by tools/micro/gemm_lab.hip only -- cut 1024 x 1280 outputs
-        //  into exactly 256 workgroups with 25 % fewer LDS-fill bytes per CU, and measured SLOWER than 160 tiles of 64x128: 9.5 vs 7.9 us
-        //  at K = 1280, 23.5 vs 19.0 us at K = 5120: four waves of 16x80 read six fragments per five 16-cycle MFMAs)
     }
     // measured on MI355X (tools/bench_gemm.py, profiles/r01_gemm_tile_sweep.txt). Every kernel launch starts with cold
     // L2s (data comes from MALL/HBM at ~2 us loaded latency) and the L2->LDS fill rate per CU is ~30 B/clk, so:
@@ -2125,8 +1824,16 @@ int launch_tiles(const GemmParams& p, hipStream_t s) {
 inline bool force_tile_unfit(const GemmParams& p) {
     const int force = forced_tile_for(p);
     if (force < 0 || p.units == nullptr) return false;
-    static const int bn_of[] = {256, 128, 64, 128, 256, 128, 256, 128, 128, 128, 128, 256, 160, 160, 320, 160, 320, 128, 256, 128, 256, 128, 128, 128, 128, 160, 128, 128, 128};  // (28 falls back to the heuristics on grouped launches)
-    return force < (int)(sizeof(bn_of) / sizeof(int)) ? (p.unit_n % bn_of[force]) != 0 : false;
+    int bn;  // BN of the form launch_tiles runs for `force`
+    switch (force) {
+        case 0: case 20: bn = 256; break;
+        case 1: case 3: case 17: case 19: bn = 128; break;
+        case 2: bn = 64; break;
+        case 25: bn = 160; break;
+        case 28: bn = 128; break;  // (falls back to the heuristics on grouped launches; refused as before where 128 does not divide the unit)
+        default: return false;     // any other id: the heuristics decide, and they only pick tiles that fit
+    }
+    return (p.unit_n % bn) != 0;
 }
 
 template <int MM, int EPI>
@@ -2369,7 +2076,7 @@ int launch_tiles_w8(const GemmParams& p, hipStream_t s) {
     const bool fit128 = p.units == nullptr || (p.unit_n % 128) == 0;
     if (force == 0 && fit128) return launch_one<MM, OUT_T, EPI, 256, 128, 64, 64, 3, LD_PIPE, 128>(p, s);
     if (force == 2 && fit128) return launch_one<MM, OUT_T, EPI, 128, 128, 64, 32, 3, LD_PIPE, 128>(p, s);
-    // (round 5: the overlapped ring LD_OV on this kernel's 64x128 tile -- DMA issue and the next stage's fragment reads dealt out between
+    // (round 5: an overlapped ring on this kernel's 64x128 tile -- DMA issue and the next stage's fragment reads dealt out between
     //  the MFMAs and conversions, 3 / 4 ring slots -- compiled, bit-identical, and judged on the step: -0.09 ... +0.11 ms per problem, all
     //  problems together +0.03 / +0.11 ms of 12.67 (profiles/r05_fused_rowquant_gemm.txt item 9); not instantiated)
     if (force == 3 || (force < 0 && p.M <= 64) || !fit128) return launch_one<MM, OUT_T, EPI, 64, 64, 64, 32, 4, LD_DMA, 128>(p, s);

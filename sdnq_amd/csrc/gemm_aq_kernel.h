@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NT) void linear_aq_kernel(const uint16_t* __restric
             }
         });
     } else {
-        // Software pipeline one STAGE deep (the LD_OV form of gemm.hip, profiles/r05_overlapped_ring_lab.txt): the fragments of stage kt sit in
+        // Software pipeline one STAGE deep (the whole-stage overlapped ring of profiles/r05_overlapped_ring_lab.txt): the fragments of stage kt sit in
         // registers when its barrier falls, so the MFMAs start at once; dealt out between them are the fragment reads of stage kt + 1 (which that
         // barrier published) and the DMA pieces of stage kt + NSB into the slot stage kt has just vacated -- NSB - 1 stages in flight behind the
         // landed one.  Two register sets, so the loop is unrolled by two.

@@ -95,8 +95,8 @@ def test_failed_unit_raises_with_its_name_and_stderr(tmp_path, monkeypatch):
 
 def test_runs_as_a_script_without_torch():
     code = ("import sys; sys.path.insert(0, 'sdnq_amd'); import _build; "
-            "cmds = _build.build(force=True, dry_run=True, defines=['SDNQ_LAB_LUT4']); "
-            "assert 'torch' not in sys.modules and all('-DSDNQ_LAB_LUT4' in c for c in cmds if '-c' in c)")
+            "cmds = _build.build(force=True, dry_run=True, defines=['SDNQ_TRACE']); "
+            "assert 'torch' not in sys.modules and all('-DSDNQ_TRACE' in c for c in cmds if '-c' in c)")
     subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT)
     r = subprocess.run([sys.executable, os.path.join("sdnq_amd", "_build.py"), "--dry-run", "--force", "--out", "build/x.so"],
                        capture_output=True, text=True, cwd=ROOT)

@@ -336,6 +336,35 @@ def test_scaled_mm_tile_is_a_dry_run_of_the_shape_rules():
     assert lib.sdnq_hip_scaled_mm_tile(0, 1, 0, 1024, 1280, 1280, None, None, None, None) == 0  # every output pointer is optional
 
 
+def test_tile_override_ids_name_their_forms_and_retired_ids_run_the_heuristics():
+    """sdnq_hip_set_tile_override on int8 / bf16 / bias at 1024 x 1280 x 1280: each id launch_tiles knows reports its own form, and every
+    other id -- the twenty retired ones and the first unassigned one -- reports exactly what the heuristics report, so a test that
+    forces a retired id cannot pass for a form that no longer exists.  Id 28 is the K-split tile here: sdnq_internal_ks_eligible holds
+    (K = 1280 is a whole number of 128-byte stages, one plain output, 32-bit tile offsets)."""
+    import ctypes
+    lib = _lib.load()
+
+    def tile():
+        bm, bn, thr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        assert lib.sdnq_hip_scaled_mm_tile(0, 1, 1, 1024, 1280, 1280, ctypes.byref(bm), ctypes.byref(bn), ctypes.byref(thr), None) == 0
+        return bm.value, bn.value, thr.value
+    live = {0: (256, 256, 512), 1: (64, 128, 512), 2: (64, 64, 256), 3: (256, 128, 512), 17: (128, 128, 512), 19: (256, 128, 512),
+            20: (256, 256, 512), 25: (256, 160, 512), 28: (64, 80, 512)}
+    retired = [t for t in range(4, 28) if t not in live]
+    assert len(retired) == 20
+    try:
+        lib.sdnq_hip_set_tile_override(-1)
+        heuristics = tile()
+        for t, form in live.items():
+            lib.sdnq_hip_set_tile_override(t)
+            assert tile() == form, (t, tile(), form)
+        for t in retired + [29]:
+            lib.sdnq_hip_set_tile_override(t)
+            assert tile() == heuristics, (t, tile(), heuristics)
+    finally:
+        lib.sdnq_hip_set_tile_override(-1)
+
+
 def test_every_export_has_declared_argument_types():
     """ctypes converts an undeclared Python int to a 32-bit C int: a device pointer or an int64 size would be truncated silently (round 6:
     a new entry point without argtypes sent truncated pointers to the GPU).  Every export must carry argtypes, as many as its prototype

@@ -1,6 +1,6 @@
 """GPU parity of the scaled-matmul tile configurations and of the grouped (unit-table) launch.
 
-Every configuration of sdnq_amd/csrc/gemm.hip:launch_tiles -- including the ping-pong (LD_PP) schedules -- must give the bits
+Every configuration of sdnq_amd/csrc/gemm.hip:launch_tiles -- including the ping-pong (LD_8P, LD_HT) schedules -- must give the bits
 the CPU oracle gives (int8: exact integer accumulation, so the schedule cannot change a bit), on ragged shapes that exercise
 the M / N / K tails, and the grouped launch must equal one sdnq_hip_scaled_mm per layer.
 """
@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from sdnq_amd import _lib, ops  # noqa: E402
 
-TILES = list(range(29))
+TILES = [0, 1, 2, 3, 17, 19, 20, 25, 28]  # the ids launch_tiles knows; any other id runs the heuristics
 
 
 @pytest.fixture()
@@ -69,7 +69,7 @@ def test_every_tile_configuration_repeatable_at_model_size(tile, gpu_device, til
             assert torch.equal(out.view(torch.int16), ref.view(torch.int16)), (tile, (m, n, k))
 
 
-@pytest.mark.parametrize("tile", [0, 4, 6, 7])
+@pytest.mark.parametrize("tile", [0, 17, 19])  # one 64-byte-stage form, two 128-byte-stage forms
 def test_fp8_tile_configurations_match_default(tile, gpu_device, tile_override):
     m, n, k = 520, 1288, 1344
     g = torch.Generator().manual_seed(5 + tile)

@@ -13,7 +13,7 @@ from sdnq_amd import _lib, ops  # noqa: E402
 dev = torch.device("cuda:0")
 lib = _lib.load()
 shapes = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:] if "x" in a] or [(1024, 1280, 1280), (1024, 1280, 5120), (1024, 1280, 640), (1024, 1280, 2560), (1000, 1200, 1152)]
-TILES = [int(v) for v in os.environ.get("KS_TILES", "1,21,28").split(",")]
+TILES = [int(v) for v in os.environ.get("KS_TILES", "1,28").split(",")]
 ks_trace = getattr(ctypes.CDLL(_lib.LIB_PATH), "_Z22sdnq_internal_ks_tracePy")
 ks_trace.argtypes = [ctypes.c_void_p]
 ks_trace.restype = None

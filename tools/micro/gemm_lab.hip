@@ -2,7 +2,7 @@
 // handful of tile configurations only (seconds to compile instead of the library's two minutes), runs them on a list of shapes,
 // checks every configuration's output against the first one bit for bit and times back-to-back launches with HIP events.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DLAB_...] tools/micro/gemm_lab.hip -o build/gemm_lab
-//   build/gemm_lab "1024,10240,1280;1024,1280,5120" 1,12,13
+//   build/gemm_lab "1024,10240,1280;1024,1280,5120" 1,24,31
 #define SDNQ_LAB 1
 #include "../../sdnq_amd/csrc/gemm.hip"
 
@@ -21,12 +21,7 @@ static int run_cfg(int id, GemmParams p, hipStream_t s) {
         case 1: return launch_one<MM, OT, EP, 64, 128, 32, 32, 3, LD_DMA>(p, s);
         case 2: return launch_one<MM, OT, EP, 64, 64, 32, 32, 4, LD_PIPE>(p, s);
         case 3: return launch_one<MM, OT, EP, 256, 128, 64, 64, 3, LD_PIPE, 64>(p, s);
-        case 10: return launch_one<MM, OT, EP, 128, 128, 64, 32, 4, LD_PIPE, 64>(p, s);
-        case 13: return launch_one<MM, OT, EP, 256, 160, 32, 160, 3, LD_PIPE, 64>(p, s);
-        case 18: return launch_one<MM_I8_16, OT, EP, 64, 80, 16, 80, 3, LD_DMA, 128>(p, s);
-        case 19: return launch_one<MM_I8_16, OT, EP, 64, 80, 16, 80, 4, LD_DMA, 128>(p, s);
         case 24: return launch_one<MM, OT, EP, 128, 128, 64, 32, 3, LD_PIPE, 128>(p, s);
-        case 30: return launch_one<MM, OT, EP, 256, 256, 128, 64, 4, LD_8P, 64>(p, s);
         case 31: return launch_one<MM, OT, EP, 256, 128, 64, 64, 3, LD_8P, 128>(p, s);
         case 32: return launch_one<MM, OT, EP, 256, 256, 128, 64, 2, LD_HT, 128>(p, s);
 #ifdef LAB_EXTRA
@@ -75,7 +70,7 @@ int main(int argc, char** argv) {
             shapes.push_back({m, n, k});
             pos = e + 1;
         }
-        std::string il = argc > 2 ? argv[2] : "1,13";
+        std::string il = argc > 2 ? argv[2] : "1,24";
         pos = 0;
         while (pos < il.size()) {
             size_t e = il.find(',', pos);
@@ -138,20 +133,6 @@ int main(int argc, char** argv) {
             float ms;
             HC(hipEventElapsedTime(&ms, e0, e1));
             printf("  %d:%7.2f us%s", id, ms * 1e3 / reps, same ? "" : " MISMATCH");
-#ifdef SDNQ_TRACE2
-            if (id == 32) {
-                unsigned h[64];
-                HC(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_trace2), sizeof(h)));
-                const double nk = (double)((k + 127) / 128);
-                printf("\n   cycles per phase (issue | vmcnt | barrier1+lgkm | mfma | barrier2), per K tile average:\n");
-                for (int g = 0; g < 2; ++g)
-                    for (int q = 0; q < 4; ++q) {
-                        printf("   group %d phase %d:", g, q);
-                        for (int e = 0; e < 5; ++e) printf(" %7.1f", h[g * 20 + q * 5 + e] / nk);
-                        printf("\n");
-                    }
-            }
-#endif
         }
         printf("\n");
         hipFree(a); hipFree(b); hipFree(sa); hipFree(sb); hipFree(bias); hipFree(out); hipFree(ref);

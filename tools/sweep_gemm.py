@@ -14,7 +14,7 @@ from sdnq_amd import _lib, ops  # noqa: E402
 dev = torch.device("cuda:0")
 mm = ops.MM_FP8 if (len(sys.argv) > 1 and sys.argv[1] == "fp8") else ops.MM_I8
 which = sys.argv[2] if len(sys.argv) > 2 else "sdxl"
-ids = [int(v) for v in sys.argv[3].split("=")[1].split(",")] if len(sys.argv) > 3 else list(range(17))
+ids = [int(v) for v in sys.argv[3].split("=")[1].split(",")] if len(sys.argv) > 3 else [0, 1, 2, 3, 17, 19, 20, 25, 28]
 SDXL = [(4096, 640, 640), (4096, 1920, 640), (4096, 5120, 640), (4096, 640, 2560), (1024, 1280, 1280), (1024, 3840, 1280),
         (1024, 10240, 1280), (1024, 1280, 5120), (77, 1280, 2048)]
 BIG = [(8192, 8192, 8192), (16384, 8192, 4096)]

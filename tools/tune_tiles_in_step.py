@@ -11,12 +11,12 @@ SHAPES = {"sdxl_int8": [(4096, 640, 640), (4096, 1920, 640), (4096, 5120, 640), 
 SHAPES["sdxl_int8_dequant"] = [(m, n, 2 * k) for (m, n, k) in SHAPES["sdxl_int8"]]  # the fused dequantize GEMM counts K in bytes of the 16-bit rows
 SHAPES["flux_int4_had"] = [(4608, 3072, 3072), (4608, 3072, 12288), (4608, 3072, 15360), (512, 3072, 3072), (512, 3072, 12288)]
 SHAPES = SHAPES.get(workload, [])
-CANDS = {"sdxl_int8": [1, 3, 7, 9, 10, 13, 17, 19], "flux_int4_had": [1, 3, 19, 20]}.get(workload, [1, 2, 3, 4])  # launch_tiles / launch_tiles_w8 ids
+CANDS = {"sdxl_int8": [1, 3, 17, 19], "flux_int4_had": [1, 3, 19, 20]}.get(workload, [1, 2, 3, 4])  # launch_tiles / launch_tiles_w8 ids
 
 
 if os.environ.get("TUNE_SHAPES"):  # "MxNxK,MxNxK": only these problems
     SHAPES = [tuple(int(v) for v in t.split("x")) for t in os.environ["TUNE_SHAPES"].split(",")]
-if os.environ.get("TUNE_CANDS"):   # "1,21,22": only these tile ids
+if os.environ.get("TUNE_CANDS"):   # "1,17,25": only these tile ids
     CANDS = [int(v) for v in os.environ["TUNE_CANDS"].split(",")]
 
 
