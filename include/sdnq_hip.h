@@ -732,6 +732,21 @@ int sdnq_hip_attn(const void* q, const void* k, const void* v, int dtype, int64_
                   int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* out, int out_dtype,
                   const int64_t* out_strides, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
 
+/* sdnq_hip_attn_wide: sdnq_hip_attn for head dims 136 <= head_dim <= 256, head_dim % 8 == 0 (sdnq_attn_kernel triton_atten.py:143-335 on the
+ * operands of quantize_attn :443-487; get_attn_inputs :512-519 pads such a head to the next power of two, here it is padded to the next
+ * multiple of 32, which gives the same scores: the extra channels are zeros).  Same arguments, strides, mask conventions and output layout
+ * as sdnq_hip_attn; hadamard_group must be 0 (SDNQ_ERR_UNSUPPORTED otherwise, as for any other head_dim).  Always a prepare pass (Q, K, V;
+ * two launches when smooth_k meets more than 256 keys) and one forward launch in which a pair of waves owns 32 queries and splits the output
+ * channels.  workspace: sdnq_hip_attn_wide_workspace_bytes(...) bytes (< 0: SdnqStatus), 256-byte aligned, never NULL.
+ * sdnq_hip_attn and its workspace query keep their answer for head_dim > 128. */
+int64_t sdnq_hip_attn_wide_workspace_bytes(int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len, int64_t head_dim,
+                                           int hadamard_group);
+int sdnq_hip_attn_wide(const void* q, const void* k, const void* v, int dtype, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len,
+                       int64_t kv_len, int64_t head_dim, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                       int smooth_k, int hadamard_group, float sm_scale, int is_causal, const void* mask, int mask_dtype,
+                       int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* out, int out_dtype,
+                       const int64_t* out_strides, void* workspace, int64_t workspace_bytes, sdnq_stream_t stream);
+
 /* Quantized attention backward (the default configuration: int8 Q.K^T, P.V in the value dtype) on the operands of sdnq_hip_attn_prepare
  * with Q quantized (qq / qs), K in fragment order (kq / ks).
  * sdnq_hip_attn_lse <- the save_lse tail of sdnq_attn_kernel (triton_atten.py:328-334): lse [batch][q_heads][q_len] of lse_dtype (the

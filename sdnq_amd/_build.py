@@ -66,6 +66,9 @@ UNITS = (
     ("attention", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_var", "-mllvm -amdgpu-mfma-vgpr-form", None),
     ("attention_bwd", "", None),
+    # attention_wide.hip (head dims 136 .. 256): accumulators in VGPRs as above; its fp32 vector arithmetic compiles to single
+    # instructions, not to the packed-fp32 forms
+    ("attention_wide", "-mllvm -amdgpu-mfma-vgpr-form -Xclang -target-feature -Xclang -packed-fp32-ops", None),
     ("colquant", "", None),
     ("optim", "", None),
     ("parallel", "", None),

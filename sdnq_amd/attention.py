@@ -4,7 +4,8 @@ Host-side mirror of the reference's ``sdnq_triton_atten`` (kernels/triton_atten.
 defaults.  Built: the default configuration -- int8 Q.K^T (``matmul_dtype="int8"``), P.V in the value dtype
 (``pv_matmul_dtype=None``), ``smooth_k``, optional ``use_hadamard``, ``is_causal`` and ``attn_mask`` (bool or additive), grouped-query heads -- on its
 tuned kernels, and (round 6) the other matmul formats -- fp8 (e4m3) Q.K^T, P.V on int8 / fp8 / float16 codes with P quantized per (query,
-32-key block) -- on a plain kernel of their own (``sdnq_hip_attn_prepare_ex`` / ``sdnq_hip_attn_fwd_ex``).  Reference-valid options that are not
+32-key block) -- on a plain kernel of their own (``sdnq_hip_attn_prepare_ex`` / ``sdnq_hip_attn_fwd_ex``).  Head dims 136 .. 256 run the default
+configuration (no rotation) on ``sdnq_hip_attn_wide`` (csrc/attention_wide.hip).  Reference-valid options that are not
 built raise ``NotImplementedError`` naming the gap (fp16 accumulation -- an RDNA work-around --, the backward outputs).
 """
 from __future__ import annotations
@@ -213,6 +214,41 @@ def atten_fwd(qq, qs, kq, ks, vt, kn: int, sm_scale: float, is_causal: bool, out
     return out
 
 
+def _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, use_hadamard, mm, pv, matmul_dtype, pv_matmul_dtype, out_dtype):
+    """``sdnq_hip_atten`` for head dims 136 .. 256 (``sdnq_hip_attn_wide``: a prepare pass into a workspace and one forward launch).  The
+    reference pads such a head to 256 (triton_atten.py:514-519); the kernels pad it to the next multiple of 32, which gives the same scores."""
+    d = query.shape[-1]
+    if use_hadamard:
+        raise NotImplementedError(f"use_hadamard=True with head_dim {d} > 128 is not built (the reference rotates over the padded 256-wide head)")
+    if mm != "int8":
+        raise NotImplementedError(f"matmul_dtype={matmul_dtype!r} with head_dim {d} > 128 is not built (int8 Q.K^T is)")
+    if pv is not None:
+        raise NotImplementedError(f"pv_matmul_dtype={pv_matmul_dtype!r} with head_dim {d} > 128 is not built (P.V in the value dtype is)")
+    if not query.is_cuda or not key.is_cuda or not value.is_cuda or (attn_mask is not None and not attn_mask.is_cuda):
+        raise _lib.SdnqHipError("sdnq_amd attention needs CUDA/HIP tensors (no CPU fallback)")
+    z, qh, qn, _ = query.shape
+    kh, kn = key.shape[1], key.shape[2]
+    if attn_mask is not None:
+        attn_mask = prepare_mask(attn_mask, qn, kn)
+    token_major = qh > 1 and qn > 1 and query.stride(2) > query.stride(1) and query.stride(-1) == 1  # as sdnq_hip_atten: the query's layout
+    query, key, value = _rows16(query), _rows16(key), _rows16(value)
+    lib = _lib.load()
+    nbytes = lib.sdnq_hip_attn_wide_workspace_bytes(z, qh, kh, qn, kn, d, 0)
+    if nbytes < 0:
+        ops.check(int(nbytes), "attn_wide_workspace_bytes")
+    ws = torch.empty((nbytes,), device=query.device, dtype=torch.uint8)
+    if token_major:
+        out = torch.empty((z, qn, qh, d), device=query.device, dtype=out_dtype).transpose(1, 2)
+    else:
+        out = torch.empty((z, qh, qn, d), device=query.device, dtype=out_dtype)
+    mptr, mdt, ms = _mask_args(attn_mask)
+    ops.check(lib.sdnq_hip_attn_wide(query.data_ptr(), key.data_ptr(), value.data_ptr(), ops.float_code(query.dtype), z, qh, kh, qn, kn, d,
+                                     _strides(query), _strides(key), _strides(value), 1 if smooth_k else 0, 0, float(sm_scale),
+                                     1 if is_causal else 0, mptr, mdt, *ms, out.data_ptr(), ops.float_code(out_dtype), _strides(out),
+                                     ws.data_ptr(), nbytes, ops._stream(query)), "attn_wide")
+    return out
+
+
 @torch.no_grad()
 def sdnq_hip_atten(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask: torch.Tensor | None = None,
                    dropout_p: float = 0.0, is_causal: bool = False, scale: float | None = None, enable_gqa: bool = False,
@@ -230,13 +266,15 @@ def sdnq_hip_atten(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, 
     if query.ndim != 4 or key.ndim != 4 or value.ndim != 4:
         raise ValueError("query / key / value must be [batch, heads, tokens, head_dim]")
     d = query.shape[-1]
-    if key.shape[-1] != d or value.shape[-1] != d or d % 8 or not 8 <= d <= 128:
-        raise NotImplementedError("query, key and value must share a head_dim that is a multiple of 8 and at most 128")
+    if key.shape[-1] != d or value.shape[-1] != d or d % 8 or not 8 <= d <= 256:
+        raise NotImplementedError("query, key and value must share a head_dim that is a multiple of 8 and at most 256")
     if query.dtype not in (torch.bfloat16, torch.float16) or key.dtype != query.dtype or value.dtype != query.dtype:
         raise NotImplementedError("query / key / value must share one of bfloat16 / float16")
     if out_dtype is None:
         out_dtype = query.dtype
     sm_scale = d ** -0.5 if scale is None else scale  # triton_atten.py:512-513
+    if d > 128:  # head dims 136 .. 256: the kernels of csrc/attention_wide.hip (the default formats, no rotation)
+        return _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, use_hadamard, mm, pv, matmul_dtype, pv_matmul_dtype, out_dtype)
     group = 0
     if use_hadamard:  # triton_atten.py:563-569: group from the (power-of-two) head dim, halved until it divides
         from .quant_utils import get_hadamard_group_size

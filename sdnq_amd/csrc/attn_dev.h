@@ -119,9 +119,10 @@ __device__ __forceinline__ float attn_row_amax(const float (&v)[8], int lpr) {
     if (lpr == 16) amax = fmaxf(amax, lane_xor(amax, 8));
     return amax;
 }
-// per-token symmetric int8: codes of this lane's 8 channels, the row's scale
-__device__ __forceinline__ float attn_quant8(const float (&v)[8], int lpr, u32 (&o)[2]) {
-    const float scale = attn_row_amax(v, lpr) / 127.0f;
+// per-token symmetric int8: codes of this lane's 8 channels from the row's maximum |v| (a row spread over more than 16 lanes finishes the
+// maximum itself: attention_wide.hip), the row's scale
+__device__ __forceinline__ float attn_quant8_amax(const float (&v)[8], float amax, u32 (&o)[2]) {
+    const float scale = amax / 127.0f;
     RowDiv rd;  // the correctly rounded 3-instruction division (sdnq_dev.h) when every row of the wave has an ordinary scale
     rd.set(scale);
     if (__all(rd.fast)) {
@@ -141,6 +142,7 @@ __device__ __forceinline__ float attn_quant8(const float (&v)[8], int lpr, u32 (
     }
     return scale;
 }
+__device__ __forceinline__ float attn_quant8(const float (&v)[8], int lpr, u32 (&o)[2]) { return attn_quant8_amax(v, attn_row_amax(v, lpr), o); }
 
 // ---- V [heads][kn][d] -> P.V operand in MFMA-fragment order (layout above; knp = kn rounded up to 32, zero padded) ---------------------
 template <int PITCH>
