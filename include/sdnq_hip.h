@@ -768,6 +768,26 @@ int sdnq_hip_attn_bwd(const void* qq, const float* qs, const void* kq, const flo
                       void* dv, const int64_t* dv_strides, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len,
                       int64_t kv_len, int64_t head_dim, sdnq_stream_t stream);
 
+/* The same two passes for head dims 136 <= head_dim <= 256 (head_dim % 8 == 0), on the operands that sdnq_hip_attn_wide's prepare pass left in its
+ * workspace: `workspace` is that call's workspace (256-byte aligned), or a copy of its first bytes -- the Q codes, Q scales, K codes and K
+ * scales come first in its layout and are all that is read, so workspace_bytes may be anything from their end up to
+ * sdnq_hip_attn_wide_workspace_bytes(...); a shorter one: SDNQ_ERR_SHAPE.  Every other argument, the statuses and the results' layouts are
+ * those of sdnq_hip_attn_lse / sdnq_hip_attn_bwd (dq_channels / dk_channels: head_dim, or head_dim rounded up to 32).  The arithmetic and the
+ * order of every floating-point sum are theirs too: on operands that are zero above channel 128 the results equal theirs bit for bit.
+ * sdnq_hip_attn_wide_bwd launches delta, dq (a pair of waves per 32 queries, each half of the channel tiles) and dk + dv (two waves per 32
+ * keys: one accumulates dk, the other dv); deterministic, no atomics.  sdnq_hip_attn_lse and sdnq_hip_attn_bwd keep their answer
+ * (SDNQ_ERR_UNSUPPORTED) for head_dim > 128. */
+int sdnq_hip_attn_wide_lse(const void* workspace, int64_t workspace_bytes, float sm_scale, int is_causal, const void* mask, int mask_dtype,
+                           int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* lse, int lse_dtype, int64_t batch,
+                           int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len, int64_t head_dim, sdnq_stream_t stream);
+int sdnq_hip_attn_wide_bwd(const void* workspace, int64_t workspace_bytes, const void* v, const int64_t* v_strides, int v_dtype, const void* out,
+                           const int64_t* out_strides, const void* grad, const int64_t* grad_strides, int grad_dtype, const void* grad_v,
+                           const int64_t* grad_v_strides, const void* lse, float sm_scale, int is_causal, const void* mask, int mask_dtype,
+                           int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, float* delta, void* dq,
+                           const int64_t* dq_strides, int64_t dq_channels, void* dk, const int64_t* dk_strides, int64_t dk_channels, void* dv,
+                           const int64_t* dv_strides, int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len,
+                           int64_t head_dim, sdnq_stream_t stream);
+
 /* ---- training Linear: column-wise int8 quantization with transposed codes ---------------------------------------------------------
  * replaces quantize_int_mm(.., dim=0) (quant_utils.py:265-273) as the int8 training matmuls call it: on the weight of grad_input and on
  * the flattened input of grad_weight (training/layers/linear/linear_int8/linear_int8_dynamic.py:27-28, linear_int8_dynamic_ckpt.py:22-26),

@@ -69,6 +69,9 @@ UNITS = (
     # attention_wide.hip (head dims 136 .. 256): accumulators in VGPRs as above; its fp32 vector arithmetic compiles to single
     # instructions, not to the packed-fp32 forms
     ("attention_wide", "-mllvm -amdgpu-mfma-vgpr-form -Xclang -target-feature -Xclang -packed-fp32-ops", None),
+    # attention_wide_bwd.hip (the backward for head dims 136 .. 256): no packed-fp32 forms either; its accumulators are left to the
+    # register allocator (the dK wave updates them on the VALU, the dV wave on the matrix pipe)
+    ("attention_wide_bwd", "-Xclang -target-feature -Xclang -packed-fp32-ops", None),
     ("colquant", "", None),
     ("optim", "", None),
     ("parallel", "", None),

@@ -5,7 +5,8 @@ defaults.  Built: the default configuration -- int8 Q.K^T (``matmul_dtype="int8"
 (``pv_matmul_dtype=None``), ``smooth_k``, optional ``use_hadamard``, ``is_causal`` and ``attn_mask`` (bool or additive), grouped-query heads -- on its
 tuned kernels, and (round 6) the other matmul formats -- fp8 (e4m3) Q.K^T, P.V on int8 / fp8 / float16 codes with P quantized per (query,
 32-key block) -- on a plain kernel of their own (``sdnq_hip_attn_prepare_ex`` / ``sdnq_hip_attn_fwd_ex``).  Head dims 136 .. 256 run the default
-configuration (no rotation) on ``sdnq_hip_attn_wide`` (csrc/attention_wide.hip).  Reference-valid options that are not
+configuration (no rotation) on ``sdnq_hip_attn_wide`` (csrc/attention_wide.hip), with a backward on ``sdnq_hip_attn_wide_bwd``
+(csrc/attention_wide_bwd.hip).  Reference-valid options that are not
 built raise ``NotImplementedError`` naming the gap (fp16 accumulation -- an RDNA work-around --, the backward outputs).
 """
 from __future__ import annotations
@@ -214,9 +215,11 @@ def atten_fwd(qq, qs, kq, ks, vt, kn: int, sm_scale: float, is_causal: bool, out
     return out
 
 
-def _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, use_hadamard, mm, pv, matmul_dtype, pv_matmul_dtype, out_dtype):
+def _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, use_hadamard, mm, pv, matmul_dtype, pv_matmul_dtype, out_dtype,
+                with_workspace: bool = False):
     """``sdnq_hip_atten`` for head dims 136 .. 256 (``sdnq_hip_attn_wide``: a prepare pass into a workspace and one forward launch).  The
-    reference pads such a head to 256 (triton_atten.py:514-519); the kernels pad it to the next multiple of 32, which gives the same scores."""
+    reference pads such a head to 256 (triton_atten.py:514-519); the kernels pad it to the next multiple of 32, which gives the same scores.
+    ``with_workspace``: (out, workspace) -- the workspace holds the quantized operands the backward reads (``wide_operands``)."""
     d = query.shape[-1]
     if use_hadamard:
         raise NotImplementedError(f"use_hadamard=True with head_dim {d} > 128 is not built (the reference rotates over the padded 256-wide head)")
@@ -246,7 +249,7 @@ def _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, use
                                      _strides(query), _strides(key), _strides(value), 1 if smooth_k else 0, 0, float(sm_scale),
                                      1 if is_causal else 0, mptr, mdt, *ms, out.data_ptr(), ops.float_code(out_dtype), _strides(out),
                                      ws.data_ptr(), nbytes, ops._stream(query)), "attn_wide")
-    return out
+    return (out, ws) if with_workspace else out
 
 
 @torch.no_grad()
@@ -386,6 +389,97 @@ def atten_bwd(grad: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, qq, qs, 
     return dq, dk, dv
 
 
+# ---- backward for head dims 136 .. 256 (csrc/attention_wide_bwd.hip) on the workspace of ``sdnq_hip_attn_wide`` ---------------------------
+def wide_operands(ws: torch.Tensor, z: int, qh: int, kh: int, qn: int, kn: int, d: int):
+    """(q_q int8 [Z,QH,QN,DP], q_scale f32 [Z,QH,QN], k_q int8 [Z,KH,KNp/32,DP/32,64,16], k_scale f32 [Z,KH,KNp]) as views of the workspace
+    ``sdnq_hip_attn_wide`` filled (its first four slices, each 256-byte aligned; DP = d rounded up to 32, KNp = kn rounded up to 32).
+    k_q is in the fragment order ``unpack_k_fragments`` reads."""
+    dp, knp = (d + 31) // 32 * 32, (kn + 31) // 32 * 32
+    shapes = (((z, qh, qn, dp), torch.int8), ((z, qh, qn), torch.float32), ((z, kh, knp // 32, dp // 32, 64, 16), torch.int8), ((z, kh, knp), torch.float32))
+    parts, off = [], 0
+    for shp, dt in shapes:
+        nbytes = math.prod(shp) * dt.itemsize
+        parts.append(ws[off:off + nbytes].view(dt).view(shp))
+        off += -(-nbytes // 256) * 256
+    return tuple(parts)
+
+
+def quantize_attn_wide(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, smooth_k: bool = True):
+    """The prepare pass of ``sdnq_hip_attn_wide`` on its own account (the forward launch that follows it is discarded): (workspace, q_q, q_scale,
+    k_q, k_scale) -- ``wide_operands`` of the workspace.  For tests and tools that run ``atten_wide_lse`` / ``atten_wide_bwd`` on given tensors."""
+    z, qh, qn, d = query.shape
+    kh, kn = key.shape[1], key.shape[2]
+    _, ws = _atten_wide(query, key, value, None, False, 1.0, smooth_k, False, "int8", None, "int8", None, query.dtype, with_workspace=True)
+    return (ws,) + wide_operands(ws, z, qh, kh, qn, kn, d)
+
+
+def atten_wide_lse(ws: torch.Tensor, z: int, qh: int, kh: int, qn: int, kn: int, d: int, sm_scale: float, is_causal: bool, lse_dtype: torch.dtype,
+                   attn_mask: torch.Tensor | None = None) -> torch.Tensor:
+    """``atten_lse`` for head dims 136 .. 256 on the workspace of ``sdnq_hip_attn_wide``."""
+    lse = torch.empty((z, qh, qn), device=ws.device, dtype=lse_dtype)
+    mptr, mdt, ms = _mask_args(attn_mask)
+    ops.check(_lib.load().sdnq_hip_attn_wide_lse(ws.data_ptr(), ws.numel(), float(sm_scale), 1 if is_causal else 0, mptr, mdt, *ms, lse.data_ptr(),
+                                                 ops.float_code(lse_dtype), z, qh, kh, qn, kn, d, ops._stream(ws)), "attn_wide_lse")
+    return lse
+
+
+def atten_wide_bwd(grad: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, ws: torch.Tensor, value: torch.Tensor, sm_scale: float, is_causal: bool,
+                   attn_mask: torch.Tensor | None = None, need=(True, True, True), token_major: bool = False):
+    """``atten_bwd`` for head dims 136 .. 256 on the workspace of ``sdnq_hip_attn_wide`` (no rotation): (dq, dk, dv) in the dtype of ``grad``,
+    None where ``need`` says so; one call."""
+    z, qh, qn, d = grad.shape
+    kh, kn = value.shape[1], value.shape[2]
+    gdt = grad.dtype
+    grad = _rows16(grad)
+    grad_v = grad if gdt == value.dtype else _rows16(grad.to(value.dtype))  # dO as the operand of dO.V^T and dO^T.P
+    dev = grad.device
+    if not any(need):
+        return None, None, None
+    delta = torch.empty((z * qh * qn,), device=dev, dtype=torch.float32)
+    dq = dk = dv = None
+    if need[0]:
+        dq = torch.empty((z, qn, qh, d), device=dev, dtype=gdt).transpose(1, 2) if token_major else torch.empty((z, qh, qn, d), device=dev, dtype=gdt)
+    if need[1]:
+        dk = torch.empty((z, kh, kn, d), device=dev, dtype=gdt)
+    if need[2]:
+        dv = torch.empty((z, kh, kn, d), device=dev, dtype=gdt)
+    mptr, mdt, ms = _mask_args(attn_mask)
+
+    def ptr(t):
+        return (t.data_ptr(), _strides(t)) if t is not None else (None, None)
+    ops.check(_lib.load().sdnq_hip_attn_wide_bwd(ws.data_ptr(), ws.numel(), value.data_ptr(), _strides(value), ops.float_code(value.dtype),
+                                                 out.data_ptr(), _strides(out), grad.data_ptr(), _strides(grad), ops.float_code(gdt),
+                                                 grad_v.data_ptr(), _strides(grad_v), lse.data_ptr(), float(sm_scale), 1 if is_causal else 0,
+                                                 mptr, mdt, *ms, delta.data_ptr(), *ptr(dq), d, *ptr(dk), d, *ptr(dv), z, qh, kh, qn, kn, d,
+                                                 ops._stream(grad)), "attn_wide_bwd")
+    return dq, dk, dv
+
+
+class SDNQAttenWideBackward(torch.autograd.Function):
+    """``SDNQAttenBackward`` for head dims 136 .. 256: the forward is ``sdnq_hip_atten``'s own call (``sdnq_hip_attn_wide``) plus the lse pass on
+    its workspace; the backward is one call of ``sdnq_hip_attn_wide_bwd``.  The whole workspace is saved (the backward reads its first four
+    slices; a view of them would keep the rest alive anyway)."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, attn_mask, is_causal, sm_scale, smooth_k, out_dtype):
+        z, qh, qn, d = query.shape
+        kh, kn = key.shape[1], key.shape[2]
+        out, ws = _atten_wide(query, key, value, attn_mask, is_causal, sm_scale, smooth_k, False, "int8", None, "int8", None, out_dtype,
+                              with_workspace=True)
+        lse = atten_wide_lse(ws, z, qh, kh, qn, kn, d, sm_scale, is_causal, out_dtype, attn_mask)
+        ctx.sm_scale, ctx.is_causal = sm_scale, is_causal
+        ctx.token_major = out.stride(2) > out.stride(1)  # the layout _atten_wide gave the output: the query's
+        ctx.save_for_backward(ws, _rows16(value), out, lse, attn_mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        ws, value, out, lse, attn_mask = ctx.saved_tensors
+        dq, dk, dv = atten_wide_bwd(grad_output, out, lse, ws, value, ctx.sm_scale, ctx.is_causal, attn_mask, need=tuple(ctx.needs_input_grad[:3]),
+                                    token_major=ctx.token_major)
+        return dq, dk, dv, None, None, None, None, None
+
+
 class SDNQAttenBackward(torch.autograd.Function):
     """SDNQAttenBackward (triton_atten_backward.py:844-916): the forward is quantize_attn + the forward kernel (the three-call route of
     ``sdnq_hip_atten``, bit for bit the same output) plus the lse pass; the backward runs the HIP dQ and dK / dV kernels."""
@@ -427,13 +521,21 @@ def sdnq_hip_atten_with_backward(query: torch.Tensor, key: torch.Tensor, value: 
     if query.ndim != 4 or key.ndim != 4 or value.ndim != 4:
         raise ValueError("query / key / value must be [batch, heads, tokens, head_dim]")
     d = query.shape[-1]
-    if key.shape[-1] != d or value.shape[-1] != d or d % 8 or not 8 <= d <= 128:
-        raise NotImplementedError("query, key and value must share a head_dim that is a multiple of 8 and at most 128")
+    if key.shape[-1] != d or value.shape[-1] != d or d % 8 or not 8 <= d <= 256:
+        raise NotImplementedError("query, key and value must share a head_dim that is a multiple of 8 and at most 256")
     if query.dtype not in (torch.bfloat16, torch.float16) or key.dtype != query.dtype or value.dtype != query.dtype:
         raise NotImplementedError("query / key / value must share one of bfloat16 / float16")
     if out_dtype is None:
         out_dtype = query.dtype
     sm_scale = d ** -0.5 if scale is None else scale
+    if d > 128:  # head dims 136 .. 256: the kernels of csrc/attention_wide.hip and csrc/attention_wide_bwd.hip (no rotation)
+        if use_hadamard:
+            raise NotImplementedError(f"use_hadamard=True with head_dim {d} > 128 is not built (the reference rotates over the padded 256-wide head)")
+        if not query.is_cuda or not key.is_cuda or not value.is_cuda or (attn_mask is not None and not attn_mask.is_cuda):
+            raise _lib.SdnqHipError("sdnq_amd attention needs CUDA/HIP tensors (no CPU fallback)")
+        if attn_mask is not None:
+            attn_mask = prepare_mask(attn_mask, query.shape[2], key.shape[2])
+        return SDNQAttenWideBackward.apply(query, key, value, attn_mask, bool(is_causal), float(sm_scale), bool(smooth_k), out_dtype)
     group = 0
     if use_hadamard:
         from .quant_utils import get_hadamard_group_size

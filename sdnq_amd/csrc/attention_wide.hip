@@ -17,15 +17,11 @@
 // price is the score arithmetic twice.  A workgroup is two pairs: two query tiles of one head, which stream the same K / V.
 // Software pipeline: K of block kb + 1 is in registers and S(kb + 1) on the matrix pipe while the VALU works on the scores of kb; the key
 // scales and V of kb + 1 are loaded as soon as block kb has consumed its own.
-#include "attn_dev.h"
+#include "attn_wide_dev.h"
 
 namespace {
 
-constexpr int WIDE_KMEAN_SPLITS = 32;
-constexpr int WIDE_SLOTS = 256;  // a token row is spread over 32 lanes of 8 channels: 256 channel slots, those at or past DP are never stored
-
-// the kernels' head dim: head_dim rounded up to 32 (0: not a head dim of this unit)
-inline int wide_dim(int64_t head_dim) { return (head_dim < 136 || head_dim > 256 || head_dim % 8) ? 0 : (int)((head_dim + 31) / 32 * 32); }
+// wide_dim, the workspace layout wide_ws and the channel-slot constants: attn_wide_dev.h (shared with attention_wide_bwd.hip)
 
 // ---- channel sums of K: thread tid adds channels [8 (tid % 32), + 8) of the rows lo + tid / 32, + 8, ... below hi --------------------------
 template <int T_ID>
@@ -440,23 +436,6 @@ int wide_launch_d(const WideParams& p, int dp, int causal, int64_t blocks, hipSt
     if (dp == 224) return wide_launch<V_T, OUT_T, 224>(p, causal, blocks, s);
     if (dp == 256) return wide_launch<V_T, OUT_T, 256>(p, causal, blocks, s);
     return SDNQ_ERR_UNSUPPORTED;
-}
-
-inline int64_t up256(int64_t n) { return (n + 255) / 256 * 256; }
-struct WideWs { int64_t qq, qs, kq, ks, vt, kmean, total; };
-// workspace slices (bytes, 256-byte aligned)
-WideWs wide_ws(int64_t batch, int64_t q_heads, int64_t kv_heads, int64_t q_len, int64_t kv_len, int64_t dp) {
-    WideWs w{};
-    const int64_t knp = (kv_len + 31) / 32 * 32;
-    int64_t off = 0;
-    w.qq = off; off += up256(batch * q_heads * q_len * dp);
-    w.qs = off; off += up256(batch * q_heads * q_len * 4);
-    w.kq = off; off += up256(batch * kv_heads * knp * dp);
-    w.ks = off; off += up256(batch * kv_heads * knp * 4);
-    w.vt = off; off += up256(batch * kv_heads * knp * dp * 2);
-    w.kmean = off; off += up256(batch * kv_heads * WIDE_KMEAN_SPLITS * WIDE_SLOTS * 4);
-    w.total = off;
-    return w;
 }
 
 }  // namespace
