@@ -142,6 +142,28 @@ int sdnq_hip_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t 
 int sdnq_hip_rowquant_lp(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int mm_dtype, int hadamard_group,
                          void* xq, float* xs, int32_t* rowsum, void* xrot, sdnq_stream_t stream);
 
+/* ---- normalisation + row quantization in ONE launch (the producer of the activation a quantized Linear consumes) ----------------
+ * For each row of x [M][K] (x_dtype = T: SDNQ_BF16 or SDNQ_F16, row stride ldx elements), in float32:
+ *     norm 0 (LayerNorm): mean = sum(x) / K, var = sum((x - mean)^2) / K (two-pass);   norm 1 (RMSNorm): mean = 0, var = sum(x^2) / K
+ *     r = 1 / sqrt(var + eps)                             (IEEE sqrt and division)
+ *     n = (x - mean) * r
+ *     a = fmaf(n, weight[k], bias[k])  |  n * weight[k]  |  n          weight / bias: [K] of affine_dtype (SDNQ_F32 or T), NULL to skip;
+ *                                                                      bias needs weight, RMSNorm takes no bias
+ *     z = fmaf(a, 1 + scale[b][k], shift[b][k])  |  a                  the adaLN modulation: scale / shift [B][ld_mod] of T, both or neither,
+ *                                                                      b = row / rows_per_batch (M % rows_per_batch == 0), "1 + scale" one add
+ *     y = round_T(z)                                                   ONE rounding to T
+ *     xs, xq = what sdnq_hip_rowquant(y, mm_dtype, hadamard_group = 0) writes for that y, bit for bit (symmetric int8 / fp8-e4m3fn codes)
+ * y: [M][K] of T, contiguous, or NULL: the row is then never written in T (a read of 2MK bytes, a write of MK + 4M).
+ * xq / xs: both, or both NULL with y given: the normalisation alone.
+ * K % 8 == 0; every pointer, ldx * 2 and ld_mod * 2 16-byte aligned (SDNQ_ERR_ALIGN).  prefetch / prefetch_bytes: as in sdnq_hip_rowquant,
+ * a pure hint.  Validates everything before the launch; capturable.  Not built: Hadamard rotation, rowsum / xrot, asymmetric codes,
+ * 16-bit scales, float32 rows. */
+int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int norm, float eps,
+                           const void* weight, const void* bias, int affine_dtype,
+                           const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
+                           int mm_dtype, void* y, void* xq, float* xs,
+                           const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream);
+
 /* ---- a15/a16: scaled matmul (the operator seam) --------------------------------------------
  * replaces int_scaled_mm_func / fp8_scaled_mm_func (kernel_wrappers.py:193-204) and the Triton op
  * sdnq::scaled_mm (kernels/triton_scaled_mm.py:127-275):

@@ -40,6 +40,9 @@ UNITS = (
     # SGPRs with the wave, so the loads go out without a scalar round trip first; the other arguments are fetched behind them
     ("rowquant", "-DSDNQ_PRELOAD_ROWQUANT " + _PRELOAD, "SDNQ_PRELOAD_ROWQUANT"),
     # gemm.hip: the same for the GEMM kernel's 14 leading scalar arguments (tile mapping, operand descriptors, prologue DMAs)
+    # normquant.hip (normalisation + row quantization in one launch): its arguments travel as one by-value struct, so no preload; no
+    # packed-fp32 forms, as attention_wide.hip
+    ("normquant", "-Xclang -target-feature -Xclang -packed-fp32-ops", None),
     ("gemm", "-DSDNQ_PRELOAD_GEMM " + _PRELOAD, "SDNQ_PRELOAD_GEMM"),
     # the other kernels with scalar arguments get theirs preloaded as well: the GEMM variants, the weight-side units (dequant.hip's
     # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax,

@@ -51,6 +51,9 @@ std::atomic<long> g_epoch{0};        // bumped whenever a module-level switch of
 std::atomic<long> g_fused_calls{0};  // calls that took the one-launch route (ops.fused_calls counts the Python path's)
 std::atomic<long> g_plan_calls{0};   // calls a plan carried (tests / bench: proof that the fast path ran)
 thread_local int t_no_reuse = 0;     // linear._ts.no_reuse (identity_reuse_disabled): no identity-keyed reuse on this thread
+// linear._ts.seed: the tensor whose quantized copy a fused norm (norms.py) parked last on this thread.  Compared by address only, never
+// dereferenced (a stale address makes a plan decline one call: the Python forward then decides); NULL in a model without fused norms.
+thread_local PyObject* t_seed = nullptr;
 
 int float_code(at::ScalarType t) {  // ops.float_code
     if (t == at::kBFloat16) return SDNQ_BF16;
@@ -420,6 +423,7 @@ PyObject* plan_call(PyObject* self, PyObject* const* args, size_t nargsf, PyObje
             if (PyErr_Occurred()) return nullptr;
             Py_RETURN_NONE;
         }
+        if (in == t_seed) Py_RETURN_NONE;  // its codes are parked in the activation cache: the Python forward runs the GEMM on them
         at::Tensor x2 = x.dim() == 2 ? x : x.reshape({-1, p->k});
         if (x2.stride(-1) != 1 || (x2.stride(0) * (int64_t)x2.element_size()) % 16) x2 = x2.contiguous();
         void* stream = (void*)c10::hip::getCurrentHIPStream((c10::DeviceIndex)p->device).stream();
@@ -609,6 +613,10 @@ PyObject* m_set_no_reuse(PyObject*, PyObject* arg) {
     t_no_reuse = (int)v;
     Py_RETURN_NONE;
 }
+PyObject* m_set_seed(PyObject*, PyObject* arg) {
+    t_seed = arg == Py_None ? nullptr : arg;
+    Py_RETURN_NONE;
+}
 PyObject* m_chain_reset(PyObject*, PyObject*) {
     t_prev.reset();
     Py_RETURN_NONE;
@@ -631,6 +639,7 @@ PyMethodDef module_methods[] = {
     {"init", m_init, METH_O, "init(path of libsdnq_hip.so): resolve the entry points the plans launch"},
     {"bump_epoch", m_bump_epoch, METH_NOARGS, "every plan made so far is stale from now on"},
     {"set_no_reuse", m_set_no_reuse, METH_O, "this thread's identity_reuse_disabled() depth"},
+    {"set_seed", m_set_seed, METH_O, "the tensor a fused norm parked last on this thread (None: none): plans decline it"},
     {"chain_reset", m_chain_reset, METH_NOARGS, "this thread's prefetch chain forgets its last unit"},
     {"last_hint", m_last_hint, METH_NOARGS, "(hints handed to the library by this thread, then the ranges of the last one)"},
     {"fused_calls", m_fused_calls, METH_NOARGS, "plan calls that took the one-launch route"},

@@ -1,0 +1,286 @@
+// Fused normalisation + row quantization for gfx950: LayerNorm / RMSNorm (+ affine, + adaLN modulation) of an activation row, the ONE
+// rounding to the row dtype, and the int8 / fp8 codes and row scale the row quantizer (rowquant.hip) would write for that rounded row
+// -- one launch where the norm is a float kernel that writes y and the quantizer a second launch that reads y back.
+//
+//   stats (float32): LayerNorm: mean = sum(x) / K, var = sum((x - mean)^2) / K (two-pass, from the registers);  RMSNorm: ms = sum(x^2) / K
+//   r = 1 / sqrt(var + eps)                                   IEEE sqrt and division
+//   n = (x - mean) * r                                        (RMSNorm: mean = 0, x - 0 is x)
+//   a = fmaf(n, weight, bias) | n * weight | n
+//   z = fmaf(a, 1 + scale[b], shift[b]) | a                   b = row / rows_per_batch
+//   y = round_T(z);   xs = amax|y| / qmax;   xq = quant8(y / xs)     the quantizer's own arithmetic (quant8_dev.h)
+//
+// HBM-bound: reads 2 B and writes 1 B (+ 2 B with the y store) per element, + 4 B per row; the per-row vectors stay in L2.
+// Layout: the row quantizer's -- one wave (64 lanes) per row, 8 consecutive elements per lane per 512-element pass, every global
+// access a 16-byte lane vector (rowvec_dev.h).  Rows up to NP * 512 <= 4096 elements live in registers across the three reductions
+// (sum, sum of squared deviations, amax|y|); the normalised row replaces the input row in the same registers, so the row is read
+// from HBM once.  Longer rows (NP == 0) take the sweep form: the same code with every pass re-read from L2 and y recomputed for the
+// codes (same inputs, same operations: the same bits).  No LDS.
+// Every sum runs in a fixed order -- 8 per-lane accumulators over the passes, a tree over the 8, the xor butterfly over the lanes -- and
+// a row never leaves its wave, so a row's bits do not depend on M or the grid.
+#include "quant8_dev.h"
+#include "rowvec_dev.h"
+#include "sdnq_dev.h"
+
+namespace {
+
+struct NormQuantArgs {
+    const void* x;
+    int64_t M, K, ldx;
+    int row_blocks;
+    int rms;                 // 0 LayerNorm, 1 RMSNorm
+    float eps;
+    int aff_f32;             // weight / bias are float32 (else the row dtype)
+    const void* weight;      // [K] or NULL
+    const void* bias;        // [K] or NULL
+    const void* scale;       // [B][ld_mod] of the row dtype or NULL
+    const void* shift;
+    int64_t rows_per_batch, ld_mod;
+    void* y;                 // [M][K] of the row dtype or NULL
+    uint8_t* xq;             // codes and row scales: both, or both NULL (then only y is written)
+    float* xs;
+    const uint4* pf;
+    int64_t pf_vecs;
+};
+
+// 8-byte store of quantized codes, write-through (sc0 sc1) as rowquant_kernel's: the codes are read by the following GEMM from OTHER
+// XCDs; left dirty in this XCD's L2 they cost that GEMM a remote write-back per first touch
+__device__ __forceinline__ void store_codes8(uint8_t* dst, const uint2& qv) {
+#if !defined(SDNQ_RQ_STORE_PLAIN)
+    typedef int v2i_t __attribute__((ext_vector_type(2)));
+    const v2i_t w2 = {(int)qv.x, (int)qv.y};
+    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(w2) : "memory");
+#else
+    *(uint2*)dst = qv;
+#endif
+}
+
+// software prefetch of the following GEMM's weight operand, as rowquant_kernel's: the workgroups a launch appends behind its row blocks
+// just stream it once so it sits in the last-level cache (MALL) / L2 when the GEMM's LDS-DMA asks for it.  `block`: index among those workgroups (256 threads
+// each); 8 loads in flight per lane.  `sink`: any float the kernel may write (the store never happens: it keeps the loads alive).
+__device__ __forceinline__ void prefetch_block(const uint4* __restrict__ pf, int64_t pf_vecs, int64_t block, float* sink) {
+    const int64_t base = block * (256 * 8) + threadIdx.x;
+    u32 acc = 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int64_t i = base + (int64_t)u * 256;
+        if (i < pf_vecs) { const uint4 v = pf[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
+    }
+    if (acc == 0x9e3779b9u && pf_vecs < 0) sink[0] = 0.0f;  // never true: keeps the loads alive
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    return __int_as_float(wave_allreduce_i32(__float_as_int(v), [](int a, int b) { return __float_as_int(__int_as_float(a) + __int_as_float(b)); }));
+}
+__device__ __forceinline__ float tree8(const float (&a)[8]) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
+
+// 8 consecutive elements of a per-row vector (weight, bias: float32 or the row dtype; scale, shift: the row dtype) as floats
+template <int T_ID>
+__device__ __forceinline__ void load_vec8(const void* p, int64_t i, bool f32, float (&o)[8]) {
+    if (f32) {  // wave-uniform
+        Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p + i), o);
+        Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p + i + 4), o + 4);
+    } else {
+        Vec16<T_ID>::unpack(*(const uint4*)((const uint16_t*)p + i), o);
+    }
+}
+
+// what a row's elements need once its statistics are known (every branch below is wave-uniform)
+struct RowNorm {
+    float mean, r;
+    const void *weight, *bias, *scale, *shift;  // the modulation rows of this row's batch
+    bool aff_f32;
+};
+
+// y = round_T(modulate(affine((x - mean) * r))) for the 8 elements at `idx`; lanes past the end of the row get zeros
+template <int T_ID>
+__device__ __forceinline__ void norm8(const float (&x)[8], int64_t idx, bool ok, const RowNorm& c, float (&y)[8]) {
+    const int64_t i = ok ? idx : 0;
+    float w[8], b[8], sc[8], sh[8];
+    if (c.weight) load_vec8<T_ID>(c.weight, i, c.aff_f32, w);
+    if (c.bias) load_vec8<T_ID>(c.bias, i, c.aff_f32, b);
+    if (c.scale) {
+        load_vec8<T_ID>(c.scale, i, false, sc);
+        load_vec8<T_ID>(c.shift, i, false, sh);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float a = (x[e] - c.mean) * c.r;
+        if (c.bias) a = fmaf(a, w[e], b[e]);
+        else if (c.weight) a = a * w[e];
+        if (c.scale) a = fmaf(a, 1.0f + sc[e], sh[e]);
+        y[e] = ok ? FT<T_ID>::round(a) : 0.0f;
+    }
+}
+
+// T_ID: row dtype (bf16 / f16); MM: SdnqMM; NP: 512-element passes of the row held in registers (K <= NP * 512), 0: the sweep form
+template <int T_ID, int MM, int NP>
+__global__ __launch_bounds__(256) void normquant_kernel(const NormQuantArgs A) {
+    if ((int)blockIdx.x >= A.row_blocks) {
+        prefetch_block(A.pf, A.pf_vecs, (int64_t)blockIdx.x - A.row_blocks, A.xs);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= A.M) return;  // whole wave exits together
+    const int64_t K = A.K;
+    const void* row = (const char*)A.x + m * A.ldx * 2;
+    const int64_t npass = NP > 0 ? NP : (K + 511) / 512;
+    constexpr int UNR = NP > 0 ? NP : 1;  // the pass loops: unrolled over the registers, a plain loop in the sweep form
+    float v[NP > 0 ? NP : 1][8];
+    if constexpr (NP > 0) {
+        uint4 ra[NP], rb[NP];  // every pass of the row in flight before the first use
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int64_t idx = (int64_t)p * 512 + lane * 8;
+            load8_raw<T_ID>(row, idx, idx < K, ra[p], rb[p]);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) unpack8<T_ID>(ra[p], rb[p], (int64_t)p * 512 + lane * 8 < K, v[p]);
+    }
+    // pass p of the row: from the registers, or read again (L2)
+    auto pass = [&](int64_t p, float (&t)[8]) {
+        if constexpr (NP > 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t[e] = v[p][e];
+        } else {
+            const int64_t idx = p * 512 + lane * 8;
+            load8<T_ID>(row, idx, idx < K, t);
+        }
+    };
+    const float fk = (float)K;
+    RowNorm c;
+    c.mean = 0.0f;
+    if (!A.rms) {
+        float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll UNR
+        for (int64_t p = 0; p < npass; ++p) {
+            float t[8];
+            pass(p, t);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += t[e];  // (lanes past the end hold zeros)
+        }
+        c.mean = wave_sum_f32(tree8(acc)) / fk;
+    }
+    {
+        float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll UNR
+        for (int64_t p = 0; p < npass; ++p) {
+            float t[8];
+            pass(p, t);
+            const bool ok = p * 512 + lane * 8 < K;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = t[e] - c.mean;
+                acc[e] += ok ? d * d : 0.0f;
+            }
+        }
+        const float var = wave_sum_f32(tree8(acc)) / fk;
+        c.r = 1.0f / sqrtf(var + A.eps);
+    }
+    c.weight = A.weight;
+    c.bias = A.bias;
+    c.aff_f32 = A.aff_f32 != 0;
+    c.scale = c.shift = nullptr;
+    if (A.scale) {
+        int64_t b, rem;
+        divmod(m, A.rows_per_batch, b, rem);
+        c.scale = (const char*)A.scale + b * A.ld_mod * 2;
+        c.shift = (const char*)A.shift + b * A.ld_mod * 2;
+    }
+    void* yrow = A.y ? (char*)A.y + m * K * 2 : nullptr;
+    float amax = 0.0f;
+#pragma unroll UNR
+    for (int64_t p = 0; p < npass; ++p) {
+        const int64_t idx = p * 512 + lane * 8;
+        const bool ok = idx < K;
+        float t[8], yv[8];
+        pass(p, t);
+        norm8<T_ID>(t, idx, ok, c, yv);
+        if (yrow && ok) store8<T_ID>(yrow, idx, yv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            amax = fmaxf(amax, fabsf(yv[e]));
+            if constexpr (NP > 0) v[p][e] = yv[e];  // the normalised row takes the input row's registers
+        }
+    }
+    if (A.xq == nullptr) return;  // only y was asked for
+    amax = wave_max(amax);
+    const float qmax = (MM == SDNQ_MM_I8) ? 127.0f : 448.0f;
+    const float scale = amax / qmax;  // IEEE division, as rowquant_kernel
+    if (lane == 0) A.xs[m] = scale;
+    RowDiv rd;
+    rd.set(scale);
+    uint8_t* qrow = A.xq + m * K;
+    int isum = 0;  // (quant8's row sum: unused here)
+#pragma unroll UNR
+    for (int64_t p = 0; p < npass; ++p) {
+        const int64_t idx = p * 512 + lane * 8;
+        const bool ok = idx < K;
+        float yv[8];
+        if constexpr (NP > 0) {
+            pass(p, yv);
+        } else {
+            float t[8];
+            pass(p, t);
+            norm8<T_ID>(t, idx, ok, c, yv);
+        }
+        if (ok) store_codes8(qrow + idx, quant8<MM>(yv, rd, isum));
+    }
+}
+
+}  // namespace
+
+extern "C" int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int norm, float eps,
+                                      const void* weight, const void* bias, int affine_dtype,
+                                      const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
+                                      int mm_dtype, void* y, void* xq, float* xs,
+                                      const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream) {
+    if (!x || (!xq != !xs) || (!xq && !y)) return SDNQ_ERR_NULL;
+    if ((bias && !weight) || (!scale != !shift)) return SDNQ_ERR_NULL;
+    if (norm != 0 && norm != 1) return SDNQ_ERR_UNSUPPORTED;
+    if (norm == 1 && bias) return SDNQ_ERR_UNSUPPORTED;  // RMSNorm has no bias
+    if (x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;  // float32 rows: not built
+    if (mm_dtype != SDNQ_MM_I8 && mm_dtype != SDNQ_MM_FP8) return SDNQ_ERR_DTYPE;
+    if (weight && affine_dtype != SDNQ_F32 && affine_dtype != x_dtype) return SDNQ_ERR_DTYPE;
+    if (m <= 0 || k <= 0 || (k % 8) != 0 || ldx < k || k >= ((int64_t)1 << 24)) return SDNQ_ERR_SHAPE;
+    if (!(eps >= 0.0f)) return SDNQ_ERR_SHAPE;
+    if (scale && (rows_per_batch <= 0 || (m % rows_per_batch) != 0 || ld_mod < k)) return SDNQ_ERR_SHAPE;
+    if (((uintptr_t)x % 16) || ((ldx * 2) % 16) || ((uintptr_t)xq % 16) || ((uintptr_t)xs % 4) || ((uintptr_t)y % 16) ||
+        ((uintptr_t)weight % 16) || ((uintptr_t)bias % 16) || ((uintptr_t)scale % 16) || ((uintptr_t)shift % 16) ||
+        (scale && ((ld_mod * 2) % 16)))
+        return SDNQ_ERR_ALIGN;
+    NormQuantArgs a;
+    a.x = x; a.M = m; a.K = k; a.ldx = ldx;
+    a.row_blocks = (int)((m + 3) / 4);
+    a.rms = norm; a.eps = eps;
+    a.aff_f32 = affine_dtype == SDNQ_F32;
+    a.weight = weight; a.bias = bias; a.scale = scale; a.shift = shift;
+    a.rows_per_batch = rows_per_batch; a.ld_mod = ld_mod;
+    a.y = y; a.xq = (uint8_t*)xq; a.xs = xs;
+    a.pf = (const uint4*)prefetch;
+    a.pf_vecs = 0;
+    if (prefetch && prefetch_bytes > 0 && ((uintptr_t)prefetch % 16) == 0) {
+        const int64_t cap = (int64_t)32 << 20;  // at most 32 MiB, as sdnq_hip_rowquant
+        a.pf_vecs = (prefetch_bytes < cap ? prefetch_bytes : cap) / 16;
+    }
+    const int pf_blocks = (int)((a.pf_vecs + 256 * 8 - 1) / (256 * 8));
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)(a.row_blocks + pf_blocks)), block(256);
+    const int np = (int)((k + 511) / 512);
+#define NQ_LAUNCH(T, MMV, NPV) hipLaunchKernelGGL((normquant_kernel<T, MMV, NPV>), grid, block, 0, s, a)
+#define NQ_NP(T, MMV)                           \
+    do {                                        \
+        if (np <= 1) NQ_LAUNCH(T, MMV, 1);      \
+        else if (np <= 2) NQ_LAUNCH(T, MMV, 2); \
+        else if (np <= 3) NQ_LAUNCH(T, MMV, 3); \
+        else if (np <= 5) NQ_LAUNCH(T, MMV, 5); \
+        else if (np <= 6) NQ_LAUNCH(T, MMV, 6); \
+        else if (np <= 8) NQ_LAUNCH(T, MMV, 8); \
+        else NQ_LAUNCH(T, MMV, 0);              \
+    } while (0)
+#define NQ_MM(T) do { if (mm_dtype == SDNQ_MM_I8) NQ_NP(T, SDNQ_MM_I8); else NQ_NP(T, SDNQ_MM_FP8); } while (0)
+    if (x_dtype == SDNQ_BF16) NQ_MM(SDNQ_BF16);
+    else NQ_MM(SDNQ_F16);
+    SDNQ_CHECK_LAUNCH();
+    return SDNQ_OK;
+}

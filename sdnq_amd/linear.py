@@ -169,6 +169,7 @@ class _ThreadState(__import__("threading").local):
     def __init__(self):
         self.act_cache = _ActivationCache()
         self.no_reuse = 0          # nesting depth of identity_reuse_disabled()
+        self.seed = None           # the tensor whose quantized copy a fused norm parked last (park_seed); None without fused norms
         self.weight_pipeline = None  # created on first use (below: _WeightPipeline is defined later)
 
 
@@ -225,8 +226,21 @@ _groups = []  # weak references to the live SharedInputGroups (invalidate() reac
 _groups_lock = __import__("threading").Lock()
 
 
+def park_seed(t: torch.Tensor | None, params=None, result=None, producer=None):
+    """A producer of `t` that quantized it in its own launch (norms.SDNQFusedNorm) parks the result where `_rowquant_cached` would have,
+    and names `t` as this thread's seed: a layer that stopped parking (UNSHARED_AFTER) or runs on a C++ plan would otherwise quantize
+    `t` again inside its own launch -- for the seed it looks in the cache first.  None: no seed."""
+    if t is not None:
+        _ts.act_cache.put(t, params, result, producer=producer)
+    _ts.seed = t
+    if _FP is not None:
+        _FP.set_seed(t)
+
+
 def clear_activation_cache():
     _ts.act_cache.clear()
+    if _ts.seed is not None:
+        park_seed(None)
     _weight_pipeline.start_step()
 
 
@@ -984,7 +998,7 @@ def _quantized_matmul_forward(self, input: torch.Tensor, mm: int, small_batch_br
     x2 = slab = None
     one_launch = False
     if (plain and FUSED_ROWQUANT and had == 0 and input.is_cuda
-            and (not use_cache or (UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER))):
+            and (not use_cache or (UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER and _ts.seed is not input))):
         # nobody else consumes this layer's quantized activation (its input is its own: to_out, to_q of the cross attention, proj_in /
         # proj_out, ...): where the one-launch route is built and expected to win, the GEMM row-quantizes its own activation rows in
         # LDS -- no row-quantization launch, no quantized copy in HBM, one allocation, safe under graph capture (no scratch buffer).
@@ -1011,7 +1025,7 @@ def _quantized_matmul_forward(self, input: torch.Tensor, mm: int, small_batch_br
                               allow_ws=use_cache and UNSHARED_FAST_PATH, unit=st.pf.c if pf_on else None, wslab=slab)
             return y if input.dim() == 2 else y.view(*input.shape[:-1], n)
         if (use_cache and UNSHARED_FAST_PATH and self.__dict__.get("_sdnq_unshared", 0) >= UNSHARED_AFTER and input.is_cuda
-                and not torch.cuda.is_current_stream_capturing()):
+                and _ts.seed is not input and not torch.cuda.is_current_stream_capturing()):
             # nobody ever used the quantized copy this layer parked (see _ActivationCache._retire): no key, no look-up, the quantized
             # activation in the stream's workspace -- one allocation (the output) and one binding call
             x2 = input if input.dim() == 2 else input.reshape(-1, k)

@@ -208,6 +208,40 @@ def rowquant(x2d: torch.Tensor, mm: int, hadamard_group: int = 0, want_rowsum: b
     return xq, xs, rowsum, xrot
 
 
+NORM_LAYER, NORM_RMS = 0, 1
+
+
+def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale, shift, mm: int | None, want_y: bool = True,
+                  prefetch: torch.Tensor | None = None):
+    """LayerNorm (NORM_LAYER) / RMSNorm (NORM_RMS) of the rows of x2d [M,K] (bf16 / f16), the affine `weight` / `bias` [K] (float32 or
+    x2d's dtype, None to skip) and the adaLN modulation ``y * (1 + scale) + shift`` (`scale` / `shift` [B,K] of x2d's dtype with
+    M % B == 0, or both None), row-quantized in the same launch -> (y [M,K] | None, xq [M,K] int8|fp8, xs [M,1] f32).  The codes are
+    the bits ``rowquant(y, mm)`` gives for the y this returns; ``want_y=False`` never writes y, ``mm=None`` only y (xq, xs: None)."""
+    _require_cuda(x2d, weight, bias, scale, shift)
+    assert x2d.ndim == 2 and x2d.stride(1) == 1
+    m, k = x2d.shape
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is not None and (t.shape != (k,) or not t.is_contiguous() or (weight is not None and t.dtype != weight.dtype)):
+            raise _lib.SdnqHipError(f"norm_rowquant: {name} must be a contiguous [{k}] vector of one dtype with the weight")
+    rows_per_batch = ld_mod = 0
+    if scale is not None or shift is not None:
+        if (scale is None or shift is None or scale.shape != shift.shape or scale.ndim != 2 or scale.shape[1] != k or scale.shape[0] == 0
+                or m % scale.shape[0] or scale.dtype != x2d.dtype or shift.dtype != x2d.dtype or scale.stride() != shift.stride()
+                or scale.stride(1) != 1):
+            raise _lib.SdnqHipError(f"norm_rowquant: scale and shift must both be [B,{k}] rows of {x2d.dtype} with one stride and B dividing "
+                                    f"the {m} rows")
+        rows_per_batch, ld_mod = m // scale.shape[0], scale.stride(0) if scale.shape[0] > 1 else max(scale.stride(0), k)
+    y = torch.empty((m, k), device=x2d.device, dtype=x2d.dtype) if want_y else None
+    xq = None if mm is None else torch.empty((m, k), device=x2d.device, dtype=_MM_TORCH[mm])
+    xs = None if mm is None else torch.empty((m, 1), device=x2d.device, dtype=torch.float32)
+    check(_lib.load().sdnq_hip_norm_rowquant(x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), norm, float(eps), _ptr(weight),
+                                             _ptr(bias), F32 if weight is None else float_code(weight.dtype), _ptr(scale), _ptr(shift),
+                                             rows_per_batch, ld_mod, MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _ptr(prefetch),
+                                             0 if prefetch is None else prefetch.numel() * prefetch.element_size(), _stream(x2d)),
+          "norm_rowquant")
+    return y, xq, xs
+
+
 def colquant_t(x2d: torch.Tensor, want_colsum: bool = False):
     """sdnq_hip_colquant_t: int8-quantize x2d [R,C] per COLUMN and return the codes transposed -- (xq_t [C, ld_t] int8 with
     ld_t = R rounded up to 16 and columns [R, ld_t) zero, xs [C,1] f32, colsum [C] f32 | None): the operand of a scaled matmul that
