@@ -164,6 +164,28 @@ int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int
                            int mm_dtype, void* y, void* xq, float* xs,
                            const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream);
 
+/* ---- activation (+ gate product) + row quantization in ONE launch (the feed-forward producer of a quantized Linear's input) ------
+ * For each row of a [M][N] (x_dtype = T: SDNQ_BF16 or SDNQ_F16, row stride lda elements) and, if given, b [M][N] of T (row stride ldb),
+ * in float32:
+ *     g = act(a[k])        act 0 (GELU):       0.5 a (1 + erf(a / sqrt 2))
+ *                          act 1 (GELU, tanh): 0.5 a (1 + tanh(sqrt(2 / pi) (a + 0.044715 a^3)))
+ *                          act 2 (SiLU):       a / (1 + exp(-a))
+ *                          evaluated on the hardware exponential and reciprocal to within 24 / 7 / 6 float32 half-ulps of |a|
+ *                          (csrc/actquant.hip derives the bounds); act(+-0) = +-0, large |a| gives a or -0, NaN propagates
+ *     z = g * b[k]  |  g   b: the multiplier operand, NULL: ungated
+ *     y = round_T(z)       ONE rounding to T
+ *     xs, xq = what sdnq_hip_rowquant(y, mm_dtype, hadamard_group = 0) writes for that y, bit for bit (symmetric int8 / fp8-e4m3fn codes)
+ * a and b may be the two halves of one [M][2N] projection output (pointers N elements apart, lda = ldb = 2N: GEGLU keeps the value in the
+ * first half and the gate in the second, so a = the second half, b = the first) or two tensors (SwiGLU: a = gate_proj(x), b = up_proj(x)).
+ * y: [M][N] of T, contiguous, not overlapping a or b, or NULL: the row is then never written in T.
+ * xq / xs: both, or both NULL with y given: the activation alone.
+ * N % 8 == 0; every pointer, lda * 2 and ldb * 2 16-byte aligned (SDNQ_ERR_ALIGN).  prefetch / prefetch_bytes: as in sdnq_hip_rowquant,
+ * a pure hint.  Validates everything before the launch; capturable, no workspace, no atomics.  Not built: other activations, Hadamard
+ * rotation, rowsum / xrot, asymmetric codes, 16-bit scales, float32 rows, gradients. */
+int sdnq_hip_act_rowquant(const void* a, const void* b, int x_dtype, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act,
+                          int mm_dtype, void* y, void* xq, float* xs,
+                          const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream);
+
 /* ---- a15/a16: scaled matmul (the operator seam) --------------------------------------------
  * replaces int_scaled_mm_func / fp8_scaled_mm_func (kernel_wrappers.py:193-204) and the Triton op
  * sdnq::scaled_mm (kernels/triton_scaled_mm.py:127-275):

@@ -43,6 +43,9 @@ UNITS = (
     # normquant.hip (normalisation + row quantization in one launch): its arguments travel as one by-value struct, so no preload; no
     # packed-fp32 forms, as attention_wide.hip
     ("normquant", "-Xclang -target-feature -Xclang -packed-fp32-ops", None),
+    # actquant.hip (activation + gate product + row quantization in one launch): one by-value struct as well; its multiplies and fmas
+    # are written as packed pairs
+    ("actquant", "", None),
     ("gemm", "-DSDNQ_PRELOAD_GEMM " + _PRELOAD, "SDNQ_PRELOAD_GEMM"),
     # the other kernels with scalar arguments get theirs preloaded as well: the GEMM variants, the weight-side units (dequant.hip's
     # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax,

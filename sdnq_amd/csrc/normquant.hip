@@ -42,32 +42,6 @@ struct NormQuantArgs {
     int64_t pf_vecs;
 };
 
-// 8-byte store of quantized codes, write-through (sc0 sc1) as rowquant_kernel's: the codes are read by the following GEMM from OTHER
-// XCDs; left dirty in this XCD's L2 they cost that GEMM a remote write-back per first touch
-__device__ __forceinline__ void store_codes8(uint8_t* dst, const uint2& qv) {
-#if !defined(SDNQ_RQ_STORE_PLAIN)
-    typedef int v2i_t __attribute__((ext_vector_type(2)));
-    const v2i_t w2 = {(int)qv.x, (int)qv.y};
-    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(w2) : "memory");
-#else
-    *(uint2*)dst = qv;
-#endif
-}
-
-// software prefetch of the following GEMM's weight operand, as rowquant_kernel's: the workgroups a launch appends behind its row blocks
-// just stream it once so it sits in the last-level cache (MALL) / L2 when the GEMM's LDS-DMA asks for it.  `block`: index among those workgroups (256 threads
-// each); 8 loads in flight per lane.  `sink`: any float the kernel may write (the store never happens: it keeps the loads alive).
-__device__ __forceinline__ void prefetch_block(const uint4* __restrict__ pf, int64_t pf_vecs, int64_t block, float* sink) {
-    const int64_t base = block * (256 * 8) + threadIdx.x;
-    u32 acc = 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int64_t i = base + (int64_t)u * 256;
-        if (i < pf_vecs) { const uint4 v = pf[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
-    }
-    if (acc == 0x9e3779b9u && pf_vecs < 0) sink[0] = 0.0f;  // never true: keeps the loads alive
-}
-
 __device__ __forceinline__ float wave_sum_f32(float v) {
     return __int_as_float(wave_allreduce_i32(__float_as_int(v), [](int a, int b) { return __float_as_int(__int_as_float(a) + __int_as_float(b)); }));
 }

@@ -1,8 +1,9 @@
 // How the one-wave-per-row kernels move a row: 8 consecutive elements per lane per 512-element pass, every global access a 16-byte
-// (bf16 / f16) or 2 x 16-byte (f32) lane-contiguous vector.  Shared by the row quantizers (rowquant.hip) and the fused
-// normalisation + row quantization (normquant.hip); the per-element quantizer arithmetic both apply is quant8_dev.h.  (The row
-// quantizer's write-through code store and prefetch workgroups stay written out in rowquant_kernel: called from here, one
-// instantiation's register allocation and the prefetch block's operand order changed -- profiles/normquant_kernel_compare.txt.)
+// (bf16 / f16) or 2 x 16-byte (f32) lane-contiguous vector.  Shared by the row quantizers (rowquant.hip), the fused normalisation + row
+// quantization (normquant.hip) and the fused activation + row quantization (actquant.hip); the per-element quantizer arithmetic all of
+// them apply is quant8_dev.h.  The write-through code store and the prefetch workgroups at the end of this file serve normquant.hip and
+// actquant.hip.  (The row quantizer's own stay written out in rowquant_kernel: called from here, one instantiation's register
+// allocation and the prefetch block's operand order changed -- profiles/normquant_kernel_compare.txt.)
 #pragma once
 #include "sdnq_dev.h"
 
@@ -47,4 +48,31 @@ __device__ __forceinline__ void store8(void* row, int64_t idx, const float (&v)[
     } else {
         *(uint4*)((uint16_t*)row + idx) = Vec16<T_ID>::pack(v);
     }
+}
+
+// 8-byte store of quantized codes, write-through (sc0 sc1) as rowquant_kernel's: the codes are read by the following GEMM from OTHER
+// XCDs; left dirty in this XCD's L2 they cost that GEMM a remote write-back per first touch
+__device__ __forceinline__ void store_codes8(uint8_t* dst, const uint2& qv) {
+#if !defined(SDNQ_RQ_STORE_PLAIN)
+    typedef int v2i_t __attribute__((ext_vector_type(2)));
+    const v2i_t w2 = {(int)qv.x, (int)qv.y};
+    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(w2) : "memory");
+#else
+    *(uint2*)dst = qv;
+#endif
+}
+
+// software prefetch of the following GEMM's weight operand, as rowquant_kernel's: the workgroups a launch appends behind its row blocks
+// just stream it once so it sits in the last-level cache (MALL) / L2 when the GEMM's LDS-DMA asks for it.  `block`: index among those workgroups (THREADS
+// threads each); 8 loads in flight per lane.  `sink`: any float the kernel may write (the store never happens: it keeps the loads alive).
+template <int THREADS = 256>
+__device__ __forceinline__ void prefetch_block(const uint4* __restrict__ pf, int64_t pf_vecs, int64_t block, float* sink) {
+    const int64_t base = block * (THREADS * 8) + threadIdx.x;
+    u32 acc = 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int64_t i = base + (int64_t)u * THREADS;
+        if (i < pf_vecs) { const uint4 v = pf[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
+    }
+    if (acc == 0x9e3779b9u && pf_vecs < 0) sink[0] = 0.0f;  // never true: keeps the loads alive
 }

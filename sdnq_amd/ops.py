@@ -242,6 +242,32 @@ def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale,
     return y, xq, xs
 
 
+ACT_GELU, ACT_GELU_TANH, ACT_SILU = 0, 1, 2
+
+
+def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | None, want_y: bool = True,
+                 prefetch: torch.Tensor | None = None):
+    """``act(a) * b`` (`b` None: ``act(a)``) over the rows of a [M,N] (bf16 / f16; ACT_GELU, ACT_GELU_TANH or ACT_SILU), computed in
+    float32 with ONE rounding and row-quantized in the same launch -> (y [M,N] | None, xq [M,N] int8|fp8, xs [M,1] f32).  `a` and `b`
+    may be row-strided views (the halves of one [M,2N] projection output); N % 8 == 0, pointers and row strides 16-byte aligned.  The
+    codes are the bits ``rowquant(y, mm)`` gives for the y this returns; ``want_y=False`` never writes y, ``mm=None`` only y (xq, xs:
+    None)."""
+    _require_cuda(a, b)
+    assert a.ndim == 2 and a.stride(1) == 1
+    m, n = a.shape
+    if b is not None and (b.shape != a.shape or b.dtype != a.dtype or b.stride(1) != 1 or b.device != a.device):
+        raise _lib.SdnqHipError(f"act_rowquant: the multiplier must be [{m},{n}] rows of {a.dtype} on a's device")
+    y = torch.empty((m, n), device=a.device, dtype=a.dtype) if want_y else None
+    xq = None if mm is None else torch.empty((m, n), device=a.device, dtype=_MM_TORCH[mm])
+    xs = None if mm is None else torch.empty((m, 1), device=a.device, dtype=torch.float32)
+    check(_lib.load().sdnq_hip_act_rowquant(a.data_ptr(), _ptr(b), float_code(a.dtype), m, n, a.stride(0) if m > 1 else n,
+                                            0 if b is None else (b.stride(0) if m > 1 else n), act,
+                                            MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _ptr(prefetch),
+                                            0 if prefetch is None else prefetch.numel() * prefetch.element_size(), _stream(a)),
+          "act_rowquant")
+    return y, xq, xs
+
+
 def colquant_t(x2d: torch.Tensor, want_colsum: bool = False):
     """sdnq_hip_colquant_t: int8-quantize x2d [R,C] per COLUMN and return the codes transposed -- (xq_t [C, ld_t] int8 with
     ld_t = R rounded up to 16 and columns [R, ld_t) zero, xs [C,1] f32, colsum [C] f32 | None): the operand of a scaled matmul that
