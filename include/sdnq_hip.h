@@ -155,14 +155,12 @@ int sdnq_hip_rowquant_lp(const void* x, int x_dtype, int64_t m, int64_t k, int64
  *     xs, xq = what sdnq_hip_rowquant(y, mm_dtype, hadamard_group = 0) writes for that y, bit for bit (symmetric int8 / fp8-e4m3fn codes)
  * y: [M][K] of T, contiguous, or NULL: the row is then never written in T (a read of 2MK bytes, a write of MK + 4M).
  * xq / xs: both, or both NULL with y given: the normalisation alone.
- * K % 8 == 0; every pointer, ldx * 2 and ld_mod * 2 16-byte aligned (SDNQ_ERR_ALIGN).  prefetch / prefetch_bytes: as in sdnq_hip_rowquant,
- * a pure hint.  Validates everything before the launch; capturable.  Not built: Hadamard rotation, rowsum / xrot, asymmetric codes,
- * 16-bit scales, float32 rows. */
+ * K % 8 == 0; every pointer, ldx * 2 and ld_mod * 2 16-byte aligned (SDNQ_ERR_ALIGN).  Validates everything before the launch;
+ * capturable.  Not built: Hadamard rotation, rowsum / xrot, asymmetric codes, 16-bit scales, float32 rows. */
 int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int norm, float eps,
                            const void* weight, const void* bias, int affine_dtype,
                            const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
-                           int mm_dtype, void* y, void* xq, float* xs,
-                           const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream);
+                           int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream);
 
 /* ---- activation (+ gate product) + row quantization in ONE launch (the feed-forward producer of a quantized Linear's input) ------
  * For each row of a [M][N] (x_dtype = T: SDNQ_BF16 or SDNQ_F16, row stride lda elements) and, if given, b [M][N] of T (row stride ldb),
@@ -179,12 +177,11 @@ int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int
  * first half and the gate in the second, so a = the second half, b = the first) or two tensors (SwiGLU: a = gate_proj(x), b = up_proj(x)).
  * y: [M][N] of T, contiguous, not overlapping a or b, or NULL: the row is then never written in T.
  * xq / xs: both, or both NULL with y given: the activation alone.
- * N % 8 == 0; every pointer, lda * 2 and ldb * 2 16-byte aligned (SDNQ_ERR_ALIGN).  prefetch / prefetch_bytes: as in sdnq_hip_rowquant,
- * a pure hint.  Validates everything before the launch; capturable, no workspace, no atomics.  Not built: other activations, Hadamard
- * rotation, rowsum / xrot, asymmetric codes, 16-bit scales, float32 rows, gradients. */
+ * N % 8 == 0; every pointer, lda * 2 and ldb * 2 16-byte aligned (SDNQ_ERR_ALIGN).  Validates everything before the launch; capturable,
+ * no workspace, no atomics.  Not built: other activations, Hadamard rotation, rowsum / xrot, asymmetric codes, 16-bit scales, float32
+ * rows, gradients. */
 int sdnq_hip_act_rowquant(const void* a, const void* b, int x_dtype, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act,
-                          int mm_dtype, void* y, void* xq, float* xs,
-                          const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream);
+                          int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream);
 
 /* ---- a15/a16: scaled matmul (the operator seam) --------------------------------------------
  * replaces int_scaled_mm_func / fp8_scaled_mm_func (kernel_wrappers.py:193-204) and the Triton op

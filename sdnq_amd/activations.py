@@ -17,6 +17,7 @@ import torch
 
 from . import linear as _L
 from . import ops
+from .producers import FuseResult as FuseActivationsResult, fuse, unfuse
 
 _PLAIN, _PROJ, _MLP = "plain", "proj", "mlp"
 
@@ -113,8 +114,8 @@ class SDNQFusedActivation(torch.nn.Module):
         seeding = self.__dict__.get("_sdnq_unshared", 0) < _L.UNSHARED_AFTER and _L.CACHE_ACTIVATIONS > 0
         y2, xq, xs = ops.act_rowquant(a, b, self.act, self.mm if seeding else None)
         y = y2.view(shape)
-        if seeding:  # the params tuple of linear._rowquant_cached: symmetric codes, no rotation, no rowsum, no rotated copy
-            _L.park_seed(y, (self.mm, 0, False, False, False, ops._stream(y)), (y2, xq, xs, None, None), producer=self)
+        if seeding:
+            _L.park_produced(y, y2, xq, xs, self.mm, self)
         return y
 
     def forward(self, x: torch.Tensor, *args, **kwargs) -> torch.Tensor:
@@ -133,19 +134,6 @@ class SDNQFusedActivation(torch.nn.Module):
         return self._launch(h[:, n:], h[:, :n], (*x.shape[:-1], n))
 
 
-class FuseActivationsResult(int):
-    """What ``fuse_activations()`` returns: an int (the number of modules wrapped) that also carries ``.fused`` -- their qualified names
-    -- and ``.skipped`` -- [(qualified module name, reason)] of the candidates left as they were."""
-
-    def __new__(cls, fused, skipped):
-        r = super().__new__(cls, len(fused))
-        r.fused, r.skipped = list(fused), list(skipped)
-        return r
-
-    def __iter__(self):  # `fused, skipped = fuse_activations(model)`
-        return iter((self.fused, self.skipped))
-
-
 def _candidate(mod: torch.nn.Module) -> bool:
     """What the default walk looks at: the modules ``act_kind`` could accept and their near misses (they get a sentence)."""
     return (isinstance(mod, (torch.nn.GELU, torch.nn.SiLU)) or (type(mod).__name__ in ("GEGLU", "SwiGLU", "GELU", "ApproximateGELU") and hasattr(mod, "proj"))
@@ -158,38 +146,9 @@ def fuse_activations(model: torch.nn.Module, targets=None, mm: str = "int8") -> 
     wrapper's).  `mm`: the matmul dtype of the layers behind the activations ("int8" / "fp8") -- the parked codes serve the layers that
     quantize to it.  Named targets the kernel cannot stand in for, and by default the near misses, are listed in ``.skipped`` with the
     reason."""
-    ops.mm_code(mm)
-    mods = dict(model.named_modules())
-    if targets is None or callable(targets):
-        names = [n for n, m in mods.items() if n and (targets(n, m) if callable(targets) else _candidate(m))]
-    else:
-        names = list(targets)
-    fused, skipped = [], []
-    for name in names:
-        mod = mods.get(name)
-        if mod is None or not name:
-            skipped.append((name, "is not a submodule of the model"))
-            continue
-        parents = [name[:i] for i, c in enumerate(name) if c == "."]
-        if any(p in fused or isinstance(mods[p], SDNQFusedActivation) for p in parents):
-            continue  # inside a wrapper: the wrapper's
-        kind = act_kind(mod)
-        if isinstance(kind, str):
-            skipped.append((name, kind))
-            continue
-        parent, _, leaf = name.rpartition(".")
-        setattr(mods[parent], leaf, SDNQFusedActivation(mod, mm))
-        fused.append(name)
-    return FuseActivationsResult(fused, skipped)
+    return fuse(model, targets, mm, SDNQFusedActivation, act_kind, _candidate)
 
 
 def unfuse_activations(model: torch.nn.Module) -> int:
     """Put the wrapped modules back; returns how many."""
-    count = 0
-    for parent in list(model.modules()):
-        for leaf, child in list(parent.named_children()):
-            if isinstance(child, SDNQFusedActivation) and not isinstance(parent, SDNQFusedActivation):
-                setattr(parent, leaf, child.module)
-                count += 1
-    _L.park_seed(None)
-    return count
+    return unfuse(model, SDNQFusedActivation, "module")

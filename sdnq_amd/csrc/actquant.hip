@@ -55,7 +55,7 @@ struct ActQuantArgs {
     void* y;                 // [M][N] of the row dtype or NULL
     uint8_t* xq;             // codes and row scales: both, or both NULL (then only y is written)
     float* xs;
-    const uint4* pf;
+    const uint4* pf;         // NULL / 0: no entry point takes a prefetch operand (rowvec_dev.h: prefetch_block)
     int64_t pf_vecs;
 };
 
@@ -109,14 +109,6 @@ __device__ __forceinline__ uint4 act8(const uint4& ra, const uint4& rb, bool ok)
 
 // the lane vector at element `idx` of a row; UNCONDITIONAL, as load8_raw (rowvec_dev.h): a lane past the end re-reads the row's start
 __device__ __forceinline__ uint4 load_raw(const void* row, int64_t idx, bool ok) { return *(const uint4*)((const uint16_t*)row + (ok ? idx : 0)); }
-
-template <int MM>
-__device__ __forceinline__ float row_scale(float amax, int lane, float* xs) {
-    amax = wave_max(amax);
-    const float scale = amax / ((MM == SDNQ_MM_I8) ? 127.0f : 448.0f);  // IEEE division, as rowquant_kernel
-    if (lane == 0) *xs = scale;
-    return scale;
-}
 
 // Rows of N <= NP * 512 <= 4096.  T_ID: row dtype (bf16 / f16); MM: SdnqMM; ACT: the activation; GATED: z = act(a) * b
 template <int T_ID, int MM, int ACT, bool GATED, int NP>
@@ -237,8 +229,7 @@ __global__ __launch_bounds__(64) void actquant_long_kernel(const ActQuantArgs A)
 }  // namespace
 
 extern "C" int sdnq_hip_act_rowquant(const void* a, const void* b, int x_dtype, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act,
-                                     int mm_dtype, void* y, void* xq, float* xs,
-                                     const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream) {
+                                     int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream) {
     if (!a || (!xq != !xs) || (!xq && !y)) return SDNQ_ERR_NULL;
     if (act != ACT_GELU && act != ACT_GELU_TANH && act != ACT_SILU) return SDNQ_ERR_UNSUPPORTED;
     if (x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;  // float32 rows: not built
@@ -250,21 +241,14 @@ extern "C" int sdnq_hip_act_rowquant(const void* a, const void* b, int x_dtype, 
     ActQuantArgs A;
     A.a = a; A.b = b; A.M = m; A.N = n; A.lda = lda; A.ldb = ldb;
     A.y = y; A.xq = (uint8_t*)xq; A.xs = xs;
-    A.pf = (const uint4*)prefetch;
-    A.pf_vecs = 0;
-    if (prefetch && prefetch_bytes > 0 && ((uintptr_t)prefetch % 16) == 0) {
-        const int64_t cap = (int64_t)32 << 20;  // at most 32 MiB, as sdnq_hip_rowquant
-        A.pf_vecs = (prefetch_bytes < cap ? prefetch_bytes : cap) / 16;
-    }
+    A.pf = nullptr; A.pf_vecs = 0;
     const int np = (int)((n + 511) / 512);
     const bool reg = n <= ACT_REG_MAX_N;
-    const int threads = reg ? 256 : 64;  // four rows per workgroup | one
-    A.row_blocks = (int)(reg ? (m + 3) / 4 : m);
+    A.row_blocks = (int)(reg ? (m + 3) / 4 : m);  // four rows per workgroup | one
     A.use_lds = (!reg && xq && n <= ACT_LDS_MAX_N) ? 1 : 0;  // (nothing to hold for a y-only launch)
-    const int pf_blocks = (int)((A.pf_vecs + threads * 8 - 1) / (threads * 8));
     const size_t lds_bytes = A.use_lds ? (size_t)np * 64 * sizeof(uint4) : 0;  // <= 32 KB
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)(A.row_blocks + pf_blocks)), block((unsigned)threads);
+    dim3 grid((unsigned)A.row_blocks), block(reg ? 256u : 64u);
 #define AQ_REG(T, MMV, ACTV, G, NPV) hipLaunchKernelGGL((actquant_reg_kernel<T, MMV, ACTV, G, NPV>), grid, block, 0, s, A)
 #define AQ_NP(T, MMV, ACTV, G)                                                                       \
     do {                                                                                             \

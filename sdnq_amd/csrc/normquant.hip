@@ -38,7 +38,7 @@ struct NormQuantArgs {
     void* y;                 // [M][K] of the row dtype or NULL
     uint8_t* xq;             // codes and row scales: both, or both NULL (then only y is written)
     float* xs;
-    const uint4* pf;
+    const uint4* pf;         // NULL / 0: no entry point takes a prefetch operand (rowvec_dev.h: prefetch_block)
     int64_t pf_vecs;
 };
 
@@ -178,12 +178,8 @@ __global__ __launch_bounds__(256) void normquant_kernel(const NormQuantArgs A) {
         }
     }
     if (A.xq == nullptr) return;  // only y was asked for
-    amax = wave_max(amax);
-    const float qmax = (MM == SDNQ_MM_I8) ? 127.0f : 448.0f;
-    const float scale = amax / qmax;  // IEEE division, as rowquant_kernel
-    if (lane == 0) A.xs[m] = scale;
     RowDiv rd;
-    rd.set(scale);
+    rd.set(row_scale<MM>(amax, lane, A.xs + m));
     uint8_t* qrow = A.xq + m * K;
     int isum = 0;  // (quant8's row sum: unused here)
 #pragma unroll UNR
@@ -207,8 +203,7 @@ __global__ __launch_bounds__(256) void normquant_kernel(const NormQuantArgs A) {
 extern "C" int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int norm, float eps,
                                       const void* weight, const void* bias, int affine_dtype,
                                       const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
-                                      int mm_dtype, void* y, void* xq, float* xs,
-                                      const void* prefetch, int64_t prefetch_bytes, sdnq_stream_t stream) {
+                                      int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream) {
     if (!x || (!xq != !xs) || (!xq && !y)) return SDNQ_ERR_NULL;
     if ((bias && !weight) || (!scale != !shift)) return SDNQ_ERR_NULL;
     if (norm != 0 && norm != 1) return SDNQ_ERR_UNSUPPORTED;
@@ -231,15 +226,9 @@ extern "C" int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int
     a.weight = weight; a.bias = bias; a.scale = scale; a.shift = shift;
     a.rows_per_batch = rows_per_batch; a.ld_mod = ld_mod;
     a.y = y; a.xq = (uint8_t*)xq; a.xs = xs;
-    a.pf = (const uint4*)prefetch;
-    a.pf_vecs = 0;
-    if (prefetch && prefetch_bytes > 0 && ((uintptr_t)prefetch % 16) == 0) {
-        const int64_t cap = (int64_t)32 << 20;  // at most 32 MiB, as sdnq_hip_rowquant
-        a.pf_vecs = (prefetch_bytes < cap ? prefetch_bytes : cap) / 16;
-    }
-    const int pf_blocks = (int)((a.pf_vecs + 256 * 8 - 1) / (256 * 8));
+    a.pf = nullptr; a.pf_vecs = 0;
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)(a.row_blocks + pf_blocks)), block(256);
+    dim3 grid((unsigned)a.row_blocks), block(256);
     const int np = (int)((k + 511) / 512);
 #define NQ_LAUNCH(T, MMV, NPV) hipLaunchKernelGGL((normquant_kernel<T, MMV, NPV>), grid, block, 0, s, a)
 #define NQ_NP(T, MMV)                           \

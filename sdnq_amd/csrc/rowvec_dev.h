@@ -1,9 +1,9 @@
 // How the one-wave-per-row kernels move a row: 8 consecutive elements per lane per 512-element pass, every global access a 16-byte
 // (bf16 / f16) or 2 x 16-byte (f32) lane-contiguous vector.  Shared by the row quantizers (rowquant.hip), the fused normalisation + row
 // quantization (normquant.hip) and the fused activation + row quantization (actquant.hip); the per-element quantizer arithmetic all of
-// them apply is quant8_dev.h.  The write-through code store and the prefetch workgroups at the end of this file serve normquant.hip and
-// actquant.hip.  (The row quantizer's own stay written out in rowquant_kernel: called from here, one instantiation's register
-// allocation and the prefetch block's operand order changed -- profiles/normquant_kernel_compare.txt.)
+// them apply is quant8_dev.h.  The write-through code store, the prefetch workgroups and the row scale at the end of this file serve
+// normquant.hip and actquant.hip.  (The row quantizer's own stay written out in rowquant_kernel: called from here, one instantiation's
+// register allocation and the prefetch block's operand order changed -- profiles/normquant_kernel_compare.txt.)
 #pragma once
 #include "sdnq_dev.h"
 
@@ -62,9 +62,12 @@ __device__ __forceinline__ void store_codes8(uint8_t* dst, const uint2& qv) {
 #endif
 }
 
-// software prefetch of the following GEMM's weight operand, as rowquant_kernel's: the workgroups a launch appends behind its row blocks
-// just stream it once so it sits in the last-level cache (MALL) / L2 when the GEMM's LDS-DMA asks for it.  `block`: index among those workgroups (THREADS
-// threads each); 8 loads in flight per lane.  `sink`: any float the kernel may write (the store never happens: it keeps the loads alive).
+// software prefetch of a following GEMM's weight operand, as rowquant_kernel's: workgroups appended behind a launch's row blocks stream
+// it once into the last-level cache.  The entry points of normquant.hip / actquant.hip take no such operand (pf_vecs is 0, no workgroup
+// is appended): the leading branch of their kernels is never taken.  It stays because the kernels measured slower without it in 6 of
+// 33 cases (profiles/producer_refactor_bench.jsonl, build "operand_removed"; that build also held the wave index in an SGPR, so what
+// the plain removal costs is not measured).  `block`: index among those workgroups (THREADS threads each); `sink`: any float the kernel
+// may write (the store never happens: it keeps the loads alive).
 template <int THREADS = 256>
 __device__ __forceinline__ void prefetch_block(const uint4* __restrict__ pf, int64_t pf_vecs, int64_t block, float* sink) {
     const int64_t base = block * (THREADS * 8) + threadIdx.x;
@@ -75,4 +78,13 @@ __device__ __forceinline__ void prefetch_block(const uint4* __restrict__ pf, int
         if (i < pf_vecs) { const uint4 v = pf[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
     }
     if (acc == 0x9e3779b9u && pf_vecs < 0) sink[0] = 0.0f;  // never true: keeps the loads alive
+}
+
+// the scale of a row whose wave holds per-lane maxima of |y|: amax / qmax of the MM codes, stored by lane 0, returned to every lane
+template <int MM>
+__device__ __forceinline__ float row_scale(float amax, int lane, float* xs) {
+    amax = wave_max(amax);
+    const float scale = amax / ((MM == SDNQ_MM_I8) ? 127.0f : 448.0f);  // IEEE division, as rowquant_kernel
+    if (lane == 0) *xs = scale;
+    return scale;
 }

@@ -226,12 +226,10 @@ _groups = []  # weak references to the live SharedInputGroups (invalidate() reac
 _groups_lock = __import__("threading").Lock()
 
 
-def park_seed(t: torch.Tensor | None, params=None, result=None, producer=None):
-    """A producer of `t` that quantized it in its own launch (norms.SDNQFusedNorm) parks the result where `_rowquant_cached` would have,
-    and names `t` as this thread's seed: a layer that stopped parking (UNSHARED_AFTER) or runs on a C++ plan would otherwise quantize
-    `t` again inside its own launch -- for the seed it looks in the cache first.  None: no seed."""
-    if t is not None:
-        _ts.act_cache.put(t, params, result, producer=producer)
+def park_seed(t: torch.Tensor | None):
+    """Name `t`, whose quantized copy its producer just parked (park_produced), as this thread's seed: a layer that stopped parking
+    (UNSHARED_AFTER) or runs on a C++ plan would otherwise quantize `t` again inside its own launch -- for the seed it looks in the
+    cache first.  None: no seed."""
     _ts.seed = t
     if _FP is not None:
         _FP.set_seed(t)
@@ -266,6 +264,7 @@ def invalidate(tensor: torch.Tensor | None = None):
 def _rowquant_cached(input: torch.Tensor, k: int, mm: int, had: int, want_rowsum: bool, want_xrot: bool, prefetch, asymmetric=False,
                      cache: bool = True):
     # the stream is part of the key: an entry produced on one stream is not ordered against work on another
+    # (park_produced below writes this tuple and `res` for a producer's codes: a field added here is added there)
     params = (mm, had, want_rowsum, want_xrot, asymmetric, ops._stream(input) if input.is_cuda else -1)
     cache = cache and CACHE_ACTIVATIONS > 0
     if cache:
@@ -280,6 +279,16 @@ def _rowquant_cached(input: torch.Tensor, k: int, mm: int, had: int, want_rowsum
     if cache:
         _ts.act_cache.put(input, params, res)
     return res
+
+
+def park_produced(y: torch.Tensor, y2: torch.Tensor, xq: torch.Tensor, xs: torch.Tensor, mm: int, producer):
+    """A module that computed `y` (a view of the rows y2) and quantized it in its own launch (producers.FusedProducer) parks the codes
+    where `_rowquant_cached` above would have: its `params` and `res` for symmetric codes of `mm`, no rotation, no row sum, no rotated
+    copy, on y's current stream -- the layers that receive `y` hit the entry and launch no quantizer.  `y` becomes the seed."""
+    _ts.act_cache.put(y, (mm, 0, False, False, False, ops._stream(y)), (y2, xq, xs, None, None), producer=producer)
+    _ts.seed = y  # (park_seed(y), written out: one call less per producer forward)
+    if _FP is not None:
+        _FP.set_seed(y)
 
 
 class _State:

@@ -17,6 +17,7 @@ import torch
 
 from . import linear as _L
 from . import ops
+from .producers import FuseResult as FuseNormsResult, fuse, unfuse
 
 
 def norm_kind(mod: torch.nn.Module):
@@ -102,60 +103,24 @@ class SDNQFusedNorm(torch.nn.Module):
         seeding = self.__dict__.get("_sdnq_unshared", 0) < _L.UNSHARED_AFTER and _L.CACHE_ACTIVATIONS > 0
         y2, xq, xs = ops.norm_rowquant(x2, self.kind, self._eps(x.dtype), weight, bias, scale, shift, self.mm if seeding else None)
         y = y2.view(x.shape)
-        if seeding:  # the params tuple of linear._rowquant_cached: symmetric codes, no rotation, no rowsum, no rotated copy
-            _L.park_seed(y, (self.mm, 0, False, False, False, ops._stream(y)), (y2, xq, xs, None, None), producer=self)
+        if seeding:
+            _L.park_produced(y, y2, xq, xs, self.mm, self)
         return y
 
 
-class FuseNormsResult(int):
-    """What ``fuse_norms()`` returns: an int (the number of norms wrapped) that also carries ``.fused`` -- their qualified names -- and
-    ``.skipped`` -- [(qualified module name, reason)] of the norms left as they were."""
-
-    def __new__(cls, fused, skipped):
-        r = super().__new__(cls, len(fused))
-        r.fused, r.skipped = list(fused), list(skipped)
-        return r
-
-    def __iter__(self):  # `fused, skipped = fuse_norms(model)`
-        return iter((self.fused, self.skipped))
+def _candidate(mod: torch.nn.Module) -> bool:
+    """What the default walk looks at: the modules ``norm_kind`` could accept and their near misses (they get a sentence)."""
+    return isinstance(mod, torch.nn.LayerNorm) or "rmsnorm" in type(mod).__name__.lower()
 
 
 def fuse_norms(model: torch.nn.Module, targets=None, mm: str = "int8") -> FuseNormsResult:
     """Wrap norm modules of `model` in ``SDNQFusedNorm`` (in place).  `targets`: qualified names, or a predicate ``(name, module) -> bool``;
-    by default every ``LayerNorm`` / RMSNorm-shaped module over one trailing dimension with K % 8 == 0.  `mm`: the matmul dtype of the
-    layers behind the norms ("int8" / "fp8") -- the parked codes serve the layers that quantize to it.  Named targets the kernel cannot
-    stand in for, and by default the norms it cannot, are listed in ``.skipped`` with the reason."""
-    ops.mm_code(mm)
-    mods = dict(model.named_modules())
-    if targets is None or callable(targets):
-        # (a norm inside a wrapper is the wrapper's)
-        names = [n for n, m in mods.items() if n and not isinstance(m, SDNQFusedNorm) and not isinstance(mods.get(n.rpartition(".")[0]), SDNQFusedNorm)
-                 and (targets(n, m) if callable(targets) else isinstance(m, torch.nn.LayerNorm) or "rmsnorm" in type(m).__name__.lower())]
-    else:
-        names = list(targets)
-    fused, skipped = [], []
-    for name in names:
-        mod = mods.get(name)
-        if mod is None or not name:
-            skipped.append((name, "is not a submodule of the model"))
-            continue
-        kind = norm_kind(mod)
-        if isinstance(kind, str):
-            skipped.append((name, kind))
-            continue
-        parent, _, leaf = name.rpartition(".")
-        setattr(mods[parent], leaf, SDNQFusedNorm(mod, mm))
-        fused.append(name)
-    return FuseNormsResult(fused, skipped)
+    by default every ``LayerNorm`` / RMSNorm-shaped module over one trailing dimension with K % 8 == 0 (a norm inside a wrapper is the
+    wrapper's).  `mm`: the matmul dtype of the layers behind the norms ("int8" / "fp8") -- the parked codes serve the layers that quantize
+    to it.  Named targets the kernel cannot stand in for, and by default the norms it cannot, are listed in ``.skipped`` with the reason."""
+    return fuse(model, targets, mm, SDNQFusedNorm, norm_kind, _candidate)
 
 
 def unfuse_norms(model: torch.nn.Module) -> int:
     """Put the wrapped norm modules back; returns how many."""
-    count = 0
-    for parent in list(model.modules()):
-        for leaf, child in list(parent.named_children()):
-            if isinstance(child, SDNQFusedNorm) and not isinstance(parent, SDNQFusedNorm):
-                setattr(parent, leaf, child.norm)
-                count += 1
-    _L.park_seed(None)
-    return count
+    return unfuse(model, SDNQFusedNorm, "norm")

@@ -211,8 +211,15 @@ def rowquant(x2d: torch.Tensor, mm: int, hadamard_group: int = 0, want_rowsum: b
 NORM_LAYER, NORM_RMS = 0, 1
 
 
-def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale, shift, mm: int | None, want_y: bool = True,
-                  prefetch: torch.Tensor | None = None):
+def _produced(m: int, n: int, device, dtype, mm: int | None, want_y: bool):
+    """(y [m,n] of dtype | None, xq [m,n] int8|fp8 | None, xs [m,1] f32 | None): what a producer launch (norm_rowquant, act_rowquant) writes."""
+    y = torch.empty((m, n), device=device, dtype=dtype) if want_y else None
+    if mm is None:
+        return y, None, None
+    return y, torch.empty((m, n), device=device, dtype=_MM_TORCH[mm]), torch.empty((m, 1), device=device, dtype=torch.float32)
+
+
+def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale, shift, mm: int | None, want_y: bool = True):
     """LayerNorm (NORM_LAYER) / RMSNorm (NORM_RMS) of the rows of x2d [M,K] (bf16 / f16), the affine `weight` / `bias` [K] (float32 or
     x2d's dtype, None to skip) and the adaLN modulation ``y * (1 + scale) + shift`` (`scale` / `shift` [B,K] of x2d's dtype with
     M % B == 0, or both None), row-quantized in the same launch -> (y [M,K] | None, xq [M,K] int8|fp8, xs [M,1] f32).  The codes are
@@ -231,13 +238,10 @@ def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale,
             raise _lib.SdnqHipError(f"norm_rowquant: scale and shift must both be [B,{k}] rows of {x2d.dtype} with one stride and B dividing "
                                     f"the {m} rows")
         rows_per_batch, ld_mod = m // scale.shape[0], scale.stride(0) if scale.shape[0] > 1 else max(scale.stride(0), k)
-    y = torch.empty((m, k), device=x2d.device, dtype=x2d.dtype) if want_y else None
-    xq = None if mm is None else torch.empty((m, k), device=x2d.device, dtype=_MM_TORCH[mm])
-    xs = None if mm is None else torch.empty((m, 1), device=x2d.device, dtype=torch.float32)
+    y, xq, xs = _produced(m, k, x2d.device, x2d.dtype, mm, want_y)
     check(_lib.load().sdnq_hip_norm_rowquant(x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), norm, float(eps), _ptr(weight),
                                              _ptr(bias), F32 if weight is None else float_code(weight.dtype), _ptr(scale), _ptr(shift),
-                                             rows_per_batch, ld_mod, MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _ptr(prefetch),
-                                             0 if prefetch is None else prefetch.numel() * prefetch.element_size(), _stream(x2d)),
+                                             rows_per_batch, ld_mod, MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _stream(x2d)),
           "norm_rowquant")
     return y, xq, xs
 
@@ -245,8 +249,7 @@ def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale,
 ACT_GELU, ACT_GELU_TANH, ACT_SILU = 0, 1, 2
 
 
-def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | None, want_y: bool = True,
-                 prefetch: torch.Tensor | None = None):
+def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | None, want_y: bool = True):
     """``act(a) * b`` (`b` None: ``act(a)``) over the rows of a [M,N] (bf16 / f16; ACT_GELU, ACT_GELU_TANH or ACT_SILU), computed in
     float32 with ONE rounding and row-quantized in the same launch -> (y [M,N] | None, xq [M,N] int8|fp8, xs [M,1] f32).  `a` and `b`
     may be row-strided views (the halves of one [M,2N] projection output); N % 8 == 0, pointers and row strides 16-byte aligned.  The
@@ -257,13 +260,10 @@ def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | No
     m, n = a.shape
     if b is not None and (b.shape != a.shape or b.dtype != a.dtype or b.stride(1) != 1 or b.device != a.device):
         raise _lib.SdnqHipError(f"act_rowquant: the multiplier must be [{m},{n}] rows of {a.dtype} on a's device")
-    y = torch.empty((m, n), device=a.device, dtype=a.dtype) if want_y else None
-    xq = None if mm is None else torch.empty((m, n), device=a.device, dtype=_MM_TORCH[mm])
-    xs = None if mm is None else torch.empty((m, 1), device=a.device, dtype=torch.float32)
+    y, xq, xs = _produced(m, n, a.device, a.dtype, mm, want_y)
     check(_lib.load().sdnq_hip_act_rowquant(a.data_ptr(), _ptr(b), float_code(a.dtype), m, n, a.stride(0) if m > 1 else n,
                                             0 if b is None else (b.stride(0) if m > 1 else n), act,
-                                            MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _ptr(prefetch),
-                                            0 if prefetch is None else prefetch.numel() * prefetch.element_size(), _stream(a)),
+                                            MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _stream(a)),
           "act_rowquant")
     return y, xq, xs
 

@@ -50,6 +50,9 @@ def test_targets_kinds_and_unfuse():
     assert set(skipped) == {"quick", "odd", "relu_mlp"} and skipped["odd"] == "N = 24 / 2 is not a multiple of 8"
     assert "is not a GELU / SiLU" in skipped["quick"] and skipped["relu_mlp"].startswith("its act_fn is a ReLU")
     assert fuse_activations(model) == 0 and fuse_activations(model, targets=["act"]).skipped == [("act", "is fused already")]
+    res = fuse_activations(model, targets=["mlp.module.act_fn"])  # inside an existing wrapper: the wrapper's
+    assert res == 0 and res.fused == [] and res.skipped == [] and type(model["mlp"].module.act_fn) is torch.nn.SiLU
+    assert fuse_activations(model, targets=lambda name, mod: name == "act").skipped == [("act", "is fused already")]
     assert unfuse_activations(model) == 3 and all(model[n] is m for n, m in originals.items()) and isinstance(model["ff"][0], GEGLU)
     res = fuse_activations(model, targets=["mlp.act_fn", "ff.2", "nowhere"], mm="fp8")
     assert res.fused == ["mlp.act_fn"] and model["mlp"].act_fn.mm == ops.MM_FP8 and [n for n, _ in res.skipped] == ["ff.2", "nowhere"]
@@ -80,7 +83,7 @@ def test_status_codes_without_gpu():
     p += (-p) % 16
 
     def call(a=p, b=None, x_dtype=1, n=64, lda=64, ldb=0, act=0, mm=0, y=None, xq=p, xs=p):
-        return lib.sdnq_hip_act_rowquant(a, b, x_dtype, 4, n, lda, ldb, act, mm, y, xq, xs, None, 0, None)
+        return lib.sdnq_hip_act_rowquant(a, b, x_dtype, 4, n, lda, ldb, act, mm, y, xq, xs, None)
 
     assert call(a=None) == _lib.ERR_NULL and call(xq=None) == _lib.ERR_NULL and call(xs=None, y=p) == _lib.ERR_NULL
     assert call(x_dtype=0) == _lib.ERR_DTYPE and call(mm=5) == _lib.ERR_DTYPE

@@ -6,7 +6,8 @@ import torch
 
 import sdnq_amd
 from sdnq_amd import _lib, ops
-from sdnq_amd.norms import SDNQFusedNorm, fuse_norms, norm_kind, unfuse_norms
+from sdnq_amd.activations import FuseActivationsResult
+from sdnq_amd.norms import FuseNormsResult, SDNQFusedNorm, fuse_norms, norm_kind, unfuse_norms
 
 
 class LlamaRMSNorm(torch.nn.Module):
@@ -38,6 +39,14 @@ def test_default_targets_names_and_predicate():
     assert "not a LayerNorm or an RMSNorm-shaped module" in res.skipped[0][1] and res.skipped[1][1] == "is not a submodule of the model"
     assert fuse_norms(model, targets=["rms"]).skipped == [("rms", "is fused already")]
     unfuse_norms(model)
+    # a target inside an existing wrapper is the wrapper's: not wrapped a second time, and unfuse_norms restores the original object
+    ln = model["ln"]
+    assert fuse_norms(model) == 3
+    res = fuse_norms(model, targets=["ln.norm"])
+    assert res == 0 and res.fused == [] and res.skipped == [] and model["ln"].norm is ln and type(ln) is torch.nn.LayerNorm
+    assert fuse_norms(model, targets=lambda name, mod: name == "ln").skipped == [("ln", "is fused already")]  # a predicate that matches a wrapper
+    assert unfuse_norms(model) == 3 and model["ln"] is ln
+    assert FuseNormsResult is FuseActivationsResult and isinstance(res, FuseNormsResult)
     assert fuse_norms(model, targets=lambda name, mod: name.startswith("inner")).fused == ["inner.0"]
     with pytest.raises(_lib.SdnqHipError):
         fuse_norms(model, mm="int4")
@@ -74,7 +83,7 @@ def test_status_codes_without_gpu():
     p += (-p) % 16
 
     def call(x=p, x_dtype=1, k=64, ldx=64, norm=0, weight=None, bias=None, affine_dtype=0, scale=None, shift=None, rpb=0, ld_mod=0, mm=0, y=None, xq=p, xs=p):
-        return lib.sdnq_hip_norm_rowquant(x, x_dtype, 4, k, ldx, norm, 1e-5, weight, bias, affine_dtype, scale, shift, rpb, ld_mod, mm, y, xq, xs, None, 0, None)
+        return lib.sdnq_hip_norm_rowquant(x, x_dtype, 4, k, ldx, norm, 1e-5, weight, bias, affine_dtype, scale, shift, rpb, ld_mod, mm, y, xq, xs, None)
 
     assert call(x=None) == _lib.ERR_NULL and call(xq=None) == _lib.ERR_NULL and call(bias=p) == _lib.ERR_NULL and call(scale=p) == _lib.ERR_NULL
     assert call(x_dtype=0) == _lib.ERR_DTYPE and call(mm=5) == _lib.ERR_DTYPE and call(weight=p, affine_dtype=2) == _lib.ERR_DTYPE

@@ -167,6 +167,37 @@ def test_activation_cache_teaches_producers_whether_their_entry_was_used():
     assert b.__dict__["_sdnq_unshared"] < 0   # stays negative: one use by another layer settles it
 
 
+def test_park_produced_stores_the_entry_the_row_quantizer_path_looks_up(monkeypatch):
+    """linear.park_produced writes, for a producer's codes, the params and the result `_rowquant_cached` would have stored for
+    (mm, no rotation, no row sum, no rotated copy, symmetric) on the same stream: the layer behind the producer hits the entry and
+    launches no quantizer.  CPU stand-ins; a field added to one of the two tuples and not the other makes the look-up miss."""
+    import pytest
+    from sdnq_amd import linear as L, ops
+
+    class Producer:
+        pass
+
+    def no_launch(*a, **k):
+        raise AssertionError("the parked entry was not found: _rowquant_cached went on to quantize")
+
+    monkeypatch.setattr(L.ops, "_stream", lambda t: -1)  # (what _rowquant_cached names as the stream of a CPU tensor)
+    monkeypatch.setattr(L.ops, "rowquant", no_launch)
+    monkeypatch.setattr(L, "CACHE_ACTIVATIONS", max(L.CACHE_ACTIVATIONS, 1))
+    L.clear_activation_cache()
+    y2 = torch.zeros(6, 16)
+    y, xq, xs, who = y2.view(2, 3, 16), torch.zeros(6, 16, dtype=torch.int8), torch.ones(6, 1), Producer()
+    try:
+        L.park_produced(y, y2, xq, xs, ops.MM_I8, who)
+        assert L._ts.seed is y and L._ts.act_cache.entries[-1][5] is who
+        hit = L._rowquant_cached(y, 16, ops.MM_I8, 0, False, False, None)
+        assert len(hit) == 5 and hit[0] is y2 and hit[1] is xq and hit[2] is xs and hit[3] is None and hit[4] is None
+        with pytest.raises(AssertionError):  # codes of another matmul dtype, or rotated ones, are another entry
+            L._rowquant_cached(y, 16, ops.MM_FP8, 0, False, False, None)
+    finally:
+        L.clear_activation_cache()
+    assert L._ts.seed is None and not L._ts.act_cache.entries and who.__dict__["_sdnq_unshared"] < 0
+
+
 def test_gpu_skip_allow_list_is_short_and_literal():
     """tests/conftest.py turns any skip of a -m gpu test on a GPU box into a failure unless its reason is allow-listed."""
     from tests import conftest as C
