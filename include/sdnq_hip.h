@@ -183,6 +183,25 @@ int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int64_t k, int
 int sdnq_hip_act_rowquant(const void* a, const void* b, int x_dtype, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act,
                           int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream);
 
+/* ---- the two producers for ROTATED consumers (layers quantized with use_hadamard) --------------------------------------------------
+ * replace, behind a norm / an activation, the reference's rotate_hadamard(input) (quant_utils.py:194-209, called from
+ * linear_int8.py:55-56 / linear_fp8.py) and quantize_int_mm_input / quantize_fp_mm_input (linear_int8.py:15-22, linear_fp8.py:13-20)
+ * of the layers that consume y.  Arguments, checks and y as the plain sibling's -- y has the sibling's bits: rotation changes no
+ * model's y -- plus hadamard_group:
+ *     xs, xq = what sdnq_hip_rowquant(y, mm_dtype, hadamard_group) writes for that y on its default dispatch, bit for bit: the codes
+ *              and the row scale of round_T(rotate_hadamard(y)).
+ * hadamard_group: 0 (the plain sibling's launch), or a power of two in 4 .. 512 that divides the row length (else SDNQ_ERR_SHAPE,
+ * reported after the sibling's own statuses).  Group 256 on rows up to 16384 rotates on the matrix cores as sdnq_hip_rowquant does
+ * (v_mfma_f32_16x16x16), every other group with the butterflies of sdnq_hip_hadamard.  xq / xs NULL with y given: the sibling's launch.
+ * One launch, capturable, no workspace, no atomics.  Not expressible here, so left to sdnq_hip_rowquant on y: rowsum / xrot consumers
+ * (zero-point and SVD layers), asymmetric codes, 16-bit scales; float32 rows are SDNQ_ERR_DTYPE as in the siblings. */
+int sdnq_hip_norm_rowquant_had(const void* x, int x_dtype, int64_t m, int64_t k, int64_t ldx, int norm, float eps,
+                               const void* weight, const void* bias, int affine_dtype,
+                               const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
+                               int mm_dtype, int hadamard_group, void* y, void* xq, float* xs, sdnq_stream_t stream);
+int sdnq_hip_act_rowquant_had(const void* a, const void* b, int x_dtype, int64_t m, int64_t n, int64_t lda, int64_t ldb, int act,
+                              int mm_dtype, int hadamard_group, void* y, void* xq, float* xs, sdnq_stream_t stream);
+
 /* ---- a15/a16: scaled matmul (the operator seam) --------------------------------------------
  * replaces int_scaled_mm_func / fp8_scaled_mm_func (kernel_wrappers.py:193-204) and the Triton op
  * sdnq::scaled_mm (kernels/triton_scaled_mm.py:127-275):

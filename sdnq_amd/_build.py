@@ -46,6 +46,10 @@ UNITS = (
     # actquant.hip (activation + gate product + row quantization in one launch): one by-value struct as well; its multiplies and fmas
     # are written as packed pairs
     ("actquant", "", None),
+    # normquant_had.hip, actquant_had.hip (the two producers for rotated consumers: y, then the codes of rotate_hadamard(y)): one
+    # by-value struct each; the flags of their plain siblings
+    ("normquant_had", "-Xclang -target-feature -Xclang -packed-fp32-ops", None),
+    ("actquant_had", "", None),
     ("gemm", "-DSDNQ_PRELOAD_GEMM " + _PRELOAD, "SDNQ_PRELOAD_GEMM"),
     # the other kernels with scalar arguments get theirs preloaded as well: the GEMM variants, the weight-side units (dequant.hip's
     # dequantizers and re-quantizers, skinny.hip's few-row linears, linear_float.hip's linear_float and lowrank_down), conv_pixel_amax,

@@ -17,7 +17,7 @@ import torch
 
 from . import linear as _L
 from . import ops
-from .producers import FuseResult as FuseActivationsResult, fuse, unfuse
+from .producers import FuseResult as FuseActivationsResult, fuse, hadamard_fit, unfuse
 
 _PLAIN, _PROJ, _MLP = "plain", "proj", "mlp"
 
@@ -76,22 +76,35 @@ def act_kind(mod: torch.nn.Module):
     return "is not a GELU / SiLU, a GEGLU / SwiGLU / GELU with a `proj`, or a gate_proj / up_proj / down_proj MLP"
 
 
+def _out_width(mod: torch.nn.Module, kind):
+    """N of the rows the module's activation writes, where its projection tells (None for a bare ``nn.GELU`` / ``nn.SiLU``)."""
+    shape, _, gated = kind
+    if shape == _PLAIN:
+        return None
+    return mod.gate_proj.out_features if shape == _MLP else mod.proj.out_features // (2 if gated else 1)
+
+
 class SDNQFusedActivation(torch.nn.Module):
     """``module`` (see ``act_kind``) with its activation, gate product and the row quantization of the result in one launch.
 
     Calls the kernel cannot serve run the wrapped module's own forward and park nothing: gradients required, CPU tensors, a dtype other
     than bf16 / f16, a last dimension that is no multiple of 8, inference-mode tensors (no version counter) and
     ``identity_reuse_disabled()``.  When nobody used the parked codes for ``linear.UNSHARED_AFTER`` steps the kernel writes only ``y``
-    from then on."""
+    from then on.  `hadamard_group` > 0: the consumers are layers quantized with ``use_hadamard`` and that ``hadamard_group_size`` --
+    the codes parked are those of the rotated row (``y`` is the same); rows the group does not divide get ``y`` alone and park nothing."""
 
-    def __init__(self, module: torch.nn.Module, mm: str = "int8"):
+    def __init__(self, module: torch.nn.Module, mm: str = "int8", hadamard_group: int = 0):
         super().__init__()
         kind = act_kind(module)
         if isinstance(kind, str):
             raise ValueError(f"SDNQFusedActivation: {type(module).__name__} {kind}")
+        misfit = hadamard_fit(hadamard_group, _out_width(module, kind) or 0)
+        if misfit:
+            raise ValueError(f"SDNQFusedActivation: {misfit}")
         self.module = module
         self.shape, self.act, self.gated = kind
         self.mm = ops.mm_code(mm)
+        self.had = hadamard_group
 
     def _fusable(self, x: torch.Tensor) -> bool:
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() >= 1 and x.numel() > 0):
@@ -112,10 +125,12 @@ class SDNQFusedActivation(torch.nn.Module):
     def _launch(self, a: torch.Tensor, b: torch.Tensor | None, shape) -> torch.Tensor:
         """act(a) * b for 2-D operands -> y viewed as `shape`, its codes parked under y."""
         seeding = self.__dict__.get("_sdnq_unshared", 0) < _L.UNSHARED_AFTER and _L.CACHE_ACTIVATIONS > 0
-        y2, xq, xs = ops.act_rowquant(a, b, self.act, self.mm if seeding else None)
+        if self.had and a.shape[1] % self.had:
+            seeding = False  # (a bare nn.GELU / nn.SiLU on rows the group does not divide: no rotated layer can consume them)
+        y2, xq, xs = ops.act_rowquant(a, b, self.act, self.mm if seeding else None, hadamard_group=self.had)
         y = y2.view(shape)
-        if seeding:
-            _L.park_produced(y, y2, xq, xs, self.mm, self)
+        if xq is not None:
+            _L.park_produced(y, y2, xq, xs, self.mm, self, self.had)
         return y
 
     def forward(self, x: torch.Tensor, *args, **kwargs) -> torch.Tensor:
@@ -140,13 +155,14 @@ def _candidate(mod: torch.nn.Module) -> bool:
             or all(hasattr(mod, a) for a in ("gate_proj", "up_proj", "down_proj")))
 
 
-def fuse_activations(model: torch.nn.Module, targets=None, mm: str = "int8") -> FuseActivationsResult:
+def fuse_activations(model: torch.nn.Module, targets=None, mm: str = "int8", hadamard_group: int = 0) -> FuseActivationsResult:
     """Wrap activation modules of `model` in ``SDNQFusedActivation`` (in place).  `targets`: qualified names, or a predicate
     ``(name, module) -> bool``; by default every module ``act_kind`` recognises, outermost first (the ``act_fn`` of a wrapped MLP is the
     wrapper's).  `mm`: the matmul dtype of the layers behind the activations ("int8" / "fp8") -- the parked codes serve the layers that
-    quantize to it.  Named targets the kernel cannot stand in for, and by default the near misses, are listed in ``.skipped`` with the
-    reason."""
-    return fuse(model, targets, mm, SDNQFusedActivation, act_kind, _candidate)
+    quantize to it.  `hadamard_group`: the ``hadamard_group_size`` of those layers when they were quantized with ``use_hadamard`` (the
+    parked codes are then those of the rotated row), 0 for un-rotated layers.  Named targets the kernel cannot stand in for, by default
+    the near misses, and modules whose N the group cannot rotate are listed in ``.skipped`` with the reason."""
+    return fuse(model, targets, mm, SDNQFusedActivation, act_kind, _candidate, hadamard_group, _out_width)
 
 
 def unfuse_activations(model: torch.nn.Module) -> int:

@@ -17,6 +17,7 @@
 // codes (same inputs, same operations: the same bits).  No LDS.
 // Every sum runs in a fixed order -- 8 per-lane accumulators over the passes, a tree over the 8, the xor butterfly over the lanes -- and
 // a row never leaves its wave, so a row's bits do not depend on M or the grid.
+#include "normquant_dev.h"
 #include "quant8_dev.h"
 #include "rowvec_dev.h"
 #include "sdnq_dev.h"
@@ -41,50 +42,6 @@ struct NormQuantArgs {
     const uint4* pf;         // NULL / 0: no entry point takes a prefetch operand (rowvec_dev.h: prefetch_block)
     int64_t pf_vecs;
 };
-
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    return __int_as_float(wave_allreduce_i32(__float_as_int(v), [](int a, int b) { return __float_as_int(__int_as_float(a) + __int_as_float(b)); }));
-}
-__device__ __forceinline__ float tree8(const float (&a)[8]) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
-
-// 8 consecutive elements of a per-row vector (weight, bias: float32 or the row dtype; scale, shift: the row dtype) as floats
-template <int T_ID>
-__device__ __forceinline__ void load_vec8(const void* p, int64_t i, bool f32, float (&o)[8]) {
-    if (f32) {  // wave-uniform
-        Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p + i), o);
-        Vec16<SDNQ_F32>::unpack(*(const uint4*)((const float*)p + i + 4), o + 4);
-    } else {
-        Vec16<T_ID>::unpack(*(const uint4*)((const uint16_t*)p + i), o);
-    }
-}
-
-// what a row's elements need once its statistics are known (every branch below is wave-uniform)
-struct RowNorm {
-    float mean, r;
-    const void *weight, *bias, *scale, *shift;  // the modulation rows of this row's batch
-    bool aff_f32;
-};
-
-// y = round_T(modulate(affine((x - mean) * r))) for the 8 elements at `idx`; lanes past the end of the row get zeros
-template <int T_ID>
-__device__ __forceinline__ void norm8(const float (&x)[8], int64_t idx, bool ok, const RowNorm& c, float (&y)[8]) {
-    const int64_t i = ok ? idx : 0;
-    float w[8], b[8], sc[8], sh[8];
-    if (c.weight) load_vec8<T_ID>(c.weight, i, c.aff_f32, w);
-    if (c.bias) load_vec8<T_ID>(c.bias, i, c.aff_f32, b);
-    if (c.scale) {
-        load_vec8<T_ID>(c.scale, i, false, sc);
-        load_vec8<T_ID>(c.shift, i, false, sh);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        float a = (x[e] - c.mean) * c.r;
-        if (c.bias) a = fmaf(a, w[e], b[e]);
-        else if (c.weight) a = a * w[e];
-        if (c.scale) a = fmaf(a, 1.0f + sc[e], sh[e]);
-        y[e] = ok ? FT<T_ID>::round(a) : 0.0f;
-    }
-}
 
 // T_ID: row dtype (bf16 / f16); MM: SdnqMM; NP: 512-element passes of the row held in registers (K <= NP * 512), 0: the sweep form
 template <int T_ID, int MM, int NP>
@@ -204,20 +161,9 @@ extern "C" int sdnq_hip_norm_rowquant(const void* x, int x_dtype, int64_t m, int
                                       const void* weight, const void* bias, int affine_dtype,
                                       const void* scale, const void* shift, int64_t rows_per_batch, int64_t ld_mod,
                                       int mm_dtype, void* y, void* xq, float* xs, sdnq_stream_t stream) {
-    if (!x || (!xq != !xs) || (!xq && !y)) return SDNQ_ERR_NULL;
-    if ((bias && !weight) || (!scale != !shift)) return SDNQ_ERR_NULL;
-    if (norm != 0 && norm != 1) return SDNQ_ERR_UNSUPPORTED;
-    if (norm == 1 && bias) return SDNQ_ERR_UNSUPPORTED;  // RMSNorm has no bias
-    if (x_dtype != SDNQ_BF16 && x_dtype != SDNQ_F16) return SDNQ_ERR_DTYPE;  // float32 rows: not built
-    if (mm_dtype != SDNQ_MM_I8 && mm_dtype != SDNQ_MM_FP8) return SDNQ_ERR_DTYPE;
-    if (weight && affine_dtype != SDNQ_F32 && affine_dtype != x_dtype) return SDNQ_ERR_DTYPE;
-    if (m <= 0 || k <= 0 || (k % 8) != 0 || ldx < k || k >= ((int64_t)1 << 24)) return SDNQ_ERR_SHAPE;
-    if (!(eps >= 0.0f)) return SDNQ_ERR_SHAPE;
-    if (scale && (rows_per_batch <= 0 || (m % rows_per_batch) != 0 || ld_mod < k)) return SDNQ_ERR_SHAPE;
-    if (((uintptr_t)x % 16) || ((ldx * 2) % 16) || ((uintptr_t)xq % 16) || ((uintptr_t)xs % 4) || ((uintptr_t)y % 16) ||
-        ((uintptr_t)weight % 16) || ((uintptr_t)bias % 16) || ((uintptr_t)scale % 16) || ((uintptr_t)shift % 16) ||
-        (scale && ((ld_mod * 2) % 16)))
-        return SDNQ_ERR_ALIGN;
+    const int st = norm_rowquant_check(x, x_dtype, m, k, ldx, norm, eps, weight, bias, affine_dtype, scale, shift, rows_per_batch, ld_mod, mm_dtype,
+                                       y, xq, xs);
+    if (st != SDNQ_OK) return st;
     NormQuantArgs a;
     a.x = x; a.M = m; a.K = k; a.ldx = ldx;
     a.row_blocks = (int)((m + 3) / 4);

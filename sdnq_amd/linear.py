@@ -281,11 +281,16 @@ def _rowquant_cached(input: torch.Tensor, k: int, mm: int, had: int, want_rowsum
     return res
 
 
-def park_produced(y: torch.Tensor, y2: torch.Tensor, xq: torch.Tensor, xs: torch.Tensor, mm: int, producer):
+def park_produced(y: torch.Tensor, y2: torch.Tensor, xq: torch.Tensor, xs: torch.Tensor, mm: int, producer, had: int = 0):
     """A module that computed `y` (a view of the rows y2) and quantized it in its own launch (producers.FusedProducer) parks the codes
-    where `_rowquant_cached` above would have: its `params` and `res` for symmetric codes of `mm`, no rotation, no row sum, no rotated
-    copy, on y's current stream -- the layers that receive `y` hit the entry and launch no quantizer.  `y` becomes the seed."""
-    _ts.act_cache.put(y, (mm, 0, False, False, False, ops._stream(y)), (y2, xq, xs, None, None), producer=producer)
+    where `_rowquant_cached` above would have: its `params` and `res` for symmetric codes of `mm`, rotated in Hadamard groups of `had`
+    (0: not rotated), no row sum, no rotated copy, on y's current stream -- the layers that receive `y` hit the entry and launch no
+    quantizer.  `y` becomes the seed.  A rotated layer (``use_hadamard``) is never on a C++ plan; on the Python path it looks the
+    tuple up with its own group as `had`: the plain w8a8 layer (K <= 5120, no SVD, no zero point) inline in `_quantized_matmul_forward`,
+    in front of ``ops.linear_w8a8``; longer rows in front of ``ops.linear_call``; the 4-bit per-call route and mixed SVD dtypes in
+    `_rowquant_cached`.  tests/test_producer_hadamard_gpu.py observes the hit of the first on the parked entry's flag.  A layer that also
+    wants the row sum or the rotated copy (zero point, SVD), or is rotated in another group, looks up another key and quantizes for itself."""
+    _ts.act_cache.put(y, (mm, had, False, False, False, ops._stream(y)), (y2, xq, xs, None, None), producer=producer)
     _ts.seed = y  # (park_seed(y), written out: one call less per producer forward)
     if _FP is not None:
         _FP.set_seed(y)

@@ -17,7 +17,7 @@ import torch
 
 from . import linear as _L
 from . import ops
-from .producers import FuseResult as FuseNormsResult, fuse, unfuse
+from .producers import FuseResult as FuseNormsResult, fuse, hadamard_fit, unfuse
 
 
 def norm_kind(mod: torch.nn.Module):
@@ -47,16 +47,22 @@ class SDNQFusedNorm(torch.nn.Module):
 
     Calls the kernel cannot serve run the wrapped module's own forward and park nothing: gradients required, CPU tensors, a dtype other
     than bf16 / f16 or than the affine parameters', inference-mode tensors (no version counter) and ``identity_reuse_disabled()``.
-    When nobody used the parked codes for ``linear.UNSHARED_AFTER`` steps the kernel writes only ``y`` from then on."""
+    When nobody used the parked codes for ``linear.UNSHARED_AFTER`` steps the kernel writes only ``y`` from then on.
+    `hadamard_group` > 0: the consumers are layers quantized with ``use_hadamard`` and that ``hadamard_group_size`` -- the codes parked
+    are those of the rotated row (``y`` is the same)."""
 
-    def __init__(self, norm: torch.nn.Module, mm: str = "int8"):
+    def __init__(self, norm: torch.nn.Module, mm: str = "int8", hadamard_group: int = 0):
         super().__init__()
         kind = norm_kind(norm)
         if isinstance(kind, str):
             raise ValueError(f"SDNQFusedNorm: {type(norm).__name__} {kind}")
+        misfit = hadamard_fit(hadamard_group, kind[1])
+        if misfit:
+            raise ValueError(f"SDNQFusedNorm: {misfit}")
         self.norm = norm
         self.kind, self.k = kind
         self.mm = ops.mm_code(mm)
+        self.had = hadamard_group
 
     def _eps(self, dtype: torch.dtype) -> float:
         eps = getattr(self.norm, "eps", None)
@@ -101,10 +107,11 @@ class SDNQFusedNorm(torch.nn.Module):
             weight = weight.detach().contiguous()
             bias = None if bias is None else bias.detach().contiguous()
         seeding = self.__dict__.get("_sdnq_unshared", 0) < _L.UNSHARED_AFTER and _L.CACHE_ACTIVATIONS > 0
-        y2, xq, xs = ops.norm_rowquant(x2, self.kind, self._eps(x.dtype), weight, bias, scale, shift, self.mm if seeding else None)
+        y2, xq, xs = ops.norm_rowquant(x2, self.kind, self._eps(x.dtype), weight, bias, scale, shift, self.mm if seeding else None,
+                                       hadamard_group=self.had)
         y = y2.view(x.shape)
-        if seeding:
-            _L.park_produced(y, y2, xq, xs, self.mm, self)
+        if xq is not None:
+            _L.park_produced(y, y2, xq, xs, self.mm, self, self.had)
         return y
 
 
@@ -113,12 +120,15 @@ def _candidate(mod: torch.nn.Module) -> bool:
     return isinstance(mod, torch.nn.LayerNorm) or "rmsnorm" in type(mod).__name__.lower()
 
 
-def fuse_norms(model: torch.nn.Module, targets=None, mm: str = "int8") -> FuseNormsResult:
+def fuse_norms(model: torch.nn.Module, targets=None, mm: str = "int8", hadamard_group: int = 0) -> FuseNormsResult:
     """Wrap norm modules of `model` in ``SDNQFusedNorm`` (in place).  `targets`: qualified names, or a predicate ``(name, module) -> bool``;
     by default every ``LayerNorm`` / RMSNorm-shaped module over one trailing dimension with K % 8 == 0 (a norm inside a wrapper is the
     wrapper's).  `mm`: the matmul dtype of the layers behind the norms ("int8" / "fp8") -- the parked codes serve the layers that quantize
-    to it.  Named targets the kernel cannot stand in for, and by default the norms it cannot, are listed in ``.skipped`` with the reason."""
-    return fuse(model, targets, mm, SDNQFusedNorm, norm_kind, _candidate)
+    to it.  `hadamard_group`: the ``hadamard_group_size`` of those layers when they were quantized with ``use_hadamard`` (the parked codes
+    are then those of the rotated row; a layer of another rotation quantizes for itself), 0 for un-rotated layers.  Named targets the
+    kernel cannot stand in for, by default the norms it cannot, and norms whose K the group cannot rotate are listed in ``.skipped`` with
+    the reason."""
+    return fuse(model, targets, mm, SDNQFusedNorm, norm_kind, _candidate, hadamard_group, lambda mod, kind: kind[1])
 
 
 def unfuse_norms(model: torch.nn.Module) -> int:

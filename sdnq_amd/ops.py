@@ -219,11 +219,14 @@ def _produced(m: int, n: int, device, dtype, mm: int | None, want_y: bool):
     return y, torch.empty((m, n), device=device, dtype=_MM_TORCH[mm]), torch.empty((m, 1), device=device, dtype=torch.float32)
 
 
-def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale, shift, mm: int | None, want_y: bool = True):
+def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale, shift, mm: int | None, want_y: bool = True,
+                  hadamard_group: int = 0):
     """LayerNorm (NORM_LAYER) / RMSNorm (NORM_RMS) of the rows of x2d [M,K] (bf16 / f16), the affine `weight` / `bias` [K] (float32 or
     x2d's dtype, None to skip) and the adaLN modulation ``y * (1 + scale) + shift`` (`scale` / `shift` [B,K] of x2d's dtype with
     M % B == 0, or both None), row-quantized in the same launch -> (y [M,K] | None, xq [M,K] int8|fp8, xs [M,1] f32).  The codes are
-    the bits ``rowquant(y, mm)`` gives for the y this returns; ``want_y=False`` never writes y, ``mm=None`` only y (xq, xs: None)."""
+    the bits ``rowquant(y, mm, hadamard_group)`` gives for the y this returns -- `hadamard_group` > 0: the codes of the ROTATED row, for
+    layers quantized with ``use_hadamard`` (sdnq_hip_norm_rowquant_had; y does not depend on it); ``want_y=False`` never writes y,
+    ``mm=None`` only y (xq, xs: None)."""
     _require_cuda(x2d, weight, bias, scale, shift)
     assert x2d.ndim == 2 and x2d.stride(1) == 1
     m, k = x2d.shape
@@ -239,32 +242,51 @@ def norm_rowquant(x2d: torch.Tensor, norm: int, eps: float, weight, bias, scale,
                                     f"the {m} rows")
         rows_per_batch, ld_mod = m // scale.shape[0], scale.stride(0) if scale.shape[0] > 1 else max(scale.stride(0), k)
     y, xq, xs = _produced(m, k, x2d.device, x2d.dtype, mm, want_y)
-    check(_lib.load().sdnq_hip_norm_rowquant(x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), norm, float(eps), _ptr(weight),
-                                             _ptr(bias), F32 if weight is None else float_code(weight.dtype), _ptr(scale), _ptr(shift),
-                                             rows_per_batch, ld_mod, MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _stream(x2d)),
-          "norm_rowquant")
+    head = (x2d.data_ptr(), float_code(x2d.dtype), m, k, x2d.stride(0), norm, float(eps), _ptr(weight), _ptr(bias),
+            F32 if weight is None else float_code(weight.dtype), _ptr(scale), _ptr(shift), rows_per_batch, ld_mod, MM_I8 if mm is None else mm)
+    if hadamard_group and mm is not None:
+        st = _lib.load().sdnq_hip_norm_rowquant_had(*head, hadamard_group, _ptr(y), _ptr(xq), _ptr(xs), _stream(x2d))
+        if st != _lib.ERR_UNSUPPORTED:
+            check(st, "norm_rowquant_had")
+            return y, xq, xs
+        if not want_y:
+            check(st, "norm_rowquant_had")
+        # "not built": y alone, the consumer quantizes for itself.  No rotated form answers so today -- the entry points build every group
+        # they accept, and a norm / an activation they do not know gets the same status from the plain call below, which raises
+        xq = xs = None
+    check(_lib.load().sdnq_hip_norm_rowquant(*head, _ptr(y), _ptr(xq), _ptr(xs), _stream(x2d)), "norm_rowquant")
     return y, xq, xs
 
 
 ACT_GELU, ACT_GELU_TANH, ACT_SILU = 0, 1, 2
 
 
-def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | None, want_y: bool = True):
+def act_rowquant(a: torch.Tensor, b: torch.Tensor | None, act: int, mm: int | None, want_y: bool = True, hadamard_group: int = 0):
     """``act(a) * b`` (`b` None: ``act(a)``) over the rows of a [M,N] (bf16 / f16; ACT_GELU, ACT_GELU_TANH or ACT_SILU), computed in
     float32 with ONE rounding and row-quantized in the same launch -> (y [M,N] | None, xq [M,N] int8|fp8, xs [M,1] f32).  `a` and `b`
     may be row-strided views (the halves of one [M,2N] projection output); N % 8 == 0, pointers and row strides 16-byte aligned.  The
-    codes are the bits ``rowquant(y, mm)`` gives for the y this returns; ``want_y=False`` never writes y, ``mm=None`` only y (xq, xs:
-    None)."""
+    codes are the bits ``rowquant(y, mm, hadamard_group)`` gives for the y this returns -- `hadamard_group` > 0: the codes of the ROTATED
+    row, for layers quantized with ``use_hadamard`` (sdnq_hip_act_rowquant_had; y does not depend on it); ``want_y=False`` never writes
+    y, ``mm=None`` only y (xq, xs: None)."""
     _require_cuda(a, b)
     assert a.ndim == 2 and a.stride(1) == 1
     m, n = a.shape
     if b is not None and (b.shape != a.shape or b.dtype != a.dtype or b.stride(1) != 1 or b.device != a.device):
         raise _lib.SdnqHipError(f"act_rowquant: the multiplier must be [{m},{n}] rows of {a.dtype} on a's device")
     y, xq, xs = _produced(m, n, a.device, a.dtype, mm, want_y)
-    check(_lib.load().sdnq_hip_act_rowquant(a.data_ptr(), _ptr(b), float_code(a.dtype), m, n, a.stride(0) if m > 1 else n,
-                                            0 if b is None else (b.stride(0) if m > 1 else n), act,
-                                            MM_I8 if mm is None else mm, _ptr(y), _ptr(xq), _ptr(xs), _stream(a)),
-          "act_rowquant")
+    head = (a.data_ptr(), _ptr(b), float_code(a.dtype), m, n, a.stride(0) if m > 1 else n,
+            0 if b is None else (b.stride(0) if m > 1 else n), act, MM_I8 if mm is None else mm)
+    if hadamard_group and mm is not None:
+        st = _lib.load().sdnq_hip_act_rowquant_had(*head, hadamard_group, _ptr(y), _ptr(xq), _ptr(xs), _stream(a))
+        if st != _lib.ERR_UNSUPPORTED:
+            check(st, "act_rowquant_had")
+            return y, xq, xs
+        if not want_y:
+            check(st, "act_rowquant_had")
+        # "not built": y alone, the consumer quantizes for itself.  No rotated form answers so today -- the entry points build every group
+        # they accept, and a norm / an activation they do not know gets the same status from the plain call below, which raises
+        xq = xs = None
+    check(_lib.load().sdnq_hip_act_rowquant(*head, _ptr(y), _ptr(xq), _ptr(xs), _stream(a)), "act_rowquant")
     return y, xq, xs
 
 

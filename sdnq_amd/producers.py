@@ -25,10 +25,21 @@ class FuseResult(int):
         return iter((self.fused, self.skipped))
 
 
-def fuse(model: torch.nn.Module, targets, mm: str, wrapper, kind_of, candidate) -> FuseResult:
+def hadamard_fit(hadamard_group: int, k: int):
+    """None if rows of `k` elements can be rotated in Hadamard groups of `hadamard_group` (0: no rotation), else a sentence: the rule of
+    the library's ``hadamard_log2``."""
+    g = hadamard_group
+    if g == 0 or (isinstance(g, int) and 4 <= g <= 512 and not g & (g - 1) and k % g == 0):
+        return None
+    return f"hadamard_group = {g} is not a power of two in 4 .. 512 that divides the row length {k}"
+
+
+def fuse(model: torch.nn.Module, targets, mm: str, wrapper, kind_of, candidate, hadamard_group: int = 0, width=None) -> FuseResult:
     """Wrap modules of `model` in `wrapper` (in place).  `targets`: qualified names, or a predicate ``(name, module) -> bool``, else
     every module `candidate(module)` accepts.  `kind_of(module)` is a sentence for a module `wrapper` cannot stand in for.  A target
-    below a wrapped (or just-wrapped) module is that wrapper's and is dropped."""
+    below a wrapped (or just-wrapped) module is that wrapper's and is dropped.  `hadamard_group` > 0: the wrappers park the codes of the
+    rotated row; `width(module, kind)` is the row length a module's output is known to have (None: known only at its forward) and a
+    module whose rows the group cannot rotate is skipped with a sentence."""
     ops.mm_code(mm)
     mods = dict(model.named_modules())
     if targets is None or callable(targets):
@@ -48,8 +59,13 @@ def fuse(model: torch.nn.Module, targets, mm: str, wrapper, kind_of, candidate) 
         if isinstance(kind, str):
             skipped.append((name, kind))
             continue
+        k = width(mod, kind) if hadamard_group and width is not None else None
+        misfit = hadamard_fit(hadamard_group, 0 if k is None else k)
+        if misfit:
+            skipped.append((name, misfit))
+            continue
         parent, _, leaf = name.rpartition(".")
-        setattr(mods[parent], leaf, wrapper(mod, mm))
+        setattr(mods[parent], leaf, wrapper(mod, mm, hadamard_group))
         fused.append(name)
     return FuseResult(fused, skipped)
 
